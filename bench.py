@@ -7,10 +7,16 @@ batch 32 per GPU, fp32 tensors and results (BASELINE.json configs[1]; synthetic 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-``roofline`` (dominant kernel = an implicit-GEMM conv kernel; algorithmic FLOP / HIP-event time measured inside the timed
-region, priced against the peak of the MFMA instruction it issues) and ``cpu_baseline`` (the CPU oracle timed on this
-box's host cores, N=1 only).
+Prints ONE JSON line on rank 0: ``metric``, ``value`` (clips/s over the timed steps), ``unit``, ``higher_is_better``,
+``dtype``, ``ms_per_step`` (wall time of one timed step) and ``config``.  A plain run sets up, warms up, times ``--steps``
+steps and prints that line, nothing more.
+
+``--full`` adds what takes runs or steps of its own: ``roofline`` (dominant kernel = an implicit-GEMM conv kernel; algorithmic
+FLOP / HIP-event time measured inside the timed region, priced against the peak of the MFMA instruction it issues),
+``alt_arith`` (the same step timed again in the 'bf16x2' arithmetic) and ``cpu_baseline`` (the CPU oracle timed on the
+host cores, N=1 only).
+
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float32): see ``dump_outputs``.
 """
 import argparse
 import copy
@@ -215,6 +221,41 @@ def cpu_baseline(depth, num_classes, head, loss, budget_s=25.0):
                        f'(torch {torch.__version__} CPU, fp32)')
 
 
+DUMP_MAX_BYTES = 64 * 2**20
+DUMP_SAMPLE = 4 * 2**20            # elements per sampled array: two of them (state, gradients) = 32 MiB of float32
+
+
+def dump_outputs(path, out, model, train):
+    """What the last timed step handed its caller, as float32 ``.npy`` files under ``path``: every floating tensor of the step's
+    result dict (``<key>.npy``: the losses; logits and representations for 'predict') and, for a training step, the model it
+    updated in place -- ``state_sample.npy``, a fixed sample of the floating ``state_dict()`` entries (parameters after the SGD
+    step, BatchNorm running statistics) concatenated in ``state_dict()`` order, and ``grad_sample.npy``, the same for the
+    parameter gradients of the step (zeros where a parameter got none).  The sample indices come from a seeded permutation, so
+    two runs with the same arguments dump the same elements."""
+    import re
+
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v) and v.is_floating_point():
+            arrays[re.sub(r'[^A-Za-z0-9_.-]', '_', k)] = v.detach().float().cpu().numpy()
+    if train:
+        state = [v.detach().reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()]
+        grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in model.parameters()]
+        for name, parts in (('state_sample', state), ('grad_sample', grads)):
+            flat = torch.cat(parts)
+            if flat.numel() > DUMP_SAMPLE:
+                idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+                flat = flat[idx.to(flat.device)]
+            arrays[name] = flat.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit')
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f'{name}.npy'), a)
+
+
 _JSON_FD = None
 
 
@@ -309,6 +350,11 @@ def main():
                          "LSCLoss, feature-KD against a frozen previous model (task >= 1), clip 1.0, SGD; 'predict': eval forward "
                          "+ representations of BaseCIL.predict_step (SURVEY section 8(f) rank 1), no backward; 'i3d': BASELINE config 4, "
                          "I3D-ResNet50 fwd+bwd+SGD on 32x3x224x224 clips (default batch 16)")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what a plain run leaves out: the per-kernel table and `roofline`, the `alt_arith` run and '
+                         'the `cpu_baseline` (each can still be dropped with its --no-* option)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed to DIR/<name>.npy (float32, <= 64 MiB)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--arith', default='bf16x3', choices=['bf16x3', 'f32mfma', 'bf16x2', 'bf16x1', 'bf16'],
@@ -321,6 +367,10 @@ def main():
                          "MFMA products; reported under `alt_arith`, never as `value`)")
     ap.add_argument('--selftest-cpu', action='store_true', help=argparse.SUPPRESS)   # launcher test: gloo ranks, no GPU
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not args.full:                          # a plain run: the headline line only
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_alt_arith = True
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # Started without a launcher: this process has not touched the GPU (importing torch does not), so it may start
@@ -389,7 +439,7 @@ def main():
         class _Predict:                       # same interface as TrainEngine.step for the timing loop below
             def step(self, b, _loss_fn=None):
                 r = predictor.predict_step(b)
-                return {'loss_cls': r['cls_score'].sum() * 0.0, 'repr_': r['repr_']}
+                return dict(r, loss_cls=r['cls_score'].sum() * 0.0)
         engine = _Predict()
 
     g = torch.Generator().manual_seed(1000 + rank)
@@ -478,10 +528,12 @@ def main():
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     timer.enabled = False
     loss_val = float(out['loss_cls'].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model, train=not predict)
 
-    # The same step once more in the 'bf16x2' arithmetic (16 significand bits per operand, three MFMA products instead of six):
-    # a second record beside the headline, which stays the fp32-level arithmetic.  Same model configuration, batch, warm-up and
-    # step count, same barrier + synchronize bracket, max over ranks.
+    # --full: the same step once more in the 'bf16x2' arithmetic (16 significand bits per operand, three MFMA products instead of
+    # six): a second record beside the headline, which stays the fp32-level arithmetic.  Same model configuration, batch, warm-up
+    # and step count, same barrier + synchronize bracket, max over ranks.
     alt = None
     if args.arith == 'bf16x3' and not (cil or predict or i3d or args.no_alt_arith):
         K.set_conv_arith('bf16x2')
