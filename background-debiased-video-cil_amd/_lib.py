@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # is then the caller's business
 _OVERRIDE = os.environ.get('BDVCIL_LIB_PATH')
 LIB_PATH = _OVERRIDE or os.path.join(_HERE, 'csrc', 'libbdvcil_hip.so')
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _lib = None
 
@@ -110,6 +110,12 @@ SIGNATURES = {
     'bdv_jpeg_entropy_decode_batch': (c_int, [P, P, c_int, POINTER(JpegInfo), P, P, c_int]),
     'bdv_jpeg_workspace_bytes': (c_size_t, [POINTER(JpegInfo), c_int]),
     'bdv_jpeg_reconstruct_u8': (c_int, [P, P, POINTER(JpegInfo), c_int, P, c_size_t, P, P]),
+    'bdv_temporal_median_u8': (c_int, [P, c_int64, P, P, P, P, c_int, c_int, c_int, P, P]),
+    'bdv_jpeg_encode_info': (c_int, [c_int, c_int, c_int, POINTER(JpegInfo)]),
+    'bdv_jpeg_forward_u8': (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
+    'bdv_jpeg_encode_bound': (c_size_t, [c_int, c_int]),
+    'bdv_jpeg_entropy_encode': (c_int, [P, c_int, c_int, c_int, P, c_size_t, P]),
+    'bdv_jpeg_entropy_encode_batch': (c_int, [P, c_int, c_int, c_int, c_int, P, c_size_t, P, c_int]),
     'bdv_crop_normalize_u8': (c_int, [P, P, c_int, c_int, c_int, _F3, _F3, P, P, c_int, c_int, c_int, c_int, P]),
     'bdv_lsc_fwd': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     'bdv_lsc_bwd': (c_int, [P, P, P, P, P, P, P, P, c_float, P, c_int, c_int, c_int, c_int, P]),
@@ -146,7 +152,7 @@ class HipExtensionError(RuntimeError):
 
 
 HASHED_SOURCES = ('conv_mfma.hip', 'bn.hip', 'pool_frontend.hip', 'head_loss.hip', 'repr.hip', 'augment.hip', 'optim.hip', 'jpeg.hip',
-                  'api_common.cpp', 'common.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
+                  'background.hip', 'api_common.cpp', 'common.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
 
 
 def source_hash():

@@ -192,6 +192,11 @@ class RawFrameClipLoader:
         self.bg_files, self.bg_video_infos = (list(bg_files) if bg_files else None), bg_video_infos
         self.input_size = int(input_size)
 
+    def set_bg_files(self, bg_files: Sequence[str]) -> None:
+        """The background list of the dataset being trained on (``CILTaskLoop`` calls this before each fit when the config names
+        a ``bg_dir``); an empty list means the random-frame fallback."""
+        self.bg_files = list(bg_files) if bg_files else None
+
     # ---- host side ------------------------------------------------------------------------------------------------------------
     def _read(self, path: str) -> bytes:
         with open(path, 'rb') as f:
@@ -266,8 +271,16 @@ class PrefetchLoader:
         self.stream = torch.cuda.Stream()
         self.pool = ThreadPoolExecutor(max_workers=1)
         self.queue = []
+        self._bg_files = None           # set_bg_files: the list handed to the loader with each batch submitted after it
 
-    def _work(self, video_infos, phase):
+    def set_bg_files(self, bg_files: Sequence[str]) -> None:
+        """Forwarded to the loader; takes effect from the next submitted batch (batches already queued keep the list they were
+        submitted with)."""
+        self._bg_files = list(bg_files) if bg_files is not None else []
+
+    def _work(self, video_infos, phase, bg_files=None):
+        if bg_files is not None and hasattr(self.loader, 'set_bg_files'):
+            self.loader.set_bg_files(bg_files)
         with torch.cuda.stream(self.stream):
             batch = self.loader(video_infos, phase)
             ev = torch.cuda.Event()
@@ -275,7 +288,7 @@ class PrefetchLoader:
         return batch, ev
 
     def submit(self, video_infos, phase: str):
-        self.queue.append(self.pool.submit(self._work, video_infos, phase))
+        self.queue.append(self.pool.submit(self._work, video_infos, phase, self._bg_files))
 
     def get(self):
         batch, ev = self.queue.pop(0).result()

@@ -150,6 +150,7 @@ class RawframeRecords:
         self.phase = phase
         self.video_infos: List[dict] = []
         self.bg_files: List[str] = []
+        self.merge_bg_files = True       # BackgroundMixDataset(merge_bg_files=...): extend() also appends the others' backgrounds
         if ann_file:
             for rel, total, label in read_ann_file(ann_file):
                 frame_dir = osp.join(self.data_prefix, rel) if self.data_prefix is not None else rel
@@ -159,9 +160,12 @@ class RawframeRecords:
         return len(self.video_infos)
 
     def extend(self, others: Union['RawframeRecords', Iterable['RawframeRecords']]):
-        """``CILDataModule.merge_dataset`` (libs/cil/cil.py:377-407): video_infos are appended in order."""
+        """``CILDataModule.merge_dataset`` (libs/cil/cil.py:377-407): video_infos are appended in order, and the others'
+        ``bg_files`` when ``merge_bg_files``."""
         for o in ([others] if isinstance(others, RawframeRecords) else others):
             self.video_infos.extend(o.video_infos)
+            if self.merge_bg_files:
+                self.bg_files.extend(o.bg_files)
         return self
 
 
@@ -243,6 +247,11 @@ class CILWorkDir:
 
 
 # ---- batches ----------------------------------------------------------------------------------------------------------
+
+def _first_seen(paths: Iterable[str]) -> List[str]:
+    """The distinct paths in first-seen order (the reference keeps these lists in a ``set``, whose order depends on hashing)."""
+    return list(dict.fromkeys(paths))
+
 
 def epoch_batches(n: int, batch_size: int, shuffle: bool, generator: Optional[torch.Generator] = None, rank: int = 0,
                   world: int = 1) -> List[List[int]]:
@@ -359,6 +368,7 @@ class CILTaskLoop:
         self.optimizer_mode = 'default'
         self.current_best = 0 if config.get('save_best', False) else None
         self.history: List[Dict] = []
+        self._all_bg_files: Dict[str, None] = {}       # keep_all_backgrounds (libs/cil/cil.py:62), an ordered set
 
         # models (libs/cil/cil.py:429-452): current + frozen previous copy, hooks for KD / representation
         self.current_model = build_model(config.model).to(self.device)
@@ -412,18 +422,45 @@ class CILTaskLoop:
     def exemplar_size(self) -> int:
         return sum(len(e) for e in self.exemplar_datasets)
 
+    def _bg_config(self) -> Optional[dict]:
+        """``config.data.train`` when it names a ``bg_dir`` (a BackgroundMixDataset config), else None."""
+        train = (self.config.get('data') or {}).get('train') or {}
+        return train if train.get('bg_dir') else None
+
+    def _train_records(self, ann_file) -> RawframeRecords:
+        """A train-phase ``RawframeRecords``; with a ``bg_dir`` its ``bg_files`` as BackgroundMixDataset's constructor makes them
+        (libs/loader/comix_loader.py:67-100): rank 0 extracts the missing backgrounds, the other ranks wait and then resolve."""
+        records = RawframeRecords(str(ann_file), self.config.data_root, phase='train')
+        bg = self._bg_config()
+        if bg is None:
+            return records
+        from .background import resolve_bg_files
+        records.merge_bg_files = bool(bg.get('merge_bg_files', True))
+        if not bg.get('back_ground_from_bg_dir', True):
+            return records
+        kw = dict(map_bg_to_video=bg.get('map_bg_to_video', True), bg_image_extension=bg.get('bg_image_extension', '.jpg'))
+        if self.rank == 0:
+            records.bg_files = resolve_bg_files(records.video_infos, bg['bg_dir'],
+                                                extract_bg_if_not_found=bg.get('extract_bg_if_not_found', True), **kw)
+        self._barrier()
+        if self.rank != 0:
+            records.bg_files = resolve_bg_files(records.video_infos, bg['bg_dir'], extract_bg_if_not_found=False, **kw)
+        return records
+
     def reload_train_dataset(self, use_internal_exemplar: bool = True):
-        self.train_dataset = RawframeRecords(str(self.files.task_splits_ann_files['train'][self._current_task]),
-                                             self.config.data_root, phase='train')
+        self.train_dataset = self._train_records(self.files.task_splits_ann_files['train'][self._current_task])
         if use_internal_exemplar:
             self.train_dataset.extend(self.exemplar_datasets)
+        if self._bg_config() is not None and self.config.get('keep_all_backgrounds', False):
+            # libs/cil/cil.py:193-195
+            self._all_bg_files.update(dict.fromkeys(self.train_dataset.bg_files))
+            self.train_dataset.bg_files = list(self._all_bg_files)
 
     def build_exemplar_from_current_task(self, exemplar_meta: dict):
         if self.rank == 0:
             self.files.create_exemplar_ann_file(exemplar_meta, self._current_task, self.config.data_root)
         self._barrier()
-        self.exemplar_datasets.append(RawframeRecords(str(self.files.exemplar_ann_file(self._current_task)),
-                                                      self.config.data_root, phase='train'))
+        self.exemplar_datasets.append(self._train_records(self.files.exemplar_ann_file(self._current_task)))
 
     def _load_state(self, model, path):
         """Every rank reads a checkpoint rank 0 wrote: wait for the writer first (a collective on the GPU stream does not
@@ -444,7 +481,7 @@ class CILTaskLoop:
         for task_idx in range(self._current_task):
             if not self.files.exemplar_ann_file(task_idx).exists():
                 break
-            self.exemplar_datasets.append(RawframeRecords(str(self.files.exemplar_ann_file(task_idx)), self.config.data_root))
+            self.exemplar_datasets.append(self._train_records(self.files.exemplar_ann_file(task_idx)))
         if len(self.exemplar_datasets) < self.starting_task:
             # the reference needs the weights of that task to extract features; it uses whatever current_model holds
             for i in range(len(self.exemplar_datasets), self.starting_task):
@@ -463,6 +500,10 @@ class CILTaskLoop:
         self.current_model.update_fc(self.num_classes(self._current_task))
         self.prev_model.update_fc(self.num_classes(self._current_task))
         self._freeze_prev()
+        if self._bg_config() is not None and self.config.get('keep_all_backgrounds', False):
+            # libs/cil/cil.py:690-694: the backgrounds of every earlier task's training set
+            for i in range(self._current_task):
+                self._all_bg_files.update(dict.fromkeys(self._train_records(self.files.task_splits_ann_files['train'][i]).bg_files))
         self.reload_train_dataset(use_internal_exemplar=True)
 
     def _freeze_prev(self):
@@ -513,6 +554,8 @@ class CILTaskLoop:
         accum = int(cfg.get('accumulate_grad_batches', 1))
         if accum > 1 and reducer is not None:
             raise NotImplementedError('accumulate_grad_batches > 1 with several ranks (the 8-GPU setting of the configs uses 1)')
+        if self._bg_config() is not None and hasattr(self.clip_loader, 'set_bg_files'):
+            self.clip_loader.set_bg_files(records.bg_files)
         epoch_losses = []
         try:
             self._fit_epochs(records, max_epochs, validate, optimizer, scheduler, reducer, clip, accum, epoch_losses)
@@ -574,8 +617,21 @@ class CILTaskLoop:
         return self.fit(self.train_dataset, self.config.num_epochs_per_task, validate)
 
     def build_cbf_dataset(self) -> RawframeRecords:
-        """Class-balanced set = all exemplars so far (libs/cil/cil.py:160-187)."""
-        return RawframeRecords(None, self.config.data_root, phase='train').extend(self.exemplar_datasets)
+        """Class-balanced set = all exemplars so far (libs/cil/cil.py:146-170).  With a ``bg_dir``: every background seen
+        (``keep_all_backgrounds``), or the current training set's plus the exemplars' (``cbf_full_bg``), else none."""
+        cbf = RawframeRecords(None, self.config.data_root, phase='train')
+        bg = self._bg_config()
+        if bg is not None:
+            cbf.merge_bg_files = bool(bg.get('merge_bg_files', True))
+        cbf.extend(self.exemplar_datasets)
+        if bg is not None:
+            if self.config.get('keep_all_backgrounds', False):
+                cbf.bg_files = list(self._all_bg_files)
+            elif self.config.get('cbf_full_bg', False):
+                cbf.bg_files = _first_seen(list(self.train_dataset.bg_files) + cbf.bg_files)
+            else:
+                cbf.bg_files = []
+        return cbf
 
     def train_cbf(self) -> List[float]:
         self.training_phase = 'cbf_step'

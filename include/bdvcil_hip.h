@@ -458,6 +458,37 @@ size_t bdv_jpeg_workspace_bytes(const bdv_jpeg_info* info, int B);
 int bdv_jpeg_reconstruct_u8(const short* coefs, const unsigned short* qts, const bdv_jpeg_info* info, int B, void* workspace,
                             size_t workspace_bytes, unsigned char* rgb, void* stream);
 
+/* ---- background extraction --------------------------------------------
+ * BackgroundMixDataset.__init__ with extract_bg_if_not_found=True (libs/loader/comix_loader.py:60-100) makes every missing
+ * bg_dir/<video>.jpg with bg_extraction_tmf (:148-164): the per-pixel np.median of the video's frames, .astype(np.uint8),
+ * written by cv2.imwrite -- a baseline JPEG with libjpeg-turbo's defaults (quality 95, 4:2:0, ISLOW DCT, standard Huffman tables).
+ *
+ * bdv_temporal_median_u8 (device): V videos of one frame geometry; frames (total_frames, H, W, 3) uint8 holds their frames back
+ * to back, video v at frames first[v] .. first[v] + counts[v] - 1 (first int64, counts int32: device arrays, and the same values on
+ * the host in first_host / counts_host, checked against total_frames before the launch; 1..65535 frames per video).
+ * out (V, H, W, 3) uint8 = np.median(frames of v, axis=0).astype(uint8): the middle order statistic for an odd count, the floor
+ * of the mean of the two middle ones for an even count.  One launch; the frame stack is read twice. */
+int bdv_temporal_median_u8(const uint8_t* frames, int64_t total_frames, const int64_t* first, const int32_t* counts,
+                           const int64_t* first_host, const int32_t* counts_host, int V, int H, int W, uint8_t* out, void* stream);
+/* The encoder's side of the bdv_jpeg_info struct, on the host: geometry of a YCbCr 4:2:0 stream of width x height (the layout
+ * bdv_jpeg_entropy_decode produces) and the quantisation tables of jpeg_set_quality(quality) (tables 0 / 1 for Y / CbCr).
+ * quality 25..100 (no entry exceeds 255 there, so force_baseline cannot matter); else BDV_EINVAL. */
+int bdv_jpeg_encode_info(int width, int height, int quality, bdv_jpeg_info* info);
+/* cv2.imwrite's forward stage (device): rgb (B, height, width, 3) uint8 -> coefs (B, coef_count) int16, quantised, per
+ * component a raster of 64-short blocks in natural order over the MCU-padded grid, exactly what bdv_jpeg_entropy_decode returns
+ * for libjpeg-turbo's file: fixed-point RGB -> YCbCr (jccolor.c), edge replication, h2v2 downsampling (jcsample.c), ISLOW forward
+ * DCT (jfdctint.c), quantisation on divisors qt << 3 (jcdctmgr.c), dummy blocks as jccoefct.c makes them.  coefs 16-byte aligned. */
+int bdv_jpeg_forward_u8(const uint8_t* rgb, int B, int height, int width, int quality, short* coefs, void* stream);
+/* Host side of cv2.imwrite: coefs (HOST, coef_count int16 as above) -> the whole file (SOI, APP0 JFIF 1.01, DQT 0, DQT 1, SOF0,
+ * DHT DC0 / AC0 / DC1 / AC1 with the standard tables, SOS, entropy-coded data, EOI) into out[0 .. capacity); *size = its length
+ * (also when capacity is too small, which returns BDV_EINVAL).  Thread-safe.  bdv_jpeg_encode_bound(width, height) bytes always
+ * suffice.  The _batch form encodes n images of one size on `threads` std::thread workers (the caller's thread is one of them):
+ * image i from coefs + i * coef_count into out + i * stride, its length in sizes[i]. */
+size_t bdv_jpeg_encode_bound(int width, int height);
+int bdv_jpeg_entropy_encode(const short* coefs, int width, int height, int quality, unsigned char* out, size_t capacity, size_t* size);
+int bdv_jpeg_entropy_encode_batch(const short* coefs, int n, int width, int height, int quality, unsigned char* out, size_t stride,
+                                  size_t* sizes, int threads);
+
 /* ---- optimizer: multi-tensor global-norm clip + SGD(momentum, wd) ---------------------------
  * torch.optim.SGD built at libs/cil/cil.py:467 with the groups of libs/models/cil_heads/tsm.py:273-303
  * and PL gradient_clip_val (cil.py:743).  Tables are device arrays, one entry per tensor. */

@@ -1,0 +1,145 @@
+"""Background extraction (bg_extraction_tmf) on synthetic UCF101-sized videos: the CPU path the reference takes against the GPU path
+of bdvcil_amd.background, and the median / forward-DCT kernels alone.  Dev tool; every phase is a process of its own, so that a
+job script can give each its own time limit:
+
+    python tools/bench_background.py --phase make    --data DIR          # 64 videos x 187 frames of 240 x 320, q95, Pillow
+    python tools/bench_background.py --phase cpu     --data DIR --out R  # Pillow decode + np.median + Pillow encode, 16 processes
+    python tools/bench_background.py --phase gpu     --data DIR --out R  # resolve_bg_files end to end (decode, median, encode, write)
+    rocprofv3 --kernel-trace --stats --output-format csv -d S -- python tools/bench_background.py --phase kernels --data DIR
+    python tools/bench_background.py --phase report  --out R --stats S > profiles/r04_background.txt
+
+The CPU path decodes with Pillow (cv2 is not installed; both run libjpeg-turbo with the same defaults)."""
+import argparse
+import glob
+import io
+import json
+import os
+import sys
+import time
+from concurrent.futures import ProcessPoolExecutor
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+VIDEOS, FRAMES, H, W = 64, 187, 240, 320
+
+
+def _make_video(args):
+    root, v = args
+    from PIL import Image
+    d = os.path.join(root, 'frames', f'v_{v:03d}')
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(v)
+    yy, xx = np.mgrid[0:H, 0:W]
+    base = np.stack([128 + 100 * np.sin(xx / (7.0 + v % 5) + yy / 13.0), 128 + 90 * np.cos(xx / 5.0 + v),
+                     128 + 80 * np.sin(yy / 3.0 + xx / 11.0)], -1)
+    for i in range(1, FRAMES + 1):
+        f = np.roll(base, 2 * i, axis=1) + rng.normal(0, 10, base.shape)
+        f[60:120, (3 * i) % 200:(3 * i) % 200 + 80] = 40 + (i % 7) * 30           # a moving foreground block
+        Image.fromarray(np.clip(f, 0, 255).astype(np.uint8)).save(os.path.join(d, f'img_{i:05}.jpg'), quality=95)
+
+
+def _cpu_one(args):
+    d, dest = args
+    from PIL import Image
+    frames = [np.asarray(Image.open(p).convert('RGB')) for p in sorted(glob.glob(os.path.join(d, '*')))]
+    med = np.median(frames, axis=0).astype(np.uint8)
+    Image.fromarray(med).save(dest, quality=95)
+
+
+def _videos(data):
+    return sorted(glob.glob(os.path.join(data, 'frames', 'v_*')))
+
+
+def _record(out, key, value):
+    res = {}
+    if os.path.exists(out):
+        with open(out) as f:
+            res = json.load(f)
+    res[key] = value
+    with open(out, 'w') as f:
+        json.dump(res, f, indent=1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--phase', required=True, choices=['make', 'cpu', 'gpu', 'kernels', 'report'])
+    ap.add_argument('--data', default='bench_out/background')
+    ap.add_argument('--out', default='bench_out/background.json')
+    ap.add_argument('--stats', default=None)
+    ap.add_argument('--procs', type=int, default=16)
+    a = ap.parse_args()
+    frame_bytes, stack = H * W * 3, VIDEOS * FRAMES * H * W * 3
+    if a.phase == 'make':
+        with ProcessPoolExecutor(a.procs) as ex:
+            list(ex.map(_make_video, [(a.data, v) for v in range(VIDEOS)]))
+        n = sum(os.path.getsize(p) for p in glob.glob(os.path.join(a.data, 'frames', '*', '*.jpg')))
+        print(f'{VIDEOS} videos x {FRAMES} frames of {W} x {H}, q95: {n / 2**20:.1f} MiB of JPEG')
+    elif a.phase == 'cpu':
+        dest = os.path.join(a.data, 'bg_cpu')
+        os.makedirs(dest, exist_ok=True)
+        jobs = [(d, os.path.join(dest, os.path.basename(d) + '.jpg')) for d in _videos(a.data)]
+        t = time.perf_counter()
+        with ProcessPoolExecutor(a.procs) as ex:
+            list(ex.map(_cpu_one, jobs))
+        dt = time.perf_counter() - t
+        _record(a.out, 'cpu', dict(seconds=dt, videos=len(jobs), procs=a.procs))
+        print(f'cpu: {len(jobs)} videos in {dt:.2f} s on {a.procs} processes ({dt / len(jobs) * 1e3:.1f} ms per video)')
+    elif a.phase == 'gpu':
+        import torch
+        from bdvcil_amd.background import resolve_bg_files
+        from bdvcil_amd.decode import JpegDecoder
+        dec = JpegDecoder('cuda', threads=16)
+        infos = [dict(frame_dir=d, total_frames=FRAMES, label=0) for d in _videos(a.data)]
+        warm = os.path.join(a.data, 'bg_gpu_warm')
+        resolve_bg_files(infos[:2], warm, decoder=dec)           # library load, kernel load, allocator warm-up
+        dest = os.path.join(a.data, 'bg_gpu')
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = resolve_bg_files(infos, dest, decoder=dec)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t
+        assert len(out) == len(infos)
+        same = sum(open(p, 'rb').read() == open(os.path.join(a.data, 'bg_cpu', os.path.basename(p)), 'rb').read()
+                   for p in out if os.path.exists(os.path.join(a.data, 'bg_cpu', os.path.basename(p))))
+        _record(a.out, 'gpu', dict(seconds=dt, videos=len(out), identical_to_cpu=same))
+        print(f'gpu: {len(out)} videos in {dt:.2f} s ({dt / len(out) * 1e3:.1f} ms per video), {same} files identical to the CPU path')
+    elif a.phase == 'kernels':
+        import torch
+        from bdvcil_amd.background import jpeg_forward, temporal_median
+        frames = torch.randint(0, 256, (VIDEOS * FRAMES, H, W, 3), dtype=torch.uint8, device='cuda')
+        for _ in range(5):
+            med = temporal_median(frames, [FRAMES] * VIDEOS)
+            jpeg_forward(med, 95)
+        torch.cuda.synchronize()
+        print('kernels: 5 x (median of 64 x 187 frames, forward stage of 64 images)')
+    else:
+        with open(a.out) as f:
+            res = json.load(f)
+        print(f'# tools/bench_background.py: {VIDEOS} videos x {FRAMES} frames of {W} x {H}, Pillow q95 frames, one MI355X')
+        c, g = res.get('cpu'), res.get('gpu')
+        if c:
+            print(f'cpu path (Pillow decode + np.median + Pillow encode, {c["procs"]} processes): {c["seconds"]:.2f} s, '
+                  f'{c["seconds"] / c["videos"] * 1e3:.1f} ms per video')
+        if g:
+            print(f'gpu path (resolve_bg_files: read, host Huffman decode, decode kernels, median, forward stage, host encode, '
+                  f'write): {g["seconds"]:.2f} s, {g["seconds"] / g["videos"] * 1e3:.1f} ms per video; '
+                  f'{g["identical_to_cpu"]} of {g["videos"]} files identical to the cpu path')
+        if c and g:
+            print(f'speed-up end to end: {c["seconds"] / g["seconds"]:.1f}x')
+        if a.stats:
+            files = glob.glob(os.path.join(a.stats, '**', '*kernel_stats.csv'), recursive=True)
+            import csv
+            want = {'temporal_median_kernel': 2 * stack + VIDEOS * frame_bytes,      # two reads of the stack, one write
+                    'jpeg_forward_kernel': VIDEOS * frame_bytes + VIDEOS * 2 * (1200 + 300 + 300) * 64}
+            for fn in files:
+                for row in csv.DictReader(open(fn)):
+                    for k, nbytes in want.items():
+                        if k in row['Name']:
+                            avg_ns = float(row['AverageNs'])
+                            print(f'{k}: {int(row["Calls"])} calls, {avg_ns / 1e3:.1f} us average, {nbytes / 2**20:.1f} MiB moved '
+                                  f'(minimum), {nbytes / avg_ns:.0f} GB/s = {nbytes / avg_ns / 8000 * 100:.0f} % of 8 TB/s HBM')
+
+
+if __name__ == '__main__':
+    main()
