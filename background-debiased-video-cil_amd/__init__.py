@@ -9,6 +9,7 @@ Import as ``bdvcil_amd`` (see ``bdvcil_amd.py`` at the repo root).  Layout:
 * ``registry``, ``recognizer``, ``resnet_tsm``, ``heads``, ``losses``, ``hooks``, ``optim``
                    the reference's mmaction2-style plugin surface (same names / signatures / state_dict keys)
 * ``frontend``     fused background-mix + normalize; train front-end = RandAugment -> mix decision -> blend
+* ``actor_cut_mix``  ActorCutMix clip loader: detection boxes on the host, composite + normalize in csrc/actor_cut_mix.hip
 * ``background``   background extraction: temporal median + JPEG encode of the frames of a video (bg_extraction_tmf)
 * ``augment``      RandAugment for batches of uint8 clips (draws + device tables; pixels in csrc/augment.hip)
 * ``cil_step``     training-step arithmetic of BaseCIL / ICARLModel + a step engine
@@ -52,6 +53,7 @@ from .optim import (CILTSMOptimizerConstructor, CILTSMOptimizerConstructorImprov
                     build_optimizer)
 from .frontend import BackgroundCropFrontEnd, BackgroundMixFrontEnd, CropFrontEnd, MultiScaleCropResize, TrainClipFrontEnd, crop_offsets  # noqa: F401
 from .decode import JpegDecoder, PrefetchLoader, RawFrameClipLoader, sample_frames  # noqa: F401
+from .actor_cut_mix import ActorCutMixClipLoader  # noqa: F401
 from .augment import RandAugment  # noqa: F401
 from .background import encode_jpeg, extract_background, resolve_bg_files, temporal_median  # noqa: F401
 from .cil_step import (TrainEngine, base_training_step, icarl_training_step, icarl_video_mix_training_step,  # noqa: F401

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # is then the caller's business
 _OVERRIDE = os.environ.get('BDVCIL_LIB_PATH')
 LIB_PATH = _OVERRIDE or os.path.join(_HERE, 'csrc', 'libbdvcil_hip.so')
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _lib = None
 
@@ -117,6 +117,8 @@ SIGNATURES = {
     'bdv_jpeg_entropy_encode': (c_int, [P, c_int, c_int, c_int, P, c_size_t, P]),
     'bdv_jpeg_entropy_encode_batch': (c_int, [P, c_int, c_int, c_int, c_int, P, c_size_t, P, c_int]),
     'bdv_crop_normalize_u8': (c_int, [P, P, c_int, c_int, c_int, _F3, _F3, P, P, c_int, c_int, c_int, c_int, P]),
+    'bdv_actor_cut_mix_u8': (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, c_int64, c_int, c_int, c_int, c_int, _F3, _F3, P,
+                                     c_int, P, P]),
     'bdv_lsc_fwd': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     'bdv_lsc_bwd': (c_int, [P, P, P, P, P, P, P, P, c_float, P, c_int, c_int, c_int, c_int, P]),
     'bdv_linear_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
@@ -152,7 +154,7 @@ class HipExtensionError(RuntimeError):
 
 
 HASHED_SOURCES = ('conv_mfma.hip', 'bn.hip', 'pool_frontend.hip', 'head_loss.hip', 'repr.hip', 'augment.hip', 'optim.hip', 'jpeg.hip',
-                  'background.hip', 'api_common.cpp', 'common.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
+                  'background.hip', 'actor_cut_mix.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
 
 
 def source_hash():

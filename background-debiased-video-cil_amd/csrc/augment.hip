@@ -341,88 +341,12 @@ extern "C" int bdv_randaug_apply(const uint8_t* in, uint8_t* out, const int32_t*
 
 // ---- Resize / MultiScaleCrop + Resize of the frame pipeline: OpenCV's INTER_LINEAR on 8-bit images -------------------------------
 // UPSTREAM mmaction2 Resize -> mmcv.imresize(interpolation='bilinear') -> cv2.resize(..., INTER_LINEAR) (configs/ucf101/
-// bgmix_plus_randAug/...py:127, :136; MultiScaleCrop's crop is a view, the Resize after it does the resampling).  cv2 is absent
-// from this image: the arithmetic below restates OpenCV's published fixed-point algorithm (imgproc/resize.cpp: coefficients in 11
-// fraction bits from float weights rounded half-to-even, a horizontal pass into 32-bit rows, a vertical pass
-// ((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2 >> 2; the exact-2x shrink is the 2x2 box average cv::resize switches to)
-// -- PARITY UNPINNED, see oracle/resize_oracle.py.  The float / double operations are the same IEEE operations without contraction
-// (this file is built with -ffp-contract=off).
+// bgmix_plus_randAug/...py:127, :136; MultiScaleCrop's crop is a view, the Resize after it does the resampling).  The per-pixel
+// arithmetic (OpenCV's published fixed-point algorithm, PARITY UNPINNED, see oracle/resize_oracle.py) is in resize_linear.h, shared
+// with actor_cut_mix.hip.
+#include "resize_linear.h"
+
 namespace {
-
-struct ResizeAxis {
-  int s0, s1;     // source taps (already clamped into the box)
-  int a0, a1;     // 11-bit weights
-};
-
-__device__ __forceinline__ int sat_short(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
-
-// x axis: a tap left of / beyond the last column collapses onto the edge with weight 1 (cv::resize clamps fx there)
-__device__ __forceinline__ ResizeAxis resize_axis_x(int d, double scale, int ssize) {
-  float f = (float)((d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= s;
-  if (s < 0) {
-    f = 0.f;
-    s = 0;
-  }
-  if (s >= ssize - 1) {
-    f = 0.f;
-    s = ssize - 1;
-  }
-  ResizeAxis r;
-  r.s0 = s;
-  r.s1 = s + 1 < ssize ? s + 1 : ssize - 1;
-  r.a0 = sat_short(__float2int_rn((1.f - f) * 2048.f));
-  r.a1 = sat_short(__float2int_rn(f * 2048.f));
-  return r;
-}
-
-// y axis: the weights keep the unclamped fraction, only the row indices are clipped (resizeGeneric_Invoker)
-__device__ __forceinline__ ResizeAxis resize_axis_y(int d, double scale, int ssize) {
-  float f = (float)((d + 0.5) * scale - 0.5);
-  const int s = (int)floorf(f);
-  f -= s;
-  ResizeAxis r;
-  r.s0 = s < 0 ? 0 : s >= ssize ? ssize - 1 : s;
-  r.s1 = s + 1 < 0 ? 0 : s + 1 >= ssize ? ssize - 1 : s + 1;
-  r.a0 = sat_short(__float2int_rn((1.f - f) * 2048.f));
-  r.a1 = sat_short(__float2int_rn(f * 2048.f));
-  return r;
-}
-
-struct ResizeBox {
-  const uint8_t* base;   // first pixel of the box
-  size_t pitch;
-  int bw, bh, mode;      // mode 0: resample, 1: copy (same size), 2: 2x2 box mean (exact 2x shrink)
-  double scale_x, scale_y;
-};
-
-// one output pixel of a box -> packed 0x00BBGGRR
-__device__ __forceinline__ unsigned resize_pixel(const ResizeBox& b, int dx, int dy) {
-  unsigned out = 0;
-  if (b.mode == 1) {   // same size: cv::resize copies
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out |= (unsigned)b.base[dy * b.pitch + dx * 3 + c] << (8 * c);
-    return out;
-  }
-  if (b.mode == 2) {   // exact 2x shrink: INTER_LINEAR is replaced by the fast INTER_AREA (2x2 mean, rounded)
-    const uint8_t* p = b.base + (size_t)(2 * dy) * b.pitch + (size_t)(2 * dx) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out |= (unsigned)((p[c] + p[3 + c] + p[b.pitch + c] + p[b.pitch + 3 + c] + 2) >> 2) << (8 * c);
-    return out;
-  }
-  const ResizeAxis ax = resize_axis_x(dx, b.scale_x, b.bw), ay = resize_axis_y(dy, b.scale_y, b.bh);
-  const uint8_t* r0 = b.base + (size_t)ay.s0 * b.pitch;
-  const uint8_t* r1 = b.base + (size_t)ay.s1 * b.pitch;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int h0 = r0[ax.s0 * 3 + c] * ax.a0 + r0[ax.s1 * 3 + c] * ax.a1;
-    const int h1 = r1[ax.s0 * 3 + c] * ax.a0 + r1[ax.s1 * 3 + c] * ax.a1;
-    const int v = (((ay.a0 * (h0 >> 4)) >> 16) + ((ay.a1 * (h1 >> 4)) >> 16) + 2) >> 2;
-    out |= (unsigned)(v & 255) << (8 * c);
-  }
-  return out;
-}
 
 // grid (pixel groups of one frame, frame): four consecutive output pixels of a frame per thread -- one integer division and the
 // box's two double divisions per THREAD (the first form did them, and a 64-bit division, per pixel and was bound by that arithmetic);

@@ -272,15 +272,23 @@ class PrefetchLoader:
         self.pool = ThreadPoolExecutor(max_workers=1)
         self.queue = []
         self._bg_files = None           # set_bg_files: the list handed to the loader with each batch submitted after it
+        self._scene_infos = None        # set_scene_infos: handed to the loader once, with the first batch submitted after it
 
     def set_bg_files(self, bg_files: Sequence[str]) -> None:
         """Forwarded to the loader; takes effect from the next submitted batch (batches already queued keep the list they were
         submitted with)."""
         self._bg_files = list(bg_files) if bg_files is not None else []
 
-    def _work(self, video_infos, phase, bg_files=None):
+    def set_scene_infos(self, video_infos: Sequence[dict]) -> None:
+        """Forwarded to the loader (``ActorCutMixClipLoader``'s scene pool) with the next submitted batch only: the loader keeps
+        the pool, and its ``set_scene_infos`` looks up every video's detections, which is not repeated per batch."""
+        self._scene_infos = list(video_infos) if video_infos is not None else []
+
+    def _work(self, video_infos, phase, bg_files=None, scene_infos=None):
         if bg_files is not None and hasattr(self.loader, 'set_bg_files'):
             self.loader.set_bg_files(bg_files)
+        if scene_infos is not None and hasattr(self.loader, 'set_scene_infos'):
+            self.loader.set_scene_infos(scene_infos)
         with torch.cuda.stream(self.stream):
             batch = self.loader(video_infos, phase)
             ev = torch.cuda.Event()
@@ -288,7 +296,8 @@ class PrefetchLoader:
         return batch, ev
 
     def submit(self, video_infos, phase: str):
-        self.queue.append(self.pool.submit(self._work, video_infos, phase, self._bg_files))
+        self.queue.append(self.pool.submit(self._work, video_infos, phase, self._bg_files, self._scene_infos))
+        self._scene_infos = None
 
     def get(self):
         batch, ev = self.queue.pop(0).result()

@@ -802,6 +802,36 @@ def crop_normalize_u8(frames, crops, crop_h, crop_w, mean, std, want_nhwc4=True,
     return o4, oc
 
 
+
+def actor_cut_mix_u8(actor, scene, plan, nclips: int, out, mean, std):
+    """ActorCutMix composite + Normalize (``bdv_actor_cut_mix_u8``): actor (n_actor, T, Ha, Wa, 3) / scene (n_scene, T, Hs, Ws, 3) | None
+    uint8 clips after Resize(-1, 256); ``plan``: the host int32 table of include/bdvcil_hip.h (validated there before the launch);
+    out (B_out, T, 3, Hd, Wd) fp32, the clips' rows written.  Returns the mask pixel counts (nclips,) int32 on the device."""
+    _chk(actor, dtype=torch.uint8, name='actor')
+    if actor.dim() != 5 or actor.shape[-1] != 3:
+        raise ValueError(f'actor_cut_mix_u8: actor must be (n, T, H, W, 3), got {tuple(actor.shape)}')
+    n_actor, T, Ha, Wa, _ = (int(d) for d in actor.shape)
+    n_scene, Hs, Ws = 0, 0, 0
+    if scene is not None:
+        _chk(scene, dtype=torch.uint8, name='scene')
+        if scene.dim() != 5 or tuple(scene.shape[1:2]) != (T,) or scene.shape[-1] != 3:
+            raise ValueError(f'actor_cut_mix_u8: scene must be (n, {T}, H, W, 3), got {tuple(scene.shape)}')
+        n_scene, _, Hs, Ws, _ = (int(d) for d in scene.shape)
+    _chk(out, dtype=torch.float32, name='out')
+    if out.dim() != 5 or out.shape[1] != T or out.shape[2] != 3:
+        raise ValueError(f'actor_cut_mix_u8: out must be (B, {T}, 3, Hd, Wd), got {tuple(out.shape)}')
+    B_out, Hd, Wd = int(out.shape[0]), int(out.shape[3]), int(out.shape[4])
+    host = torch.as_tensor(plan, dtype=torch.int32).reshape(-1).contiguous()
+    dev = host.to(actor.device, non_blocking=False)
+    counts = torch.empty(int(nclips), dtype=torch.int32, device=actor.device)
+    f3 = ctypes.c_float * 3
+    m = torch.tensor(list(mean), dtype=torch.float32)
+    inv = 1.0 / torch.tensor(list(std), dtype=torch.float32)      # fp32 reciprocal, as in bgmix_normalize_u8
+    check(lib().bdv_actor_cut_mix_u8(_p(actor), n_actor, Ha, Wa, _p(scene), n_scene, Hs, Ws, _p(dev), host.data_ptr(), int(host.numel()),
+                                     int(nclips), T, Hd, Wd, f3(*m.tolist()), f3(*inv.tolist()), _p(out), B_out, _p(counts), _stream()),
+          'bdv_actor_cut_mix_u8')
+    return counts
+
 WGRAD_X3 = _x3_default('BDVCIL_WGRAD_X3')
 
 

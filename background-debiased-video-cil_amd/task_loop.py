@@ -556,6 +556,8 @@ class CILTaskLoop:
             raise NotImplementedError('accumulate_grad_batches > 1 with several ranks (the 8-GPU setting of the configs uses 1)')
         if self._bg_config() is not None and hasattr(self.clip_loader, 'set_bg_files'):
             self.clip_loader.set_bg_files(records.bg_files)
+        if hasattr(self.clip_loader, 'set_scene_infos'):           # ActorCutMix: scenes come from the whole (merged) training set
+            self.clip_loader.set_scene_infos(records.video_infos)
         epoch_losses = []
         try:
             self._fit_epochs(records, max_epochs, validate, optimizer, scheduler, reducer, clip, accum, epoch_losses)

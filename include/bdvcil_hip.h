@@ -324,6 +324,22 @@ int bdv_bg_resize_crop_u8(const uint8_t* src, int B, int Hs, int Ws, int Hr, int
 int bdv_crop_normalize_u8(const uint8_t* frames, const int32_t* crops, int ncrops, int crop_h, int crop_w,
                           const float mean[3], const float inv_std[3], float* out_nhwc4, float* out_nchw, int B, int T,
                           int H, int W, void* stream);
+/* ActorCutMix composite (libs/loader/actor_cut_mix_loader.py:135-164 with libs/pipelines/box.py:176-207, :116-159,
+ * :339-379): for every ActorCutMix clip of a batch, FlipWithBox + ResizeWithBox((Wd, Hd)) of the actor and of the scene
+ * frames, BuildHumanMask from the actor's boxes, ActorCutOut(127) of the scene's own boxes, actor * mask + scene * (1 - mask)
+ * and Normalize, in one launch.  actor (n_actor, T, Ha, Wa, 3) / scene (n_scene, T, Hs, Ws, 3) uint8: the clips after
+ * Resize(-1, 256) (scene may be NULL when n_scene == 0).  plan: nclips*T frames, int32, on the device (read by the kernel) AND
+ * on the host (every index validated before the launch), plan_len ints:
+ *   nclips x (out_row, actor_row, actor_flip, scene_row, scene_flip)   scene_row = -1 only for a clip without actor boxes
+ *   actor box offsets (nclips*T + 1), scene box offsets (nclips*T + 1)  frame f = clip * T + t; at most BDV_ACM_MAX_BOXES per frame
+ *   actor boxes, then scene boxes: x0 y0 x1 y1 each, 0 <= x <= Wd, 0 <= y <= Hd (the .astype(int) of the final boxes; the pixels
+ *   [y0, y1) x [x0, x1), an inverted box is empty)
+ * A clip with no actor box in any frame is all actor (mask 1).  out (B_out, T, 3, Hd, Wd) fp32, 16-byte aligned: rows out_row of
+ * the clips, values (x - mean) * inv_std; the other rows are not touched.  counts (nclips) int32: mask pixels per clip. */
+#define BDV_ACM_MAX_BOXES 256
+int bdv_actor_cut_mix_u8(const uint8_t* actor, int n_actor, int Ha, int Wa, const uint8_t* scene, int n_scene, int Hs, int Ws,
+                         const int32_t* plan, const int32_t* plan_host, int64_t plan_len, int nclips, int T, int Hd, int Wd,
+                         const float mean[3], const float inv_std[3], float* out, int B_out, int32_t* counts, void* stream);
 
 /* ---- classifier heads ---------------------------------------------------------------------- */
 /* libs/models/cil_heads/cosine_linear.py:27-43 (LSC): sim[n,k] = sum_p softmax_p(c)[p]*c[p],
