@@ -467,6 +467,25 @@ def bgmix_normalize(frames_u8: torch.Tensor, bg_u8: torch.Tensor, mix_mask: torc
     return out.permute(0, 1, 4, 2, 3).contiguous()
 
 
+def bgmix_normalize_f32bg(frames_u8: torch.Tensor, bg_f32: torch.Tensor, mix_mask: torch.Tensor, alpha: float = 0.5,
+                          mean: Sequence[float] = IMG_MEAN, std: Sequence[float] = IMG_STD):
+    """``bgmix_normalize`` for a background that is already fp32 pixel values in [0, 255] (B,H,W,3) -- the output of
+    ``bg_resize_crop``: torchvision's Resize of a float image is not rounded back to uint8 -- in the two layouts the front-end
+    emits -> ((B*T,H,W,4) fp32 with a +0 fourth channel, (B,T,3,H,W) fp32).  Every operation is one separately rounded fp32
+    multiply, subtract, add or divide: the blend weights are fp32(alpha) and fp32(1) - fp32(alpha)."""
+    assert bg_f32.dtype == torch.float32
+    m = torch.tensor(mean, dtype=torch.float32)
+    s = torch.tensor(std, dtype=torch.float32)
+    a = torch.tensor(alpha, dtype=torch.float32)
+    x = (frames_u8.float() - m) * (1.0 / s)                    # (B,T,H,W,3)
+    b = (bg_f32 - m) / s                                       # (B,H,W,3)
+    blend = x * (1.0 - a) + b[:, None] * a
+    out = torch.where(mix_mask.view(-1, 1, 1, 1, 1).bool(), blend, x)
+    B, T, H, W, _ = out.shape
+    nhwc4 = torch.cat([out, torch.zeros(B, T, H, W, 1)], dim=-1).reshape(B * T, H, W, 4)
+    return nhwc4, out.permute(0, 1, 4, 2, 3).contiguous()
+
+
 def bg_resize_crop(bg_u8: torch.Tensor, resize: int, crop: int, top: int, left: int, antialias: bool = False) -> torch.Tensor:
     """One background image through ``Resize(resize) -> RandomCrop(crop)`` of BackgroundMixDataset.bg_pipeline
     (libs/loader/comix_loader.py:72-73) at the given crop offsets.  bg_u8 (Hs,Ws,3) uint8 -> (crop,crop,3) fp32 in [0,255].
