@@ -99,6 +99,7 @@ SIGNATURES = {
     'bdv_bn_pair_workspace_bytes': (c_size_t, [c_int64, c_int]),
     'bdv_bn_backward_pair': (c_int, [P, P, P, P, P, P, P, c_int, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, P, c_size_t, c_int, c_int,
                                      P, c_size_t, P]),
+    'bdv_bn_eval_backward': (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_float, c_int64, c_int, P, c_size_t, c_int, c_int, P, c_size_t, P]),
     'bdv_bn_backward_maxpool_split': (c_int, [P, P, P, P, P, P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, P, c_size_t, c_int,
                                               c_int, P, c_size_t, P]),
     'bdv_bn_backward_maxpool': (c_int, [P, P, P, P, P, P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, P, c_size_t, c_int, P]),

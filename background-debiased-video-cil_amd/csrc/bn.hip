@@ -705,6 +705,88 @@ __global__ __launch_bounds__(256) void bn_bwd_pool_kernel(const void* __restrict
   }
 }
 
+// ---- backward through an eval-mode BatchNorm (running statistics: constants of the step) -----------------------------------
+// dz = dout (.) sign, dy = dz * scale with scale = gamma * invstd_running (bdv_bn_eval_params): the mean terms of the train-mode
+// apply vanish, so dy does not wait for the column sums and the backward is ONE pass.  One multiply per element, never a division
+// by gamma or scale (gamma = 0 and gamma < 0 are ordinary channels).
+// SIGN: 0 = no ReLU, 1 = the forward's 1-bit mask, 2 = the sign of the activation tensor itself (act > 0: a unit whose affine is
+// frozen keeps neither y nor a mask).  DZ: also write the masked gradient (the identity path and the downsample BatchNorm read it).
+
+// No parameter gradients: the streaming form, one 16-byte unit per lane and iteration (bn_bwd_apply_kernel's decomposition).
+template <int SIGN, bool DZ, bool NT = false, int ES = 4>
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const void* __restrict__ dout, const uint32_t* __restrict__ mask,
+                                                           const void* __restrict__ act, const float4* __restrict__ scale,
+                                                           void* __restrict__ dy, void* __restrict__ dz, int64_t n4, int CV) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  constexpr int U = ActU<ES>::value;
+  for (int64_t iu = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; iu < n4 / U; iu += stride) {
+    float4 gg[U], aa[U], dd[U];
+    act_ld16<ES, NT>(dout, iu, gg);
+    if (SIGN == 2) act_ld16<ES, false>(act, iu, aa);   // the activation is an operand of the weight gradient next: a plain load
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = iu * U + u;
+      const float4 sc = scale[(int)(i % CV)];
+      float4 g = gg[u];
+      if (SIGN == 1) g = apply_nibble(g, mask_nibble(mask, i));
+      if (SIGN == 2) g = apply_nibble(g, nibble_gt0(aa[u]));
+      gg[u] = g;
+      dd[u] = make_float4(g.x * sc.x, g.y * sc.y, g.z * sc.z, g.w * sc.w);
+    }
+    act_st16<ES>(dy, iu, dd);
+    if (DZ) act_st16<ES>(dz, iu, gg);
+  }
+}
+
+// With parameter gradients: bn_bwd_partial_kernel's block / lane decomposition and its two sums, expression for expression, with
+// the running statistics as mean / invstd; the lane that has g in registers writes dy (and dz) on the way.
+template <int SIGN, bool DZ, bool NT = false, int ES = 4>
+__global__ __launch_bounds__(256) void bn_eval_bwd_stats_kernel(const void* __restrict__ dout, const uint32_t* __restrict__ mask,
+                                                                 const void* __restrict__ act, const void* __restrict__ y,
+                                                                 const float* __restrict__ scale, const float* __restrict__ mean,
+                                                                 const float* __restrict__ invstd, void* __restrict__ dy,
+                                                                 void* __restrict__ dz, float* __restrict__ p1, float* __restrict__ p2,
+                                                                 int64_t M, int C, int CVB, int RL, int rows_per_block) {
+  __shared__ float4 sh[2][256];
+  const int tid = threadIdx.x;
+  const int cv = tid % CVB, rl = tid / CVB;
+  const int c4 = blockIdx.y * CVB + cv;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  int64_t r1 = r0 + rows_per_block;
+  if (r1 > M) r1 = M;
+  const int CV = C / 4;
+  const float4 mu = reinterpret_cast<const float4*>(mean)[c4];
+  const float4 is = reinterpret_cast<const float4*>(invstd)[c4];
+  const float4 sc = reinterpret_cast<const float4*>(scale)[c4];
+  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+  for (int64_t r = r0 + rl; r < r1; r += RL) {
+    const int64_t i = r * CV + c4;
+    float4 g = act_ld4<ES, NT>(dout, i);
+    const float4 v = act_ld4<ES, NT>(y, i);
+    if (SIGN == 1) g = apply_nibble(g, mask_nibble(mask, i));
+    if (SIGN == 2) g = apply_nibble(g, nibble_gt0(act_ld4<ES>(act, i)));
+    act_st4<ES>(dy, i, make_float4(g.x * sc.x, g.y * sc.y, g.z * sc.z, g.w * sc.w));
+    if (DZ) act_st4<ES>(dz, i, g);
+    s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
+    s2.x += g.x * ((v.x - mu.x) * is.x);
+    s2.y += g.y * ((v.y - mu.y) * is.y);
+    s2.z += g.z * ((v.z - mu.z) * is.z);
+    s2.w += g.w * ((v.w - mu.w) * is.w);
+  }
+  sh[0][tid] = s1;
+  sh[1][tid] = s2;
+  __syncthreads();
+  if (rl == 0) {
+    for (int k = 1; k < RL; ++k) {
+      const float4 a = sh[0][k * CVB + cv], b = sh[1][k * CVB + cv];
+      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
+      s2.x += b.x; s2.y += b.y; s2.z += b.z; s2.w += b.w;
+    }
+    reinterpret_cast<float4*>(p1)[(int64_t)blockIdx.x * CV + c4] = s1;
+    reinterpret_cast<float4*>(p2)[(int64_t)blockIdx.x * CV + c4] = s2;
+  }
+}
+
 template <int ES = 4>
 __global__ __launch_bounds__(256) void relu_bwd_kernel(const void* __restrict__ dout, const uint32_t* __restrict__ mask,
                                                         const void* __restrict__ add, void* __restrict__ g, int64_t n4) {
@@ -1064,6 +1146,73 @@ extern "C" int bdv_bn_backward_pair(const void* dout, const uint32_t* relu_mask,
   BDV_LAUNCH_CHECK("bdv_bn_backward_pair(apply)");
   return BDV_OK;
 }
+
+extern "C" int bdv_bn_eval_backward(const void* dout, const uint32_t* relu_mask, const void* relu_act, const void* y,
+                                    const float* scale, const float* running_mean, const float* invstd, void* dy, void* dz,
+                                    float* dgamma, float* dbeta, float beta_acc, int64_t M, int C, void* workspace,
+                                    size_t workspace_bytes, int act_dtype, int splits, void* fin_scratch, size_t fin_scratch_bytes,
+                                    void* stream) {
+  BDV_REQUIRE(dout && scale && dy, "bdv_bn_eval_backward: null pointer (dout, scale and dy are required)");
+  BDV_REQUIRE_ACT(act_dtype, "bdv_bn_eval_backward");
+  BDV_REQUIRE(M > 0 && bn_c_ok(C), "bdv_bn_eval_backward: unsupported M=%lld C=%d", (long long)M, C);
+  BDV_REQUIRE(relu_mask == nullptr || relu_act == nullptr, "bdv_bn_eval_backward: one ReLU sign source at most (relu_mask or relu_act)");
+  BDV_REQUIRE(relu_mask == nullptr || C % 32 == 0, "bdv_bn_eval_backward: relu_mask needs C %% 32 == 0");
+  BDV_REQUIRE(act_dtype == BDV_ACT_F32 || C % 8 == 0, "bdv_bn_eval_backward: bf16 tensors need C %% 8 == 0 (16-byte units)");
+  BDV_REQUIRE(bdv_aligned16(dout) && bdv_aligned16(dy) && bdv_aligned16(dz) && bdv_aligned16(relu_act) && bdv_aligned16(y) &&
+                  bdv_aligned16(scale) && (((uintptr_t)relu_mask) & 3) == 0, "bdv_bn_eval_backward: alignment");
+  BDV_REQUIRE(dy != dz && (const void*)dy != dout && (dz == nullptr || (const void*)dz != dout),
+              "bdv_bn_eval_backward: dy, dz and dout must be distinct");
+  const bool stats = dgamma != nullptr || dbeta != nullptr;
+  const int sign = relu_mask != nullptr ? 1 : relu_act != nullptr ? 2 : 0;
+  const bool nt = bn_nt_enabled();
+  hipStream_t s = (hipStream_t)stream;
+#define BDV_EVAL_DISPATCH(LAUNCH)                                                       \
+  do {                                                                                  \
+    if (sign == 1) { if (dz) { if (nt) LAUNCH(1, true, true); else LAUNCH(1, true, false); }   \
+                     else    { if (nt) LAUNCH(1, false, true); else LAUNCH(1, false, false); } } \
+    else if (sign == 2) { if (dz) { if (nt) LAUNCH(2, true, true); else LAUNCH(2, true, false); }   \
+                          else    { if (nt) LAUNCH(2, false, true); else LAUNCH(2, false, false); } } \
+    else { if (dz) { if (nt) LAUNCH(0, true, true); else LAUNCH(0, true, false); }      \
+           else    { if (nt) LAUNCH(0, false, true); else LAUNCH(0, false, false); } }  \
+  } while (0)
+  if (!stats) {   // dy = dz * scale alone: no y, no workspace, no reduction
+    const int64_t n4 = M * C / 4;
+    const dim3 grid(ew_grid(act_dtype == BDV_ACT_BF16 ? n4 / 2 : n4 / BDV_F32_UNITS)), blk(256);
+#define BDV_EVAL_BWD(SIGN_, DZ_, NT_)                                                                                          \
+  hipLaunchKernelGGL((bn_eval_bwd_kernel<SIGN_, DZ_, NT_, ES>), grid, blk, 0, s, dout, relu_mask, relu_act, (const float4*)scale, dy, \
+                     dz, n4, C / 4)
+    BDV_ACT_SWITCH(act_dtype, ES, BDV_EVAL_DISPATCH(BDV_EVAL_BWD));
+#undef BDV_EVAL_BWD
+    BDV_LAUNCH_CHECK("bdv_bn_eval_backward");
+    return BDV_OK;
+  }
+  BDV_REQUIRE(y && running_mean && invstd && workspace, "bdv_bn_eval_backward: dgamma / dbeta need y, running_mean, invstd and a workspace");
+  BDV_REQUIRE(bdv_aligned16(running_mean) && bdv_aligned16(invstd) && bdv_aligned16(workspace), "bdv_bn_eval_backward: alignment");
+  BDV_REQUIRE((const void*)dy != y && (dz == nullptr || (const void*)dz != y), "bdv_bn_eval_backward: dy / dz must not alias y");
+  if (workspace_bytes < bdv_bn_workspace_bytes(M, C)) {
+    bdv_set_error("bdv_bn_eval_backward: workspace too small");
+    return BDV_EWORKSPACE;
+  }
+  const BnGrid b = bn_grid(M, C);
+  const int S = bn_fin_resolve(splits, b.RB, C, fin_scratch, fin_scratch_bytes, "bdv_bn_eval_backward");
+  if (S < 0) return BDV_EINVAL;
+  float* p1 = (float*)workspace;
+  float* p2 = p1 + MAX_RB_TIMES_C;
+  float* coef = p2 + MAX_RB_TIMES_C;
+#define BDV_EVAL_BWD_STATS(SIGN_, DZ_, NT_)                                                                                    \
+  hipLaunchKernelGGL((bn_eval_bwd_stats_kernel<SIGN_, DZ_, NT_, ES>), dim3(b.RB, b.CC), dim3(256), 0, s, dout, relu_mask, relu_act, y, \
+                     scale, running_mean, invstd, dy, dz, p1, p2, M, C, b.CVB, b.RL, b.rows_per_block)
+  BDV_ACT_SWITCH(act_dtype, ES, BDV_EVAL_DISPATCH(BDV_EVAL_BWD_STATS));
+#undef BDV_EVAL_BWD_STATS
+#undef BDV_EVAL_DISPATCH
+  BDV_LAUNCH_CHECK("bdv_bn_eval_backward(pass)");
+  // the train-mode finalize: fixed-order fp64 column sums -> dgamma / dbeta (beta_acc as bdv_bn_backward).  Its apply coefficients
+  // go to the workspace unread; `scale` stands in for the gamma they are formed from.
+  launch_bn_bwd_finalize(p1, p2, b.RB, M, C, scale, invstd, dgamma, dbeta, beta_acc, coef, S, fin_scratch, s);
+  BDV_LAUNCH_CHECK("bdv_bn_eval_backward(finalize)");
+  return BDV_OK;
+}
+
 extern "C" int bdv_bn_backward_maxpool_split(const void* dpool, const uint8_t* pool_idx, const uint32_t* relu_mask, const float* y,
                                              const float* gamma, const float* save_mean, const float* save_invstd, float* dy,
                                              float* dgamma, float* dbeta, float beta_acc, int N, int H, int W, int C, void* workspace,

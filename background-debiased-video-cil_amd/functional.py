@@ -304,16 +304,54 @@ def _bn_wgrad_backward(dout, mask, y, gamma, mean, invstd, inp, geom, need_dw, s
     return dy, dg, db, dw
 
 
+def save_plan(needs_input_grad, training, grad):
+    """-> (save, eval_grad) of a node's forward.  ``eval_grad``: it runs the differentiable eval-mode-BatchNorm form -- something
+    behind it needs a gradient, its BatchNorms are in eval mode and the caller records a graph (``grad`` = torch.is_grad_enabled()
+    at the call: inside Function.forward it is always off).  ``save``: it keeps tensors for a backward pass.  Inference keeps the
+    fused eval kernels and saves nothing; so does bf16 activation storage, whose backward then raises."""
+    need = any(needs_input_grad)
+    eval_grad = bool(need and not training and grad and K.ACT_DTYPE == torch.float32)
+    return bool(need and (training or eval_grad)), eval_grad
+
+
+def require_eval_backward(ctx):
+    """First statement of a node's backward: a node that ran its eval-mode forward without the differentiable form (bf16 activation
+    storage) has nothing saved."""
+    if not ctx.bn_training and not ctx.eval_grad:
+        _require_fp32_storage()
+        raise NotImplementedError('backward through an eval-mode BatchNorm forward that ran with gradient recording off')
+
+
+def _require_fp32_storage():
+    if K.ACT_DTYPE != torch.float32:
+        raise NotImplementedError("backward through eval-mode BatchNorm (norm_eval / frozen_stages / partial_bn, or a BatchNorm in "
+                                  ".eval() inside a training step) is not implemented for bf16 activation storage "
+                                  "(set_conv_arith('bf16')); the other arithmetics keep fp32 tensors and are supported")
+
+
+def _sign_bits(a):
+    """1-bit sign mask (a > 0) of an activation tensor, for RELU_MASK_TAP only: the units whose BatchNorm affine is frozen write
+    no mask of their own (their backward reads the sign off the activation)."""
+    one, zero = K.bn_unit_affine(a.shape[-1], a.device)
+    return K.bn_apply(a, one, zero, None, True, want_mask=True)[1]
+
+
 class StemFn(torch.autograd.Function):
     """UPSTREAM ResNet.conv1 (7x7/2 ConvModule) + ResNet.maxpool on NHWC4 input."""
 
     @staticmethod
-    def forward(ctx, x4, weight, gamma, beta, bn, training):
+    def forward(ctx, x4, weight, gamma, beta, bn, training, grad=True):
         N, H, W, _ = x4.shape
         g = K.make_geom(N, H, W, 4, weight.shape[0], weight.shape[2], weight.shape[3], 2, weight.shape[2] // 2)
         w4 = torch.zeros((weight.shape[0], weight.shape[2], weight.shape[3], 4), dtype=torch.float32, device=x4.device)
         w4[..., :3] = weight.detach().permute(0, 2, 3, 1)           # 37 KB repack, plumbing
-        save = training and any(ctx.needs_input_grad)
+        save, eval_grad = save_plan(ctx.needs_input_grad, training, grad)
+        # eval-mode BatchNorm inside a training step: 'affine' = gamma / beta trainable (norm_eval), 'frozen' = statistics and affine
+        # fixed (only the filter trains); None = train mode, or nothing behind this node needs a gradient
+        mode = None
+        if eval_grad:
+            mode = 'affine' if (ctx.needs_input_grad[2] or ctx.needs_input_grad[3]) else 'frozen'
+        a_shape = (N, g.Ho, g.Wo, weight.shape[0])
         if training:
             y, mean, invstd, scale, shift = _conv_bn_forward(x4, w4, g, bn, gamma, beta, training)
             # BN apply + ReLU + max-pool + ReLU sign mask in one pass; the activation itself is never materialised
@@ -322,38 +360,65 @@ class StemFn(torch.autograd.Function):
                 RELU_MASK_TAP.append((tuple(y.shape), mask))
             if POOL_IDX_TAP is not None:
                 POOL_IDX_TAP.append(idx)
-            a_shape = tuple(y.shape)
+            if save:
+                ctx.save_for_backward(x4, gamma, y, mask, idx, mean, invstd)
+        elif mode == 'affine':
+            # the conv without the statistics epilogue, then the train-mode tail on the running statistics' scale / shift
+            y = K.conv_fprop(x4, w4, g)
+            scale, shift = K.bn_eval_params(gamma, beta, bn.running_mean, bn.running_var, bn.eps)
+            p, idx, mask = K.bn_relu_maxpool_fwd(y, scale, shift, out_dtype=K.ACT_DTYPE)
+            if RELU_MASK_TAP is not None:
+                RELU_MASK_TAP.append((tuple(y.shape), mask))
+            if POOL_IDX_TAP is not None:
+                POOL_IDX_TAP.append(idx)
+            ctx.save_for_backward(x4, scale, y, mask, idx, bn.running_mean, K.bn_eval_invstd(bn.running_var, bn.eps))
         else:
-            a = _conv_bn_eval(x4, w4, g, bn, gamma, beta, None, True)
+            scale, shift = K.bn_eval_params(gamma, beta, bn.running_mean, bn.running_var, bn.eps)
+            a = K.conv_fprop(x4, w4, g, affine=(scale, shift, None, True))
             p, idx = K.maxpool_fwd(a, out_dtype=K.ACT_DTYPE)
-            a_shape = tuple(a.shape)
-            y = mask = mean = invstd = None
+            if mode == 'frozen':
+                if RELU_MASK_TAP is not None:
+                    RELU_MASK_TAP.append((tuple(a.shape), _sign_bits(a)))
+                if POOL_IDX_TAP is not None:
+                    POOL_IDX_TAP.append(idx)
+                ctx.save_for_backward(x4, scale, a, idx)
         ctx.g = g
         ctx.bn_training = training
+        ctx.eval_mode = mode
+        ctx.eval_grad = eval_grad
         ctx.a_shape = a_shape
-        if save:
-            ctx.save_for_backward(x4, gamma, y, mask, idx, mean, invstd)
         return p
 
     @staticmethod
     def backward(ctx, dp):
-        if not ctx.bn_training:
-            raise NotImplementedError('backward through eval-mode BatchNorm is not implemented (norm_eval=False in all CIL configs)')
-        x4, gamma, y, mask, idx, mean, invstd = ctx.saved_tensors
+        require_eval_backward(ctx)
         dp = dp if dp.is_contiguous() else dp.contiguous()
-        # max-pool backward + BN/ReLU backward in one go: the 822 MB gradient of the stem activation is never written
-        dy, dgamma, dbeta = K.bn_backward_maxpool(dp, idx, mask, y, gamma, mean, invstd)
+        dgamma = dbeta = None
+        if ctx.bn_training:
+            x4, gamma, y, mask, idx, mean, invstd = ctx.saved_tensors
+            # max-pool backward + BN/ReLU backward in one go: the 822 MB gradient of the stem activation is never written
+            dy, dgamma, dbeta = K.bn_backward_maxpool(dp, idx, mask, y, gamma, mean, invstd)
+        elif ctx.eval_mode == 'affine':
+            x4, scale, y, mask, idx, mean, invstd = ctx.saved_tensors
+            da = K.maxpool_bwd(dp, idx, ctx.a_shape)
+            dy, _, dgamma, dbeta = K.bn_eval_backward(da, scale, relu_mask=mask, y=y, running_mean=mean, invstd=invstd, want_params=True)
+        else:
+            x4, scale, a, idx = ctx.saved_tensors
+            dy = K.bn_eval_backward(K.maxpool_bwd(dp, idx, ctx.a_shape), scale, relu_act=a)[0]
         dw = None
         if ctx.needs_input_grad[1]:
             dw4 = K.conv_wgrad(dy, x4, ctx.g)
             dw = dw4[..., :3].permute(0, 3, 1, 2)
         join_side_stream(dp.device)          # the stem is the last backward node: all wgrads are visible after it
-        return None, dw, dgamma, dbeta, None, None
+        return None, dw, dgamma, dbeta, None, None, None
 
 
-def _block_forward(x, blk, training, params, save):
+def _block_forward(x, blk, training, params, save, need_params=None, eval_grad=False):
     """Forward of one residual block (UPSTREAM BasicBlock / Bottleneck, shift_place='blockres') on NHWC storage.
-    Returns (out, saved tensors for backward, geoms)."""
+    Returns (out, saved tensors for backward, geoms).  ``need_params``: which of ``params`` need a gradient (read by the
+    eval-mode form that is differentiated)."""
+    if eval_grad:
+        return _block_forward_eval_grad(x, blk, params, need_params)
     units: List[UnitSpec] = blk.unit_specs
     bns = blk.unit_bns
     n_main = blk.n_main
@@ -534,16 +599,137 @@ def _block_backward(saved, params, geoms, n_main, has_down, dout, need_params, n
     return dx, grads, prev_partial
 
 
-_EVAL_BN_BACKWARD = 'backward through eval-mode BatchNorm is not implemented (norm_eval=False in all CIL configs)'
+# ---- a block whose BatchNorms run on their running statistics inside a training step ---------------------------------------
+# (UPSTREAM ResNet(norm_eval=True), ResNetTSM(partial_bn=True), any BatchNorm a user put into .eval()).  Per conv+BN unit, by
+# whether its gamma / beta need a gradient:
+#   affine live:   conv (no statistics epilogue) -> bn_apply with the eval scale / shift, mask written; saved like a train-mode unit
+#                  with (running_mean, invstd of running_var) as the statistics; backward = bn_eval_backward with dgamma / dbeta
+#   affine frozen: the fused eval kernel (conv + folded BatchNorm + residual + ReLU); only the activation is kept -- the operand of
+#                  the next weight gradient anyway -- and the backward reads the ReLU sign off it: no raw conv output, no mask
+# Saved per unit (SAVED_PER_UNIT slots): y | None, activation, running_mean | None, invstd | None, mask | None, scale, None; a
+# downsample branch adds yd | None, running_mean | None, invstd | None, scale.
+def _block_forward_eval_grad(x, blk, params, need_params):
+    units: List[UnitSpec] = blk.unit_specs
+    bns = blk.unit_bns
+    n_main = blk.n_main
+    has_down = len(units) > n_main
+    N, H, W, _ = x.shape
+
+    def live(i):
+        return bool(need_params[3 * i + 1] or need_params[3 * i + 2])
+
+    def eval_affine(i):
+        return K.bn_eval_params(params[3 * i + 1], params[3 * i + 2], bns[i].running_mean, bns[i].running_var, bns[i].eps)
+
+    saved, geoms = [x], []
+    identity, id_affine, down_saved = x, None, None
+    if has_down:
+        wd = params[3 * n_main]
+        gdn = units[n_main].geom(N, H, W)
+        sc_d, sh_d = eval_affine(n_main)
+        if live(n_main):
+            yd = K.conv_fprop(x, weight_krsc(wd), gdn)
+            if live(n_main - 1):        # the block-output pass applies the downsample BatchNorm itself (res_affine)
+                identity, id_affine = yd, (sc_d, sh_d)
+            else:                       # the fused kernel of a frozen last unit takes a finished residual
+                identity = K.bn_apply(yd, sc_d, sh_d, None, False)
+            down_saved = [yd, bns[n_main].running_mean, K.bn_eval_invstd(bns[n_main].running_var, bns[n_main].eps), sc_d]
+        else:
+            identity = K.conv_fprop(x, weight_krsc(wd), gdn, affine=(sc_d, sh_d, None, False))
+            down_saved = [None, None, None, sc_d]
+    cur, h, w_ = x, H, W
+    for i in range(n_main):
+        u = units[i]
+        g = u.geom(N, h, w_)
+        geoms.append(g)
+        last = i == n_main - 1
+        h2, w2 = u.out_hw(h, w_)
+        sc, sh = eval_affine(i)
+        if live(i):
+            y = K.conv_fprop(cur, weight_krsc(params[3 * i]), g).view(N, h2, w2, u.cout)
+            a, mask = K.bn_apply(y, sc, sh, identity if last else None, True, want_mask=True, res_affine=id_affine if last else None)
+            saved += [y, a, bns[i].running_mean, K.bn_eval_invstd(bns[i].running_var, bns[i].eps), mask, sc, None]
+            if RELU_MASK_TAP is not None:
+                RELU_MASK_TAP.append((tuple(a.shape), mask))
+        else:
+            a = K.conv_fprop(cur, weight_krsc(params[3 * i]), g, affine=(sc, sh, identity if last else None, True)).view(N, h2, w2, u.cout)
+            saved += [None, a, None, None, None, sc, None]
+            if RELU_MASK_TAP is not None:
+                RELU_MASK_TAP.append((tuple(a.shape), _sign_bits(a)))
+        cur, h, w_ = a, h2, w2
+    if has_down:
+        saved += down_saved
+        geoms.append(gdn)
+    return cur, saved, geoms
+
+
+def _block_backward_eval(saved, params, geoms, n_main, has_down, dout, need_params, need_dx):
+    """Backward of ``_block_forward_eval_grad``: one bn_eval_backward pass per unit (no statistics hand-over between kernels:
+    dy does not depend on the sums).  Returns (dx, parameter gradients, None)."""
+    x = saved[0]
+    Q = SAVED_PER_UNIT
+    ys = [saved[1 + Q * i] for i in range(n_main)]
+    acts = [saved[2 + Q * i] for i in range(n_main)]
+    means = [saved[3 + Q * i] for i in range(n_main)]
+    invstds = [saved[4 + Q * i] for i in range(n_main)]
+    masks = [saved[5 + Q * i] for i in range(n_main)]
+    scales = [saved[6 + Q * i] for i in range(n_main)]
+    dout = dout if dout.is_contiguous() else dout.contiguous()
+    grads: List[Optional[torch.Tensor]] = [None] * len(params)
+    k = n_main - 1
+    d, dz_out, dy_first = dout, None, None
+    for i in range(k, -1, -1):
+        wt = params[3 * i]
+        inp = acts[i - 1] if i > 0 else x
+        # the masked gradient of the block output also enters the downsample BatchNorm, or -- without one -- the identity path,
+        # which re-derives it from (dout, mask) in the conv1 dgrad epilogue where a mask exists
+        want_dz = i == k and (has_down or (need_dx and masks[k] is None))
+        if ys[i] is not None:
+            dy, dz, grads[3 * i + 1], grads[3 * i + 2] = K.bn_eval_backward(
+                d, scales[i], relu_mask=masks[i], y=ys[i], running_mean=means[i], invstd=invstds[i], want_params=True, want_dz=want_dz)
+        else:
+            dy, dz, _, _ = K.bn_eval_backward(d, scales[i], relu_act=acts[i], want_dz=want_dz)
+        if i == k:
+            dz_out = dz
+        if need_params[3 * i]:
+            grads[3 * i] = grad_like_weight(wgrad_overlapped(dy, inp, geoms[i]), wt)
+        if i == 0:
+            dy_first = dy
+        elif need_dx or any(need_params[:3 * i]):
+            d = K.conv_dgrad(dy, weight_krsc(wt), geoms[i]).view_as(inp)
+        else:
+            break                      # nothing below this unit needs a gradient
+    dx = None
+    if has_down:
+        yd, mean_d, invstd_d, sc_d = saved[1 + Q * n_main:5 + Q * n_main]
+        wd, gdn = params[3 * n_main], geoms[n_main]
+        if yd is not None:
+            dyd, _, grads[3 * n_main + 1], grads[3 * n_main + 2] = K.bn_eval_backward(
+                dz_out, sc_d, y=yd, running_mean=mean_d, invstd=invstd_d, want_params=True)
+        elif need_params[3 * n_main] or need_dx:
+            dyd = K.bn_eval_backward(dz_out, sc_d)[0]
+        if need_params[3 * n_main]:
+            grads[3 * n_main] = grad_like_weight(wgrad_overlapped(dyd, x, gdn), wd)
+        if need_dx:
+            dx_id = K.conv_dgrad(dyd, weight_krsc(wd), gdn)
+            dx = K.conv_dgrad(dy_first, weight_krsc(params[0]), geoms[0], add_src=dx_id)
+    elif need_dx:
+        if masks[k] is not None:
+            dx = K.conv_dgrad(dy_first, weight_krsc(params[0]), geoms[0], add_src=dout, add_mask_src=masks[k])
+        else:
+            dx = K.conv_dgrad(dy_first, weight_krsc(params[0]), geoms[0], add_src=dz_out)
+    if dx is not None:
+        dx = dx.view_as(x)
+    return dx, grads, None
 
 
 class ResBlockFn(torch.autograd.Function):
     """One residual block as an autograd node (used when a stage cannot run as one node, e.g. hooks on its blocks)."""
 
     @staticmethod
-    def forward(ctx, x, blk, training, *params):
-        save = training and any(ctx.needs_input_grad)
-        out, saved, geoms = _block_forward(x, blk, training, params, save)
+    def forward(ctx, x, blk, training, grad, *params):
+        save, eval_grad = save_plan(ctx.needs_input_grad, training, grad)
+        out, saved, geoms = _block_forward(x, blk, training, params, save, ctx.needs_input_grad[4:], eval_grad)
         if save:
             ctx.save_for_backward(*saved, *params)
             ctx.n_saved = len(saved)
@@ -551,18 +737,21 @@ class ResBlockFn(torch.autograd.Function):
         ctx.n_main = blk.n_main
         ctx.has_down = len(blk.unit_specs) > blk.n_main
         ctx.bn_training = training
+        ctx.eval_grad = eval_grad
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        if not ctx.bn_training:
-            raise NotImplementedError(_EVAL_BN_BACKWARD)
+        require_eval_backward(ctx)
         t = ctx.saved_tensors
         saved, params = t[:ctx.n_saved], t[ctx.n_saved:]
-        need = ctx.needs_input_grad      # (x, blk, training, *params)
+        need = ctx.needs_input_grad      # (x, blk, training, grad, *params)
+        backward = _block_backward if ctx.bn_training else _block_backward_eval
         with wgrad_batch():
-            dx, grads, _ = _block_backward(saved, params, ctx.geoms, ctx.n_main, ctx.has_down, dout, need[3:], need[0])
-        return (dx, None, None, *grads)
+            dx, grads, _ = backward(saved, params, ctx.geoms, ctx.n_main, ctx.has_down, dout, need[4:], need[0])
+        if not need[0]:
+            join_side_stream(dout.device)    # nothing below needs a gradient (frozen stem / stages): the last backward node
+        return (dx, None, None, None, *grads)
 
 
 class StageLink:
@@ -588,35 +777,37 @@ class ResStageFn(torch.autograd.Function):
     (widest) tensor.  Arithmetic per block is that of ResBlockFn."""
 
     @staticmethod
-    def forward(ctx, x, blocks, training, in_link, out_link, *params):
-        save = training and any(ctx.needs_input_grad)
+    def forward(ctx, x, blocks, training, in_link, out_link, grad, *params):
+        save, eval_grad = save_plan(ctx.needs_input_grad, training, grad)
         cur, off = x, 0
         all_saved, meta = [], []
         for blk in blocks:
             npar = 3 * len(blk.unit_specs)
-            out, saved, geoms = _block_forward(cur, blk, training, params[off:off + npar], save)
+            out, saved, geoms = _block_forward(cur, blk, training, params[off:off + npar], save,
+                                               ctx.needs_input_grad[6 + off:6 + off + npar], eval_grad)
             meta.append((len(saved), npar, geoms, blk.n_main, len(blk.unit_specs) > blk.n_main))
             all_saved += saved
             off += npar
             cur = out
         # the previous stage's last unit: operands for the statistics this stage's first conv1 dgrad can take for it
-        in_stats = in_link.stats if (save and in_link is not None and CROSS_STAGE_STATS and FUSE_BN_STATS) else None
+        # (train mode only: an eval-mode BatchNorm's backward has no statistics to hand over)
+        in_stats = in_link.stats if (save and training and in_link is not None and CROSS_STAGE_STATS and FUSE_BN_STATS) else None
         if in_stats is not None and not (meta[0][2][0].stride == 1 and ctx.needs_input_grad[0]):
             in_stats = None
         if save:
             ctx.save_for_backward(*all_saved, *params, *(in_stats or ()))
-            if out_link is not None:
+            if out_link is not None and training:
                 out_link.stats = _block_out_stats(all_saved[len(all_saved) - meta[-1][0]:], meta[-1][3])
         ctx.in_link = in_link if in_stats is not None else None
-        ctx.out_link = out_link if save else None
+        ctx.out_link = out_link if (save and training) else None
         ctx.meta = meta
         ctx.bn_training = training
+        ctx.eval_grad = eval_grad
         return cur
 
     @staticmethod
     def backward(ctx, dout):
-        if not ctx.bn_training:
-            raise NotImplementedError(_EVAL_BN_BACKWARD)
+        require_eval_backward(ctx)
         t = ctx.saved_tensors
         meta = ctx.meta
         n_saved_total = sum(m[0] for m in meta)
@@ -624,7 +815,7 @@ class ResStageFn(torch.autograd.Function):
         if ctx.in_link is not None:
             t, in_stats = t[:-4], tuple(t[-4:])
         saved_all, params_all = t[:n_saved_total], t[n_saved_total:]
-        need = ctx.needs_input_grad      # (x, blocks, training, in_link, out_link, *params)
+        need = ctx.needs_input_grad      # (x, blocks, training, in_link, out_link, grad, *params)
         s_off = [0]
         p_off = [0]
         for m in meta:
@@ -639,17 +830,28 @@ class ResStageFn(torch.autograd.Function):
                 n_saved, npar, geoms, n_main, has_down = meta[k]
                 saved = saved_all[s_off[k]:s_off[k + 1]]
                 params = params_all[p_off[k]:p_off[k + 1]]
+                if not ctx.bn_training:
+                    # a block's dx feeds the blocks below it: not needed once nothing below needs a gradient
+                    need_dx = need[0] or any(need[6:6 + p_off[k]])
+                    d, grads, part = _block_backward_eval(saved, params, geoms, n_main, has_down, d,
+                                                          need[6 + p_off[k]:6 + p_off[k + 1]], need_dx)
+                    grads_all[p_off[k]:p_off[k + 1]] = grads
+                    if d is None:
+                        break
+                    continue
                 prev_stats = in_stats if k == 0 else None
                 if k > 0:
                     pm = meta[k - 1]
                     prev_stats = _block_out_stats(saved_all[s_off[k - 1]:s_off[k]], pm[3])
                 need_dx = need[0] or k > 0
-                d, grads, part = _block_backward(saved, params, geoms, n_main, has_down, d, need[5 + p_off[k]:5 + p_off[k + 1]],
+                d, grads, part = _block_backward(saved, params, geoms, n_main, has_down, d, need[6 + p_off[k]:6 + p_off[k + 1]],
                                                  need_dx, out_stat_partial=part, prev_stats=prev_stats)
                 grads_all[p_off[k]:p_off[k + 1]] = grads
         if ctx.in_link is not None:
             ctx.in_link.partial = part   # tile sums of the statistics of `d` against the previous stage's last unit
-        return (d, None, None, None, None, *grads_all)
+        if not need[0]:
+            join_side_stream(dout.device)    # nothing below needs a gradient (frozen stem / stages): the last backward node
+        return (d, None, None, None, None, None, *grads_all)
 
 
 class AvgPoolFn(torch.autograd.Function):

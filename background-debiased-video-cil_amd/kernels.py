@@ -634,6 +634,73 @@ def bn_backward_pair(dout, relu_mask, ya, gamma_a, mean_a, invstd_a, yb, gamma_b
     return (dya, pg[0], pg[1]), (dyb, pg[2], pg[3])
 
 
+_BN_UNIT = {}       # (device, C) -> (ones, zeros): the identity affine
+
+
+def bn_unit_affine(C, device):
+    """(ones, zeros) of C channels on ``device``, cached: gamma / beta (or scale / shift) of an identity BatchNorm."""
+    key = (device.type, device.index or 0, C)
+    unit = _BN_UNIT.get(key)
+    if unit is None:
+        unit = _BN_UNIT[key] = (torch.ones(C, dtype=torch.float32, device=device), torch.zeros(C, dtype=torch.float32, device=device))
+    return unit
+
+
+def bn_eval_invstd(running_var, eps):
+    """1 / sqrt(running_var + eps) as ``bn_eval_params`` rounds it (scale for gamma = 1): the invstd of an eval-mode BatchNorm."""
+    one, zero = bn_unit_affine(running_var.numel(), running_var.device)
+    return bn_eval_params(one, zero, zero, running_var, eps)[0]
+
+
+def bn_eval_backward(dout, scale, relu_mask=None, relu_act=None, y=None, running_mean=None, invstd=None, want_params=False,
+                     want_dz=False, dgamma=None, dbeta=None, beta_acc=0.0, dy=None, splits=0):
+    """Backward through an eval-mode BatchNorm (+ ReLU) -> (dy, dz | None, dgamma | None, dbeta | None).
+    ``scale`` = gamma * invstd_running (``bn_eval_params``); dz = dout * sign, dy = dz * scale.  Sign: ``relu_mask`` (the bits of
+    ``bn_apply(want_mask=True)``), or ``relu_act`` (an activation: act > 0), or neither (no ReLU).  ``want_params`` (or ``dgamma`` /
+    ``dbeta`` to accumulate into with ``beta_acc``): also dbeta = sum dz, dgamma = sum dz * (y - running_mean) * invstd, which needs
+    ``y``, ``running_mean`` and ``invstd``; without it none of the three is read.  ``splits``: as ``bn_train_finalize``."""
+    C = dout.shape[-1]
+    M = dout.numel() // C
+    _chk_act(dout, name='dout')
+    _chk(scale, (C,), name='scale')
+    if relu_mask is not None and relu_act is not None:
+        raise ValueError('bn_eval_backward: relu_mask and relu_act are two sources of the same sign: give one')
+    if relu_mask is not None:
+        if C % 32 != 0:
+            raise ValueError('bn_eval_backward: a ReLU mask needs C % 32 == 0')
+        _chk(relu_mask, (dout.numel() // 32,), dtype=torch.int32, name='relu_mask')
+    if relu_act is not None:
+        _chk_act(relu_act, tuple(dout.shape), name='relu_act', like=dout)
+    params = want_params or dgamma is not None or dbeta is not None
+    ws = fs = None
+    if params:
+        if y is None or running_mean is None or invstd is None:
+            raise ValueError('bn_eval_backward: parameter gradients need y, running_mean and invstd')
+        _chk_act(y, tuple(dout.shape), name='y', like=dout)
+        _chk(running_mean, (C,), name='running_mean')
+        _chk(invstd, (C,), name='invstd')
+        if (dgamma is None) != (dbeta is None):
+            raise ValueError('bn_eval_backward: give dgamma and dbeta together (to accumulate into) or neither')
+        if dgamma is None:
+            dgamma = torch.empty(C, dtype=torch.float32, device=dout.device)
+            dbeta = torch.empty(C, dtype=torch.float32, device=dout.device)
+            beta_acc = 0.0
+        _chk(dgamma, (C,), name='dgamma')
+        _chk(dbeta, (C,), name='dbeta')
+        ws = _bn_ws(M, C, dout.device)
+        fs = _bn_fin_scratch(C, dout.device) if splits != 1 else None
+    else:
+        y = running_mean = invstd = None
+    d = dy if dy is not None else torch.empty_like(dout)
+    _chk_act(d, tuple(dout.shape), name='dy', like=dout)
+    dz = torch.empty_like(dout) if want_dz else None
+    check(lib().bdv_bn_eval_backward(_p(dout), _p(relu_mask), _p(relu_act), _p(y), _p(scale), _p(running_mean), _p(invstd), _p(d),
+                                     _p(dz), _p(dgamma), _p(dbeta), float(beta_acc), M, C, _p(ws), ws.numel() if ws is not None else 0,
+                                     _act_code(dout), int(splits), _p(fs), fs.numel() if fs is not None else 0, _stream()),
+          'bdv_bn_eval_backward')
+    return d, dz, dgamma, dbeta
+
+
 def bn_backward_maxpool(dpool, pool_idx, relu_mask, y, gamma, save_mean, save_invstd, splits=0):
     """BN(+ReLU) backward behind MaxPool2d(3,2,1) (the stem): the pooled gradient is expanded on the fly.
     -> (dy, dgamma, dbeta)."""

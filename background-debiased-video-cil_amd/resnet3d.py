@@ -12,7 +12,7 @@ How the 3-D network maps onto the 2-D kernels (activations stay fp32 NHWC frames
 * the stem ``5 x 7 x 7`` / stride (2, 2, 2) convolution is five per-frame ``7 x 7`` / 2 stem convolutions over the frame
   subsets ``2t + dt - 2``, accumulated through the conv epilogue's residual input; ``pool1`` (1 x 3 x 3, stride 2 in time)
   is the spatial max-pool of every second frame; ``pool2`` (2 x 1 x 1) is ``bdv_maxpool_t2``.
-* ``norm_eval=False``, ``inflate_style='3x1x1'``, ``non_local`` off, ``with_pool2=True``, temporal strides 1: the i3d_r50 config.
+* ``inflate_style='3x1x1'``, ``non_local`` off, ``with_pool2=True``, temporal strides 1: the i3d_r50 config.
 """
 from __future__ import annotations
 
@@ -87,7 +87,7 @@ class _Stem3dFn(torch.autograd.Function):
     x4: (B*T, H, W, 4), T frames per clip.  Output: (B*T/4, H/4, W/4, 64) frames."""
 
     @staticmethod
-    def forward(ctx, x4, weight, gamma, beta, bn, training, T):
+    def forward(ctx, x4, weight, gamma, beta, bn, training, T, grad=True):
         N, H, W, _ = x4.shape
         B = N // T
         Cout, _, kt, kh, kw = weight.shape
@@ -125,7 +125,9 @@ class _Stem3dFn(torch.autograd.Function):
             y = K.conv_fprop(taps[0], ws[0], g)
             for dt in range(1, kt):                                       # y += conv(tap dt): residual input of the folded epilogue
                 y = K.conv_fprop(taps[dt], ws[dt], g, affine=(one, zero, y, False))
-        save = training and any(ctx.needs_input_grad)
+        save, eval_grad = Fn.save_plan(ctx.needs_input_grad, training, grad)
+        # eval-mode BatchNorm inside a training step (Fn.StemFn): 'affine' = gamma / beta trainable, 'frozen' = only the filter trains
+        mode = None
         if training:
             rm = bn.running_mean if bn.track_running_stats else None
             rv = bn.running_var if bn.track_running_stats else None
@@ -133,10 +135,16 @@ class _Stem3dFn(torch.autograd.Function):
         else:
             scale, shift = K.bn_eval_params(gamma, beta, bn.running_mean, bn.running_var, bn.eps)
             mean = invstd = None
-        if save:
+            if eval_grad:
+                mode = 'affine' if (ctx.needs_input_grad[2] or ctx.needs_input_grad[3]) else 'frozen'
+                if mode == 'affine':
+                    mean, invstd = bn.running_mean, K.bn_eval_invstd(bn.running_var, bn.eps)
+        if save and mode != 'frozen':
             a, mask = K.bn_apply(y, scale, shift, None, True, want_mask=True)
         else:
             a, mask = K.bn_apply(y, scale, shift, None, True), None
+            if mode == 'frozen' and Fn.RELU_MASK_TAP is not None:
+                Fn.RELU_MASK_TAP.append((tuple(y.shape), Fn._sign_bits(a)))
         # pool1: temporal kernel 1, stride 2 -> the even frames; spatial 3x3 / 2
         Tp = (To - 1) // 2 + 1
         even = a.view(B, To, g.Ho, g.Wo, Cout)[:, ::2].contiguous().view(B * Tp, g.Ho, g.Wo, Cout)
@@ -147,22 +155,36 @@ class _Stem3dFn(torch.autograd.Function):
             Fn.POOL_IDX_TAP.append(pidx)
         ctx.meta = (g, B, To, Tp, kt, fused)
         ctx.bn_training = training
-        if save:
-            ctx.save_for_backward(gamma, y, mask, pidx, mean, invstd, *taps)
+        ctx.eval_mode = mode
+        ctx.eval_grad = eval_grad
+        if mode == 'frozen':        # neither the raw conv output nor a mask: the sign is read off the activation
+            ctx.save_for_backward(scale, a, pidx, *taps)
+        elif save:
+            ctx.save_for_backward(gamma if training else scale, y, mask, pidx, mean, invstd, *taps)
         return p
 
     @staticmethod
     def backward(ctx, dp):
-        if not ctx.bn_training:
-            raise NotImplementedError('backward through eval-mode BatchNorm is not implemented')
-        gamma, y, mask, pidx, mean, invstd, *taps = ctx.saved_tensors
         g, B, To, Tp, kt, fused = ctx.meta
-        Cout = y.shape[-1]
+        Fn.require_eval_backward(ctx)
+        if ctx.eval_mode == 'frozen':
+            scale, a, pidx, *taps = ctx.saved_tensors
+            Cout = a.shape[-1]
+        else:
+            gamma, y, mask, pidx, mean, invstd, *taps = ctx.saved_tensors     # (eval-mode 'affine': the scale in gamma's place)
+            Cout = y.shape[-1]
         dp = dp if dp.is_contiguous() else dp.contiguous()
         d_even = K.maxpool_bwd(dp, pidx, (B * Tp, g.Ho, g.Wo, Cout))
         da = torch.zeros((B, To, g.Ho, g.Wo, Cout), dtype=torch.float32, device=dp.device)   # odd frames: unused by pool1
         da[:, ::2] = d_even.view(B, Tp, g.Ho, g.Wo, Cout)
-        dy, dgamma, dbeta = K.bn_backward(da.view(B * To, g.Ho, g.Wo, Cout), mask, y, gamma, mean, invstd, True)
+        da = da.view(B * To, g.Ho, g.Wo, Cout)
+        dgamma = dbeta = None
+        if ctx.bn_training:
+            dy, dgamma, dbeta = K.bn_backward(da, mask, y, gamma, mean, invstd, True)
+        elif ctx.eval_mode == 'affine':
+            dy, _, dgamma, dbeta = K.bn_eval_backward(da, gamma, relu_mask=mask, y=y, running_mean=mean, invstd=invstd, want_params=True)
+        else:
+            dy = K.bn_eval_backward(da, scale, relu_act=a)[0]
         dw = None
         if ctx.needs_input_grad[1]:
             if fused:
@@ -172,7 +194,7 @@ class _Stem3dFn(torch.autograd.Function):
                 parts = [K.conv_wgrad(dy, taps[dt], g)[..., :3] for dt in range(kt)]     # each (Cout, kh, kw, 3)
                 dw = torch.stack(parts, dim=1).permute(0, 4, 1, 2, 3)                    # (Cout, 3, kt, kh, kw)
         Fn.join_side_stream(dp.device)
-        return None, dw, dgamma, dbeta, None, None, None
+        return None, dw, dgamma, dbeta, None, None, None, None
 
 
 class _PoolT2Fn(torch.autograd.Function):
@@ -197,7 +219,7 @@ class ResNet3d(nn.Module):
     arch_settings = {50: (Bottleneck3d, (3, 4, 6, 3))}
 
     def __init__(self, depth=50, pretrained=None, pretrained2d=True, conv1_kernel=(5, 7, 7), conv1_stride_t=2, pool1_stride_t=2,
-                 conv_cfg=None, norm_eval=False, inflate=(1, 1, 1, 1), inflate_style='3x1x1', with_pool2=True,
+                 conv_cfg=None, norm_eval=False, frozen_stages=-1, inflate=(1, 1, 1, 1), inflate_style='3x1x1', with_pool2=True,
                  zero_init_residual=False, **kwargs):
         super().__init__()
         if depth not in self.arch_settings:
@@ -206,7 +228,10 @@ class ResNet3d(nn.Module):
             raise NotImplementedError('ResNet3d: only the i3d_r50 settings (conv1 5x7x7 / 2, pool1 stride_t 2, 3x1x1 inflation, pool2)')
         if conv_cfg not in (None, dict(type='Conv3d')):
             raise NotImplementedError(f'conv_cfg {conv_cfg}')
+        if not -1 <= frozen_stages <= 4:
+            raise ValueError(f'frozen_stages={frozen_stages}: -1 (nothing), 0 (the stem) ... 4 (the stem and all four stages)')
         self.depth, self.pretrained, self.pretrained2d, self.norm_eval = depth, pretrained, pretrained2d, norm_eval
+        self.frozen_stages = frozen_stages
         self.zero_init_residual = zero_init_residual
         block, counts = self.arch_settings[depth]
         self.conv1 = ConvModule3d(3, 64, (5, 7, 7), (2, 2, 2), (2, 3, 3), act=True)
@@ -227,11 +252,13 @@ class ResNet3d(nn.Module):
                 if b == 0 and (s != 1 or inplanes != planes * block.expansion):
                     down = ConvModule3d(inplanes, planes * block.expansion, (1, 1, 1), (1, s, s), act=False)
                 blocks.append(block(inplanes, planes, s, bool(infl[b]), down))
+                blocks[-1].block_name = f'layer{i + 1}.{b}'
                 inplanes = planes * block.expansion
             name = f'layer{i + 1}'
             setattr(self, name, ResStage(*blocks))
             self.res_layers.append(name)
         self.feat_dim = inplanes
+        self._freeze_stages()
 
     def init_weights(self):
         if isinstance(self.pretrained, str):
@@ -263,9 +290,10 @@ class ResNet3d(nn.Module):
         x4 = K.nchw3_to_nhwc4(frames.contiguous())
         stem = self.conv1
         training = stem.bn.training
-        if training and stem.bn.track_running_stats:
-            torch._foreach_add_([m.num_batches_tracked for m in self.modules() if isinstance(m, nn.BatchNorm3d) and m.training], 1)
-        p = _Stem3dFn.apply(x4, stem.conv.weight, stem.bn.weight, stem.bn.bias, stem.bn, training, T)
+        tracked = [m.num_batches_tracked for m in self.modules() if isinstance(m, nn.BatchNorm3d) and m.training and m.track_running_stats]
+        if tracked:        # every BatchNorm that normalises with batch statistics in this call (frozen_stages: not all of them do)
+            torch._foreach_add_(tracked, 1)
+        p = _Stem3dFn.apply(x4, stem.conv.weight, stem.bn.weight, stem.bn.bias, stem.bn, training, T, torch.is_grad_enabled())
         t1 = p.shape[0] // B                                             # frames per clip after conv1 and pool1
         if t1 % 2:
             raise ValueError(f'{T} input frames leave {t1} frames for pool2, which pairs them')
@@ -278,8 +306,22 @@ class ResNet3d(nn.Module):
         n, c, h, w = out.shape
         return out.reshape(B, n // B, c, h, w).permute(0, 2, 1, 3, 4)    # (B, C, T', h, w) view
 
+    def _freeze_stages(self):
+        """UPSTREAM ResNet3d._freeze_stages: the stem in eval mode without gradients, then ``layer1 .. layer{frozen_stages}``."""
+        if self.frozen_stages >= 0:
+            self.conv1.eval()
+            for p in self.conv1.parameters():
+                p.requires_grad = False
+        for i in range(1, self.frozen_stages + 1):
+            m = getattr(self, f'layer{i}')
+            m.eval()
+            for p in m.parameters():
+                p.requires_grad = False
+
     def train(self, mode=True):
+        """Re-applies ``frozen_stages`` and ``norm_eval`` on every call, as upstream."""
         super().train(mode)
+        self._freeze_stages()
         if mode and self.norm_eval:
             for m in self.modules():
                 if isinstance(m, nn.BatchNorm3d):

@@ -138,9 +138,21 @@ class _ResBlock(nn.Module):
         params = []
         for m in self.unit_modules:
             params += [m.raw_conv.weight, m.bn.weight, m.bn.bias]
-        training = self.unit_bns[0].training
-        out = Fn.ResBlockFn.apply(xh, self, training, *params)
+        out = Fn.ResBlockFn.apply(xh, self, self.bn_training(), torch.is_grad_enabled(), *params)
         return Fn.nhwc_to_nchw_view(out)
+
+    def bn_training(self) -> bool:
+        """The mode the block's kernels run in: that of its BatchNorms, which must agree (a block is one autograd node whose
+        units hand statistics and masks to each other; a block that normalises one unit with batch statistics and the next with
+        running ones is not something any backbone option produces)."""
+        bns = self.unit_bns
+        training = bns[0].training
+        if any(b.training != training for b in bns):
+            names = self.main_names + (['downsample'] if self.downsample is not None else [])
+            modes = ', '.join(f"{n}.bn: {'train' if b.training else 'eval'}" for n, b in zip(names, bns))
+            raise ValueError(f"block {getattr(self, 'block_name', type(self).__name__)}: its BatchNorms must all be in train mode "
+                             f'or all in eval mode ({modes})')
+        return training
 
 
 class ResStage(nn.Sequential):
@@ -170,10 +182,10 @@ class ResStage(nn.Sequential):
         for b in blocks:
             for m in b.unit_modules:
                 params += [m.raw_conv.weight, m.bn.weight, m.bn.bias]
-        flags = {b.unit_bns[0].training for b in blocks}
+        flags = {b.bn_training() for b in blocks}       # every unit of every block (a mixed block raises)
         if len(flags) != 1:
             return super().forward(x)
-        out = Fn.ResStageFn.apply(xh, blocks, flags.pop(), in_link, out_link, *params)
+        out = Fn.ResStageFn.apply(xh, blocks, flags.pop(), in_link, out_link, torch.is_grad_enabled(), *params)
         return Fn.nhwc_to_nchw_view(out)
 
 
@@ -223,7 +235,8 @@ class ResNetTSM(nn.Module):
     arch_settings = {18: (BasicBlock, (2, 2, 2, 2)), 34: (BasicBlock, (3, 4, 6, 3)), 50: (Bottleneck, (3, 4, 6, 3))}
 
     def __init__(self, depth, num_segments=8, is_shift=True, non_local=(0, 0, 0, 0), non_local_cfg=None, shift_div=8,
-                 shift_place='blockres', temporal_pool=False, pretrained=None, norm_eval=False, **kwargs):
+                 shift_place='blockres', temporal_pool=False, pretrained=None, norm_eval=False, frozen_stages=-1, partial_bn=False,
+                 **kwargs):
         super().__init__()
         if depth not in self.arch_settings:
             raise KeyError(f'invalid depth {depth} for resnet')
@@ -231,7 +244,9 @@ class ResNetTSM(nn.Module):
             raise NotImplementedError('only shift_place="blockres" without temporal_pool / non_local is on the hot path '
                                       '(all 84 CIL configs; SURVEY.md section 8)')
         self.depth, self.num_segments, self.is_shift, self.shift_div = depth, num_segments, is_shift, shift_div
-        self.pretrained, self.norm_eval = pretrained, norm_eval
+        if not -1 <= frozen_stages <= 4:
+            raise ValueError(f'frozen_stages={frozen_stages}: -1 (nothing), 0 (the stem) ... 4 (the stem and all four stages)')
+        self.pretrained, self.norm_eval, self.frozen_stages, self.partial_bn = pretrained, norm_eval, frozen_stages, partial_bn
         block, counts = self.arch_settings[depth]
         self.conv1 = ConvModule(3, 64, 7, 2, 3, act=True)
         self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)       # holder only; fused into StemFn
@@ -246,12 +261,14 @@ class ResNetTSM(nn.Module):
                 if b == 0 and (s != 1 or inplanes != planes * block.expansion):
                     down = ConvModule(inplanes, planes * block.expansion, 1, s, 0, act=False)
                 blocks.append(block(inplanes, planes, s, down))
+                blocks[-1].block_name = f'layer{i + 1}.{b}'
                 inplanes = planes * block.expansion
             name = f'layer{i + 1}'
             setattr(self, name, ResStage(*blocks))
             self.res_layers.append(name)
         self.feat_dim = inplanes
         self._shift_made = False
+        self._freeze_stages()
 
     # ---- initialisation (UPSTREAM ResNet.init_weights + ResNetTSM.make_temporal_shift) ----
     def init_weights(self):
@@ -322,9 +339,11 @@ class ResNetTSM(nn.Module):
             x4 = K.nchw3_to_nhwc4(x.contiguous())
         stem = self.conv1
         training = stem.bn.training
-        if training and stem.bn.track_running_stats:
-            torch._foreach_add_([b.num_batches_tracked for b in self._bn_modules() if b.training], 1)
-        p = Fn.StemFn.apply(x4, stem.conv.weight, stem.bn.weight, stem.bn.bias, stem.bn, training)
+        # every BatchNorm that normalises with batch statistics in this call (frozen_stages / partial_bn: not all of them do)
+        tracked = [b.num_batches_tracked for b in self._bn_modules() if b.training and b.track_running_stats]
+        if tracked:
+            torch._foreach_add_(tracked, 1)
+        p = Fn.StemFn.apply(x4, stem.conv.weight, stem.bn.weight, stem.bn.bias, stem.bn, training, torch.is_grad_enabled())
         out = Fn.nhwc_to_nchw_view(p)
         link = None
         stages = [getattr(self, name) for name in self.res_layers]
@@ -338,7 +357,8 @@ class ResNetTSM(nn.Module):
                 nxt = stages[i + 1] if i + 1 < len(stages) else None
                 private = (nxt is not None and isinstance(nxt, ResStage) and not _has_hooks(stage, pre=False) and not _has_hooks(nxt, pre=True)
                            and not _global_module_hooks())
-                link = Fn.StageLink() if (training and private) else None
+                # (the stages decide themselves: only two train-mode stages hand statistics over -- ResStageFn)
+                link = Fn.StageLink() if private else None
                 stage._out_link = link
             else:
                 link = None
@@ -349,10 +369,34 @@ class ResNetTSM(nn.Module):
                     stage._in_link = stage._out_link = None      # (a stage that raised or was replaced never took them)
         return out
 
+    # ---- UPSTREAM ResNet._freeze_stages / ResNet._partial_bn / ResNet.train --------------------------------------------
+    def _freeze_stages(self):
+        """``frozen_stages >= 0``: the stem in eval mode without gradients, then ``layer1 .. layer{frozen_stages}`` likewise."""
+        if self.frozen_stages >= 0:
+            self.conv1.bn.eval()
+            for p in self.conv1.parameters():
+                p.requires_grad = False
+        for i in range(1, self.frozen_stages + 1):
+            m = getattr(self, f'layer{i}')
+            m.eval()
+            for p in m.parameters():
+                p.requires_grad = False
+
+    def _partial_bn(self):
+        """Every BatchNorm but the first in module order (the stem's): running statistics, weight and bias fixed."""
+        for k, m in enumerate(self._bn_modules()):
+            if k >= 1:
+                m.eval()
+                m.weight.requires_grad = False
+                m.bias.requires_grad = False
+
     def train(self, mode=True):
+        """Re-applies the three options on every call, as upstream: ``unfreeze_backbone()`` followed by ``train()`` restores them."""
         super().train(mode)
+        self._freeze_stages()
         if mode and self.norm_eval:
-            for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.eval()
+            for m in self._bn_modules():
+                m.eval()
+        if mode and self.partial_bn:
+            self._partial_bn()
         return self

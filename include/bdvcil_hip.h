@@ -293,6 +293,25 @@ int bdv_bn_backward_pair(const void* dout, const uint32_t* relu_mask, const void
                          const float* mean_b, const float* invstd_b, void* dyb, float* dgamma_b, float* dbeta_b,
                          int64_t M, int C, void* workspace, size_t workspace_bytes, int act_dtype, int splits,
                          void* fin_scratch, size_t fin_scratch_bytes, void* stream);
+/* Backward through an EVAL-mode BatchNorm (+res -> ReLU): UPSTREAM ResNet(norm_eval=True) / ResNet._freeze_stages /
+ * ResNetTSM(partial_bn=True) put BatchNorms into .eval() inside a training step; the reference then differentiates
+ * F.batch_norm(training=False) through cuDNN.  With scale = gamma * invstd_running (bdv_bn_eval_params) the forward is
+ * a = relu?(y*scale + shift (+res)), and
+ *   dz = dout * sign,  dy = dz * scale,  dbeta = sum dz,  dgamma = sum dz * (y - running_mean) * invstd
+ * -- one pass: dy does not depend on the sums.  Nothing is ever divided by gamma or scale (gamma = 0 and gamma < 0 are legal).
+ * sign: relu_mask (the bits of bdv_bn_apply, C % 32 == 0), or relu_act (an activation tensor of the call's act_dtype: act > 0),
+ * or neither (no ReLU); at most one of the two.
+ * dz (optional): the masked gradient itself, for the identity path and the downsample BatchNorm of a block.
+ * dgamma / dbeta (optional, each): when one is given the pass also reads y and leaves per-row-block partial sums that the
+ * train-mode finalize reduces in fixed order in fp64 (run-to-run bit-identical; written as beta_acc*old + new); this needs y,
+ * running_mean, invstd and workspace = bdv_bn_workspace_bytes(M, C); splits / fin_scratch as above.  When both are NULL, y,
+ * running_mean, invstd, workspace and fin_scratch are not read: dy = dz * scale alone.
+ * act_dtype: element type of dout, relu_act, y, dy and dz.  dy, dz, dout and y must be distinct buffers. */
+int bdv_bn_eval_backward(const void* dout, const uint32_t* relu_mask, const void* relu_act, const void* y,
+                         const float* scale, const float* running_mean, const float* invstd, void* dy, void* dz,
+                         float* dgamma, float* dbeta, float beta_acc, int64_t M, int C, void* workspace,
+                         size_t workspace_bytes, int act_dtype, int splits, void* fin_scratch, size_t fin_scratch_bytes,
+                         void* stream);
 /* g = dout * relu_mask (+ add) : masked gradient for an identity path that has no conv behind it */
 int bdv_relu_bwd(const void* dout, const uint32_t* relu_mask, const void* add, void* g, int64_t numel, int act_dtype, void* stream);
 /* out = a + b (gradient junctions) */
