@@ -14,7 +14,7 @@ storage (``nhwc_to_nchw_view``), so hooks and feature-distillation see mmaction-
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -54,11 +54,6 @@ FUSE_BN_STATS = _os.environ.get('BDVCIL_FUSE_BN_STATS', '1') != '0'
 # pass of its own: conv1 -> conv2 and conv2 -> conv3 inside a block (the block output is read by two consumers and stays a pass).
 # The activation and its ReLU mask are then never written; the backward kernels derive the sign from the conv output.
 PRE_BN = _os.environ.get('BDVCIL_PRE_BN', '0') == '1'      # off: measured 0.6 ms per step SLOWER; saves ~2.8 GB
-# The forward half of it alone: the consumer conv applies the producer's BatchNorm + ReLU in its loader and starts right away, while
-# the apply pass that writes the activation and the mask for the BACKWARD pass runs beside it on the side stream (an HBM-bound pass
-# beside an MFMA-bound conv).  The backward pass is the default one.  BDVCIL_PRE_BN=fwd.
-PRE_BN_FWD = _os.environ.get('BDVCIL_PRE_BN', '0') == 'fwd'
-SAVED_PER_UNIT = 7      # y, activation | None, mean, invstd, mask | None, scale | None, shift | None
 # A whole stage as one autograd node (ResStageFn): lets the statistics fusion above reach the block outputs.
 FUSE_STAGE = _os.environ.get('BDVCIL_FUSE_STAGE', '1') != '0'
 # one split-K reduction launch per autograd node (stage / block) instead of one per conv
@@ -69,6 +64,17 @@ BATCH_WGRAD_REDUCE = _os.environ.get('BDVCIL_BATCH_WGRAD_REDUCE', '1') != '0'
 # (stem, then per block: unit 0, unit 1, ..., block output); the parity tests compare them with the CPU reference's signs.
 RELU_MASK_TAP = None
 POOL_IDX_TAP = None      # tests: the stem max-pool's arg-max codes (3 r + s per output element), same purpose
+
+
+def _tap_mask(shape, mask):
+    """Hand one ReLU's sign bits to RELU_MASK_TAP; ``mask`` may be a callable that produces them (run only while the tap is set)."""
+    if RELU_MASK_TAP is not None:
+        RELU_MASK_TAP.append((tuple(shape), mask() if callable(mask) else mask))
+
+
+def _tap_pool(idx):
+    if POOL_IDX_TAP is not None:
+        POOL_IDX_TAP.append(idx)
 
 
 def set_side_stream_enabled(flag: bool):
@@ -356,10 +362,8 @@ class StemFn(torch.autograd.Function):
             y, mean, invstd, scale, shift = _conv_bn_forward(x4, w4, g, bn, gamma, beta, training)
             # BN apply + ReLU + max-pool + ReLU sign mask in one pass; the activation itself is never materialised
             p, idx, mask = K.bn_relu_maxpool_fwd(y, scale, shift, out_dtype=K.ACT_DTYPE)
-            if RELU_MASK_TAP is not None:
-                RELU_MASK_TAP.append((tuple(y.shape), mask))
-            if POOL_IDX_TAP is not None:
-                POOL_IDX_TAP.append(idx)
+            _tap_mask(y.shape, mask)
+            _tap_pool(idx)
             if save:
                 ctx.save_for_backward(x4, gamma, y, mask, idx, mean, invstd)
         elif mode == 'affine':
@@ -367,20 +371,16 @@ class StemFn(torch.autograd.Function):
             y = K.conv_fprop(x4, w4, g)
             scale, shift = K.bn_eval_params(gamma, beta, bn.running_mean, bn.running_var, bn.eps)
             p, idx, mask = K.bn_relu_maxpool_fwd(y, scale, shift, out_dtype=K.ACT_DTYPE)
-            if RELU_MASK_TAP is not None:
-                RELU_MASK_TAP.append((tuple(y.shape), mask))
-            if POOL_IDX_TAP is not None:
-                POOL_IDX_TAP.append(idx)
+            _tap_mask(y.shape, mask)
+            _tap_pool(idx)
             ctx.save_for_backward(x4, scale, y, mask, idx, bn.running_mean, K.bn_eval_invstd(bn.running_var, bn.eps))
         else:
             scale, shift = K.bn_eval_params(gamma, beta, bn.running_mean, bn.running_var, bn.eps)
             a = K.conv_fprop(x4, w4, g, affine=(scale, shift, None, True))
             p, idx = K.maxpool_fwd(a, out_dtype=K.ACT_DTYPE)
             if mode == 'frozen':
-                if RELU_MASK_TAP is not None:
-                    RELU_MASK_TAP.append((tuple(a.shape), _sign_bits(a)))
-                if POOL_IDX_TAP is not None:
-                    POOL_IDX_TAP.append(idx)
+                _tap_mask(a.shape, lambda: _sign_bits(a))
+                _tap_pool(idx)
                 ctx.save_for_backward(x4, scale, a, idx)
         ctx.g = g
         ctx.bn_training = training
@@ -413,25 +413,112 @@ class StemFn(torch.autograd.Function):
         return None, dw, dgamma, dbeta, None, None, None
 
 
-def _block_forward(x, blk, training, params, save, need_params=None, eval_grad=False):
+class UnitParams(NamedTuple):
+    """(weight, gamma, beta) of one conv+BN unit; also: which of the three need a gradient, and their gradients."""
+    weight: object
+    gamma: object
+    beta: object
+
+
+def split_params(params) -> List[UnitParams]:
+    """Flat (weight, gamma, beta, weight, ...) as an autograd node receives it -> one record per unit."""
+    return [UnitParams(*params[k:k + 3]) for k in range(0, len(params), 3)]
+
+
+def split_need(needs, offset) -> List[UnitParams]:
+    """``needs_input_grad`` of a node whose parameters start at position ``offset`` of ``apply(...)`` -> one record per unit."""
+    return split_params(needs[offset:])
+
+
+def _flat(records) -> list:
+    return [t for r in records for t in r]
+
+
+class UnitSaved(NamedTuple):
+    """What the forward of one conv+BN(+ReLU) unit keeps for its backward: ``y`` the raw conv output, ``act`` the activation after
+    BatchNorm (+ residual) + ReLU, ``mask`` its 1-bit ReLU signs.  Fields set (others None), by the form the unit ran in:
+
+        train mode                      y  act  mean          invstd          mask
+        train mode, apply deferred      y       mean          invstd                scale  shift
+        eval mode, affine live          y  act  running_mean  of running_var  mask  scale
+        eval mode, affine frozen           act                                      scale
+        downsample, train mode          y       mean          invstd
+        downsample, eval mode, live     y       running_mean  of running_var        scale
+        downsample, eval mode, frozen                                               scale
+
+    Apply deferred (``PRE_BN``): the consumer conv applies this unit's BatchNorm + ReLU in its loaders; the backward kernels derive
+    the sign from ``y`` and (scale, shift).  Eval mode: BatchNorms on their running statistics inside a training step (UPSTREAM
+    norm_eval / partial_bn / frozen_stages, a user's .eval()), per unit by whether its gamma / beta need a gradient.  Live: conv ->
+    bn_apply with the eval scale / shift; backward = bn_eval_backward with dgamma / dbeta.  Frozen: the fused eval kernel (conv +
+    folded BatchNorm + residual + ReLU); only the activation is kept -- the operand of the next weight gradient anyway -- and the
+    backward reads the ReLU sign off it.  The downsample branch shares the block output's mask."""
+    y: Optional[torch.Tensor] = None
+    act: Optional[torch.Tensor] = None
+    mean: Optional[torch.Tensor] = None
+    invstd: Optional[torch.Tensor] = None
+    mask: Optional[torch.Tensor] = None
+    scale: Optional[torch.Tensor] = None
+    shift: Optional[torch.Tensor] = None
+    # train mode: (scale, shift) of a unit whose apply pass was deferred, else None
+    pre_bn = property(lambda self: (self.scale, self.shift) if self.scale is not None else None)
+
+    def bn_stat_operands(self):
+        """(y, mask, mean, invstd), the order ``K.conv_dgrad(bn_stats=...)`` documents: what a dgrad epilogue needs to take the
+        BatchNorm-backward statistics of the gradient it writes into this unit's output."""
+        return self.y, self.mask, self.mean, self.invstd
+
+
+class BlockSaved(NamedTuple):
+    """Saved tensors of one block: its input, one ``UnitSaved`` per main unit, one for a downsample branch; flat for autograd."""
+    x: torch.Tensor
+    units: Sequence[UnitSaved]
+    down: Optional[UnitSaved]
+
+    def flatten(self) -> list:
+        return [self.x] + _flat(self.units) + list(self.down or ())
+
+    @classmethod
+    def unflatten(cls, tensors, n_main, has_down):
+        q = len(UnitSaved._fields)
+        units = [UnitSaved(*tensors[1 + q * i:1 + q * (i + 1)]) for i in range(n_main + has_down)]
+        return cls(tensors[0], units[:n_main], units[n_main] if has_down else None)
+
+
+class BlockPlan(NamedTuple):
+    """What an autograd node remembers about one block besides tensors.  ``geoms``: one per unit, the downsample's last."""
+    geoms: list
+    n_main: int
+    has_down: bool
+    n_units = property(lambda self: self.n_main + self.has_down)
+    n_params = property(lambda self: len(UnitParams._fields) * self.n_units)
+    n_saved = property(lambda self: 1 + len(UnitSaved._fields) * self.n_units)      # = len(BlockSaved.flatten())
+
+
+def split_stage(plans, tensors, needs, offset):
+    """``tensors``: what a node over the blocks ``plans`` saved (every block's ``flatten()``, then every block's parameters);
+    ``needs``: its needs_input_grad.  -> per block (BlockSaved, [UnitParams], [UnitParams of needs])."""
+    units, need = split_params(tensors[sum(p.n_saved for p in plans):]), split_need(needs, offset)
+    out, s, u = [], 0, 0
+    for p in plans:
+        saved = BlockSaved.unflatten(tensors[s:s + p.n_saved], p.n_main, p.has_down)
+        out.append((saved, units[u:u + p.n_units], need[u:u + p.n_units]))
+        s, u = s + p.n_saved, u + p.n_units
+    return out
+
+
+def _block_forward(x, blk, training, params, save, need=None, eval_grad=False):
     """Forward of one residual block (UPSTREAM BasicBlock / Bottleneck, shift_place='blockres') on NHWC storage.
-    Returns (out, saved tensors for backward, geoms).  ``need_params``: which of ``params`` need a gradient (read by the
-    eval-mode form that is differentiated)."""
+    ``params``: one UnitParams per unit; ``need``: which of them need a gradient (read by the eval-mode form that is
+    differentiated).  Returns (out, BlockSaved for backward | None, BlockPlan)."""
     if eval_grad:
-        return _block_forward_eval_grad(x, blk, params, need_params)
-    units: List[UnitSpec] = blk.unit_specs
-    bns = blk.unit_bns
-    n_main = blk.n_main
+        return _block_forward_eval_grad(x, blk, params, need)
+    units, bns, n_main = blk.unit_specs, blk.unit_bns, blk.n_main
     has_down = len(units) > n_main
     N, H, W, _ = x.shape
-    saved = [x]
-    geoms = []
+    saved, geoms, down, ds_event = [], [], None, None
     # identity path
     if has_down:
-        u = units[n_main]
-        wd, gd, bd = params[3 * n_main:3 * n_main + 3]
-        g = u.geom(N, H, W)
-        ds_event = None
+        (wd, gd, bd), g = params[n_main], units[n_main].geom(N, H, W)
         if training:
             # the downsample BatchNorm is applied inside the block-output kernel (res_affine): no identity tensor
             if DS_SIDE and _SIDE['enabled'] and x.is_cuda:
@@ -441,17 +528,15 @@ def _block_forward(x, blk, training, params, save, need_params=None, eval_grad=F
             else:
                 yd, mean_d, invstd_d, sc_d, sh_d = _conv_bn_forward(x, weight_krsc(wd), g, bns[n_main], gd, bd, training)
             identity, id_affine = yd, (sc_d, sh_d)
+            down = UnitSaved(y=yd, mean=mean_d, invstd=invstd_d)
         else:
             identity, id_affine = _conv_bn_eval(x, weight_krsc(wd), g, bns[n_main], gd, bd, None, False), None
     else:
         identity, id_affine = x, None
-    cur = x
-    side_events = []        # apply passes running on the side stream (PRE_BN_FWD): joined before the block returns
+    cur, h, w_ = x, H, W
     pending = None          # (scale, shift) of the previous unit when `cur` is its raw conv output
-    h, w_ = H, W
     for i in range(n_main):
-        u = units[i]
-        wt, gm, bt = params[3 * i:3 * i + 3]
+        u, (wt, gm, bt) = units[i], params[i]
         g = u.geom(N, h, w_)
         geoms.append(g)
         last = i == n_main - 1
@@ -465,167 +550,112 @@ def _block_forward(x, blk, training, params, save, need_params=None, eval_grad=F
             torch.cuda.current_stream(x.device).wait_event(ds_event)      # the identity branch is needed from here on
         h2, w2 = u.out_hw(h, w_)
         # the next unit of the main branch can apply this unit's BatchNorm + ReLU in its own loaders: no apply pass here
-        can_pre = not last and (PRE_BN or PRE_BN_FWD) and K.fprop_pre_ok(units[i + 1].geom(N, h2, w2))
-        defer = can_pre and PRE_BN
-        if can_pre and not defer and save and _SIDE['enabled'] and y.is_cuda:
-            # forward-only form: the next conv reads the raw output; activation + mask for the backward pass come from the side stream
-            (a, mask), ev = run_on_side_stream(lambda: K.bn_apply(y, sc, sh, None, True, want_mask=True), y.device)
-            side = _side_stream(y.device)[1]
-            for t in (y, sc, sh):
-                t.record_stream(side)
-            main = torch.cuda.current_stream(y.device)
-            a.record_stream(main)
-            mask.record_stream(main)
-            side_events.append(ev)
-            saved += [y, a, mean, invstd, mask, None, None]
-            if RELU_MASK_TAP is not None:
-                RELU_MASK_TAP.append((tuple(y.shape), mask))
-            cur, pending = y, (sc, sh)
-        elif defer:
-            if RELU_MASK_TAP is not None:       # tests read every ReLU's sign bits: produce them on the side
-                RELU_MASK_TAP.append((tuple(y.shape), K.bn_apply(y, sc, sh, None, True, want_mask=True)[1]))
+        if not last and PRE_BN and K.fprop_pre_ok(units[i + 1].geom(N, h2, w2)):
+            # tests read every ReLU's sign bits: produce them on the side
+            _tap_mask(y.shape, lambda: K.bn_apply(y, sc, sh, None, True, want_mask=True)[1])
             if save:
-                saved += [y, None, mean, invstd, None, sc, sh]
+                saved.append(UnitSaved(y=y, mean=mean, invstd=invstd, scale=sc, shift=sh))
             cur, pending = y, (sc, sh)
         else:
             if save:
                 a, mask = K.bn_apply(y, sc, sh, identity if last else None, True, want_mask=True,
                                      res_affine=id_affine if last else None)
-                saved += [y, a, mean, invstd, mask, None, None]
-                if RELU_MASK_TAP is not None:
-                    RELU_MASK_TAP.append((tuple(y.shape), mask))
+                saved.append(UnitSaved(y, a, mean, invstd, mask))
+                _tap_mask(y.shape, mask)
             else:
                 a = K.bn_apply(y, sc, sh, identity if last else None, True, res_affine=id_affine if last else None)
             cur, pending = a, None
         h, w_ = h2, w2
-    for ev in side_events:  # (long finished by now: an apply pass is a tenth of the conv that ran beside it)
-        torch.cuda.current_stream(x.device).wait_event(ev)
     if save and has_down:
-        saved += [yd, mean_d, invstd_d]
         geoms.append(units[n_main].geom(N, H, W))
-    return cur, (saved if save else []), geoms
+    return cur, (BlockSaved(x, saved, down) if save else None), BlockPlan(geoms, n_main, has_down)
 
 
-def _block_out_stats(saved, n_main):
-    """(y, mask, mean, invstd) of a block's last main unit: what a dgrad epilogue needs to take the BatchNorm-backward
-    statistics of the gradient it writes into that block's output."""
-    k = n_main - 1
-    q = SAVED_PER_UNIT * k
-    return saved[1 + q], saved[5 + q], saved[3 + q], saved[4 + q]
-
-
-def _block_backward(saved, params, geoms, n_main, has_down, dout, need_params, need_dx, out_stat_partial=None,
-                    prev_stats=None):
+def _block_backward(saved, params, plan, dout, need, need_dx, out_stat_partial=None, prev_stats=None):
     """Backward of one residual block.  ``out_stat_partial``: tile sums of the BatchNorm-backward statistics of ``dout``
     against this block's last unit, when the producer of ``dout`` already took them.  ``prev_stats``: statistics
     operands of the PREVIOUS block's last unit; the dgrad that writes dx then reduces them in its epilogue.
-    Returns (dx, parameter gradients, partial for the previous block | None)."""
-    x = saved[0]
-    Q = SAVED_PER_UNIT
-    ys = [saved[1 + Q * i] for i in range(n_main)]
-    acts = [saved[2 + Q * i] for i in range(n_main)]
-    means = [saved[3 + Q * i] for i in range(n_main)]
-    invstds = [saved[4 + Q * i] for i in range(n_main)]
-    masks = [saved[5 + Q * i] for i in range(n_main)]
-    # units whose apply pass never ran (PRE_BN): (scale, shift) instead of an activation and a mask
-    affs = [(saved[6 + Q * i], saved[7 + Q * i]) if saved[6 + Q * i] is not None else None for i in range(n_main)]
-    out_mask = masks[-1]
+    Returns (dx, parameter gradients in the order of the node's ``*params``, partial for the previous block | None)."""
+    x, units, down = saved
+    geoms, n_main, k = plan.geoms, plan.n_main, plan.n_main - 1
+    out_mask = units[k].mask
     dout = dout if dout.is_contiguous() else dout.contiguous()
-    grads: List[Optional[torch.Tensor]] = [None] * len(params)
-
+    grads = [UnitParams(None, None, None)] * len(params)
     # main branch, last unit first.  ``d`` is the gradient w.r.t. the unit's (post-ReLU) output.
     d, part = dout, out_stat_partial
     # A downsample branch: the masked gradient dout * (out > 0) enters two BatchNorms, the last main unit's and the downsample's.
     # One pair call reads dout and the mask once per pass for both (plain mask form only: a unit whose sign is derived from y
     # keeps the two-call path).
     pair_down = None
-    if has_down and affs[n_main - 1] is None and out_mask is not None:
-        yd, mean_d, invstd_d = saved[1 + SAVED_PER_UNIT * n_main:4 + SAVED_PER_UNIT * n_main]
-        k = n_main - 1
-        pair_main, pair_down = K.bn_backward_pair(dout, out_mask, ys[k], params[3 * k + 1], means[k], invstds[k], yd,
-                                                  params[3 * n_main + 1], mean_d, invstd_d, stat_partial_a=part)
-    for i in range(n_main - 1, -1, -1):
-        wt, gm = params[3 * i], params[3 * i + 1]
+    if plan.has_down and units[k].pre_bn is None and out_mask is not None:
+        pair_main, pair_down = K.bn_backward_pair(dout, out_mask, units[k].y, params[k].gamma, units[k].mean, units[k].invstd, down.y,
+                                                  params[n_main].gamma, down.mean, down.invstd, stat_partial_a=part)
+    for i in range(k, -1, -1):
+        u, p, prev = units[i], params[i], units[i - 1] if i > 0 else None
         # this conv's input: the previous unit's activation, or its raw conv output + (scale, shift) for the loader
-        inp = (acts[i - 1] if affs[i - 1] is None else ys[i - 1]) if i > 0 else x
-        if i == n_main - 1 and pair_down is not None:
+        inp = x if prev is None else (prev.act if prev.pre_bn is None else prev.y)
+        pre_bn = prev.pre_bn if prev is not None else None
+        if i == k and pair_down is not None:
             dy, dg, db = pair_main
-            dw = wgrad_overlapped(dy, inp, geoms[i], pre_bn=affs[i - 1] if i > 0 else None) if need_params[3 * i] else None
+            dw = wgrad_overlapped(dy, inp, geoms[i], pre_bn=pre_bn) if need[i].weight else None
         else:
-            dy, dg, db, dw = _bn_wgrad_backward(d, masks[i], ys[i], gm, means[i], invstds[i], inp, geoms[i], need_params[3 * i],
-                                                stat_partial=part, relu_affine=affs[i], pre_bn=affs[i - 1] if i > 0 else None)
-        grads[3 * i + 1], grads[3 * i + 2] = dg, db
-        if dw is not None:
-            grads[3 * i] = grad_like_weight(dw, wt)
+            dy, dg, db, dw = _bn_wgrad_backward(d, u.mask, u.y, p.gamma, u.mean, u.invstd, inp, geoms[i], need[i].weight,
+                                                stat_partial=part, relu_affine=u.pre_bn, pre_bn=pre_bn)
+        grads[i] = UnitParams(grad_like_weight(dw, p.weight) if dw is not None else None, dg, db)
         part = None
         if i > 0:
             gi = geoms[i]
             if FUSE_BN_STATS and (gi.stride == 1 or (gi.R > 1 and gi.S > 1 and gi.fold == 0)):
                 # this dgrad produces the gradient entering unit i-1's BN+ReLU: take its statistics in the epilogue
                 # (stride 2: a 3x3 filter reaches every input pixel, one block of partial rows per parity class)
-                prev = (ys[i - 1], masks[i - 1], means[i - 1], invstds[i - 1])
-                d, part = K.conv_dgrad(dy, weight_krsc(wt), gi, bn_stats=prev if affs[i - 1] is None else prev + (affs[i - 1],))
+                stats = prev.bn_stat_operands()
+                d, part = K.conv_dgrad(dy, weight_krsc(p.weight), gi, bn_stats=stats if pre_bn is None else stats + (pre_bn,))
             else:
-                d = K.conv_dgrad(dy, weight_krsc(wt), gi)
+                d = K.conv_dgrad(dy, weight_krsc(p.weight), gi)
             d = d.view_as(inp)                     # frames view (the geometry of a temporal conv names another view)
         else:
             dy_first = dy
-
     dx, prev_partial = None, None
     stats = prev_stats if (FUSE_BN_STATS and prev_stats is not None and geoms[0].stride == 1) else None
-    if has_down:
-        yd, mean_d, invstd_d = saved[1 + SAVED_PER_UNIT * n_main:4 + SAVED_PER_UNIT * n_main]
-        wd, gd = params[3 * n_main], params[3 * n_main + 1]
-        gdn = geoms[n_main]
+    if plan.has_down:
+        (wd, gd, _), gdn, need_dwd = params[n_main], geoms[n_main], need[n_main].weight
         # gradient entering the downsample BN is dout * (out > 0): same mask as the block output
         if pair_down is not None:
             dyd, dgd, dbd = pair_down
-            dwd = wgrad_overlapped(dyd, x, gdn) if need_params[3 * n_main] else None
+            dwd = wgrad_overlapped(dyd, x, gdn) if need_dwd else None
         else:
-            dyd, dgd, dbd, dwd = _bn_wgrad_backward(dout, out_mask, yd, gd, mean_d, invstd_d, x, gdn, need_params[3 * n_main])
-        grads[3 * n_main + 1], grads[3 * n_main + 2] = dgd, dbd
-        if dwd is not None:
-            grads[3 * n_main] = grad_like_weight(dwd, wd)
+            dyd, dgd, dbd, dwd = _bn_wgrad_backward(dout, out_mask, down.y, gd, down.mean, down.invstd, x, gdn, need_dwd)
+        grads[n_main] = UnitParams(grad_like_weight(dwd, wd) if dwd is not None else None, dgd, dbd)
         if need_dx:
             dx_id = K.conv_dgrad(dyd, weight_krsc(wd), gdn)
-            dx = K.conv_dgrad(dy_first, weight_krsc(params[0]), geoms[0], add_src=dx_id, bn_stats=stats)
+            dx = K.conv_dgrad(dy_first, weight_krsc(params[0].weight), geoms[0], add_src=dx_id, bn_stats=stats)
     elif need_dx:
         # identity path: dout * (out > 0), fused into the conv1 dgrad epilogue
-        dx = K.conv_dgrad(dy_first, weight_krsc(params[0]), geoms[0], add_src=dout, add_mask_src=out_mask, bn_stats=stats)
+        dx = K.conv_dgrad(dy_first, weight_krsc(params[0].weight), geoms[0], add_src=dout, add_mask_src=out_mask, bn_stats=stats)
     if stats is not None and dx is not None:
         dx, prev_partial = dx
     if dx is not None:
         dx = dx.view_as(x)
-    return dx, grads, prev_partial
+    return dx, _flat(grads), prev_partial
 
 
-# ---- a block whose BatchNorms run on their running statistics inside a training step ---------------------------------------
-# (UPSTREAM ResNet(norm_eval=True), ResNetTSM(partial_bn=True), any BatchNorm a user put into .eval()).  Per conv+BN unit, by
-# whether its gamma / beta need a gradient:
-#   affine live:   conv (no statistics epilogue) -> bn_apply with the eval scale / shift, mask written; saved like a train-mode unit
-#                  with (running_mean, invstd of running_var) as the statistics; backward = bn_eval_backward with dgamma / dbeta
-#   affine frozen: the fused eval kernel (conv + folded BatchNorm + residual + ReLU); only the activation is kept -- the operand of
-#                  the next weight gradient anyway -- and the backward reads the ReLU sign off it: no raw conv output, no mask
-# Saved per unit (SAVED_PER_UNIT slots): y | None, activation, running_mean | None, invstd | None, mask | None, scale, None; a
-# downsample branch adds yd | None, running_mean | None, invstd | None, scale.
-def _block_forward_eval_grad(x, blk, params, need_params):
-    units: List[UnitSpec] = blk.unit_specs
-    bns = blk.unit_bns
-    n_main = blk.n_main
+def _block_forward_eval_grad(x, blk, params, need):
+    """Forward of a block whose BatchNorms run on their running statistics inside a training step, in the form that is
+    differentiated: per unit the live or the frozen form of the ``UnitSaved`` table, by whether its gamma / beta need a gradient."""
+    units, bns, n_main = blk.unit_specs, blk.unit_bns, blk.n_main
     has_down = len(units) > n_main
     N, H, W, _ = x.shape
 
     def live(i):
-        return bool(need_params[3 * i + 1] or need_params[3 * i + 2])
+        return bool(need[i].gamma or need[i].beta)
 
     def eval_affine(i):
-        return K.bn_eval_params(params[3 * i + 1], params[3 * i + 2], bns[i].running_mean, bns[i].running_var, bns[i].eps)
+        return K.bn_eval_params(params[i].gamma, params[i].beta, bns[i].running_mean, bns[i].running_var, bns[i].eps)
 
-    saved, geoms = [x], []
-    identity, id_affine, down_saved = x, None, None
+    saved, geoms = [], []
+    identity, id_affine, down = x, None, None
     if has_down:
-        wd = params[3 * n_main]
-        gdn = units[n_main].geom(N, H, W)
+        wd, gdn = params[n_main].weight, units[n_main].geom(N, H, W)
         sc_d, sh_d = eval_affine(n_main)
         if live(n_main):
             yd = K.conv_fprop(x, weight_krsc(wd), gdn)
@@ -633,10 +663,11 @@ def _block_forward_eval_grad(x, blk, params, need_params):
                 identity, id_affine = yd, (sc_d, sh_d)
             else:                       # the fused kernel of a frozen last unit takes a finished residual
                 identity = K.bn_apply(yd, sc_d, sh_d, None, False)
-            down_saved = [yd, bns[n_main].running_mean, K.bn_eval_invstd(bns[n_main].running_var, bns[n_main].eps), sc_d]
+            down = UnitSaved(y=yd, mean=bns[n_main].running_mean, invstd=K.bn_eval_invstd(bns[n_main].running_var, bns[n_main].eps),
+                             scale=sc_d)
         else:
             identity = K.conv_fprop(x, weight_krsc(wd), gdn, affine=(sc_d, sh_d, None, False))
-            down_saved = [None, None, None, sc_d]
+            down = UnitSaved(scale=sc_d)
     cur, h, w_ = x, H, W
     for i in range(n_main):
         u = units[i]
@@ -644,83 +675,74 @@ def _block_forward_eval_grad(x, blk, params, need_params):
         geoms.append(g)
         last = i == n_main - 1
         h2, w2 = u.out_hw(h, w_)
-        sc, sh = eval_affine(i)
+        w, (sc, sh) = weight_krsc(params[i].weight), eval_affine(i)
         if live(i):
-            y = K.conv_fprop(cur, weight_krsc(params[3 * i]), g).view(N, h2, w2, u.cout)
+            y = K.conv_fprop(cur, w, g).view(N, h2, w2, u.cout)
             a, mask = K.bn_apply(y, sc, sh, identity if last else None, True, want_mask=True, res_affine=id_affine if last else None)
-            saved += [y, a, bns[i].running_mean, K.bn_eval_invstd(bns[i].running_var, bns[i].eps), mask, sc, None]
-            if RELU_MASK_TAP is not None:
-                RELU_MASK_TAP.append((tuple(a.shape), mask))
+            saved.append(UnitSaved(y, a, bns[i].running_mean, K.bn_eval_invstd(bns[i].running_var, bns[i].eps), mask, sc))
+            _tap_mask(a.shape, mask)
         else:
-            a = K.conv_fprop(cur, weight_krsc(params[3 * i]), g, affine=(sc, sh, identity if last else None, True)).view(N, h2, w2, u.cout)
-            saved += [None, a, None, None, None, sc, None]
-            if RELU_MASK_TAP is not None:
-                RELU_MASK_TAP.append((tuple(a.shape), _sign_bits(a)))
+            a = K.conv_fprop(cur, w, g, affine=(sc, sh, identity if last else None, True)).view(N, h2, w2, u.cout)
+            saved.append(UnitSaved(act=a, scale=sc))
+            _tap_mask(a.shape, lambda: _sign_bits(a))
         cur, h, w_ = a, h2, w2
     if has_down:
-        saved += down_saved
         geoms.append(gdn)
-    return cur, saved, geoms
+    return cur, BlockSaved(x, saved, down), BlockPlan(geoms, n_main, has_down)
 
 
-def _block_backward_eval(saved, params, geoms, n_main, has_down, dout, need_params, need_dx):
+def _block_backward_eval(saved, params, plan, dout, need, need_dx):
     """Backward of ``_block_forward_eval_grad``: one bn_eval_backward pass per unit (no statistics hand-over between kernels:
     dy does not depend on the sums).  Returns (dx, parameter gradients, None)."""
-    x = saved[0]
-    Q = SAVED_PER_UNIT
-    ys = [saved[1 + Q * i] for i in range(n_main)]
-    acts = [saved[2 + Q * i] for i in range(n_main)]
-    means = [saved[3 + Q * i] for i in range(n_main)]
-    invstds = [saved[4 + Q * i] for i in range(n_main)]
-    masks = [saved[5 + Q * i] for i in range(n_main)]
-    scales = [saved[6 + Q * i] for i in range(n_main)]
+    x, units, down = saved
+    geoms, n_main, k = plan.geoms, plan.n_main, plan.n_main - 1
+    out_mask = units[k].mask
     dout = dout if dout.is_contiguous() else dout.contiguous()
-    grads: List[Optional[torch.Tensor]] = [None] * len(params)
-    k = n_main - 1
+    grads = [UnitParams(None, None, None)] * len(params)
     d, dz_out, dy_first = dout, None, None
     for i in range(k, -1, -1):
-        wt = params[3 * i]
-        inp = acts[i - 1] if i > 0 else x
+        u, wt = units[i], params[i].weight
+        inp = units[i - 1].act if i > 0 else x
         # the masked gradient of the block output also enters the downsample BatchNorm, or -- without one -- the identity path,
         # which re-derives it from (dout, mask) in the conv1 dgrad epilogue where a mask exists
-        want_dz = i == k and (has_down or (need_dx and masks[k] is None))
-        if ys[i] is not None:
-            dy, dz, grads[3 * i + 1], grads[3 * i + 2] = K.bn_eval_backward(
-                d, scales[i], relu_mask=masks[i], y=ys[i], running_mean=means[i], invstd=invstds[i], want_params=True, want_dz=want_dz)
-        else:
-            dy, dz, _, _ = K.bn_eval_backward(d, scales[i], relu_act=acts[i], want_dz=want_dz)
+        want_dz = i == k and (plan.has_down or (need_dx and out_mask is None))
+        if u.y is not None:            # affine live
+            dy, dz, dg, db = K.bn_eval_backward(d, u.scale, relu_mask=u.mask, y=u.y, running_mean=u.mean, invstd=u.invstd,
+                                                want_params=True, want_dz=want_dz)
+        else:                          # affine frozen: the sign off the activation, no parameter gradients (dg = db = None)
+            dy, dz, dg, db = K.bn_eval_backward(d, u.scale, relu_act=u.act, want_dz=want_dz)
         if i == k:
             dz_out = dz
-        if need_params[3 * i]:
-            grads[3 * i] = grad_like_weight(wgrad_overlapped(dy, inp, geoms[i]), wt)
+        dw = grad_like_weight(wgrad_overlapped(dy, inp, geoms[i]), wt) if need[i].weight else None
+        grads[i] = UnitParams(dw, dg, db)
         if i == 0:
             dy_first = dy
-        elif need_dx or any(need_params[:3 * i]):
+        elif need_dx or any(any(n) for n in need[:i]):
             d = K.conv_dgrad(dy, weight_krsc(wt), geoms[i]).view_as(inp)
         else:
             break                      # nothing below this unit needs a gradient
     dx = None
-    if has_down:
-        yd, mean_d, invstd_d, sc_d = saved[1 + Q * n_main:5 + Q * n_main]
-        wd, gdn = params[3 * n_main], geoms[n_main]
-        if yd is not None:
-            dyd, _, grads[3 * n_main + 1], grads[3 * n_main + 2] = K.bn_eval_backward(
-                dz_out, sc_d, y=yd, running_mean=mean_d, invstd=invstd_d, want_params=True)
-        elif need_params[3 * n_main] or need_dx:
-            dyd = K.bn_eval_backward(dz_out, sc_d)[0]
-        if need_params[3 * n_main]:
-            grads[3 * n_main] = grad_like_weight(wgrad_overlapped(dyd, x, gdn), wd)
+    if plan.has_down:
+        wd, gdn = params[n_main].weight, geoms[n_main]
+        dgd = dbd = None
+        if down.y is not None:
+            dyd, _, dgd, dbd = K.bn_eval_backward(dz_out, down.scale, y=down.y, running_mean=down.mean, invstd=down.invstd,
+                                                  want_params=True)
+        elif need[n_main].weight or need_dx:
+            dyd = K.bn_eval_backward(dz_out, down.scale)[0]
+        dwd = grad_like_weight(wgrad_overlapped(dyd, x, gdn), wd) if need[n_main].weight else None
+        grads[n_main] = UnitParams(dwd, dgd, dbd)
         if need_dx:
             dx_id = K.conv_dgrad(dyd, weight_krsc(wd), gdn)
-            dx = K.conv_dgrad(dy_first, weight_krsc(params[0]), geoms[0], add_src=dx_id)
+            dx = K.conv_dgrad(dy_first, weight_krsc(params[0].weight), geoms[0], add_src=dx_id)
     elif need_dx:
-        if masks[k] is not None:
-            dx = K.conv_dgrad(dy_first, weight_krsc(params[0]), geoms[0], add_src=dout, add_mask_src=masks[k])
+        if out_mask is not None:
+            dx = K.conv_dgrad(dy_first, weight_krsc(params[0].weight), geoms[0], add_src=dout, add_mask_src=out_mask)
         else:
-            dx = K.conv_dgrad(dy_first, weight_krsc(params[0]), geoms[0], add_src=dz_out)
+            dx = K.conv_dgrad(dy_first, weight_krsc(params[0].weight), geoms[0], add_src=dz_out)
     if dx is not None:
         dx = dx.view_as(x)
-    return dx, grads, None
+    return dx, _flat(grads), None
 
 
 class ResBlockFn(torch.autograd.Function):
@@ -729,13 +751,11 @@ class ResBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, blk, training, grad, *params):
         save, eval_grad = save_plan(ctx.needs_input_grad, training, grad)
-        out, saved, geoms = _block_forward(x, blk, training, params, save, ctx.needs_input_grad[4:], eval_grad)
+        first = len(ctx.needs_input_grad) - len(params)
+        out, saved, ctx.plan = _block_forward(x, blk, training, split_params(params), save, split_need(ctx.needs_input_grad, first),
+                                              eval_grad)
         if save:
-            ctx.save_for_backward(*saved, *params)
-            ctx.n_saved = len(saved)
-        ctx.geoms = geoms
-        ctx.n_main = blk.n_main
-        ctx.has_down = len(blk.unit_specs) > blk.n_main
+            ctx.save_for_backward(*saved.flatten(), *params)
         ctx.bn_training = training
         ctx.eval_grad = eval_grad
         return out
@@ -743,15 +763,15 @@ class ResBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         require_eval_backward(ctx)
-        t = ctx.saved_tensors
-        saved, params = t[:ctx.n_saved], t[ctx.n_saved:]
-        need = ctx.needs_input_grad      # (x, blk, training, grad, *params)
+        need = ctx.needs_input_grad
+        first = len(need) - ctx.plan.n_params        # (x, blk, training, grad, *params)
+        (saved, params, need_params), = split_stage([ctx.plan], ctx.saved_tensors, need, first)
         backward = _block_backward if ctx.bn_training else _block_backward_eval
         with wgrad_batch():
-            dx, grads, _ = backward(saved, params, ctx.geoms, ctx.n_main, ctx.has_down, dout, need[4:], need[0])
+            dx, grads, _ = backward(saved, params, ctx.plan, dout, need_params, need[0])
         if not need[0]:
             join_side_stream(dout.device)    # nothing below needs a gradient (frozen stem / stages): the last backward node
-        return (dx, None, None, None, *grads)
+        return (dx, *[None] * (first - 1), *grads)
 
 
 class StageLink:
@@ -779,28 +799,26 @@ class ResStageFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, blocks, training, in_link, out_link, grad, *params):
         save, eval_grad = save_plan(ctx.needs_input_grad, training, grad)
-        cur, off = x, 0
-        all_saved, meta = [], []
+        first = len(ctx.needs_input_grad) - len(params)
+        units, need = split_params(params), split_need(ctx.needs_input_grad, first)
+        cur, all_saved, plans = x, [], []
         for blk in blocks:
-            npar = 3 * len(blk.unit_specs)
-            out, saved, geoms = _block_forward(cur, blk, training, params[off:off + npar], save,
-                                               ctx.needs_input_grad[6 + off:6 + off + npar], eval_grad)
-            meta.append((len(saved), npar, geoms, blk.n_main, len(blk.unit_specs) > blk.n_main))
-            all_saved += saved
-            off += npar
-            cur = out
+            u, n = sum(p.n_units for p in plans), len(blk.unit_bns)
+            cur, saved, plan = _block_forward(cur, blk, training, units[u:u + n], save, need[u:u + n], eval_grad)
+            all_saved.append(saved)
+            plans.append(plan)
         # the previous stage's last unit: operands for the statistics this stage's first conv1 dgrad can take for it
         # (train mode only: an eval-mode BatchNorm's backward has no statistics to hand over)
         in_stats = in_link.stats if (save and training and in_link is not None and CROSS_STAGE_STATS and FUSE_BN_STATS) else None
-        if in_stats is not None and not (meta[0][2][0].stride == 1 and ctx.needs_input_grad[0]):
+        if in_stats is not None and not (plans[0].geoms[0].stride == 1 and ctx.needs_input_grad[0]):
             in_stats = None
         if save:
-            ctx.save_for_backward(*all_saved, *params, *(in_stats or ()))
+            ctx.save_for_backward(*[t for s in all_saved for t in s.flatten()], *params, *(in_stats or ()))
             if out_link is not None and training:
-                out_link.stats = _block_out_stats(all_saved[len(all_saved) - meta[-1][0]:], meta[-1][3])
+                out_link.stats = all_saved[-1].units[-1].bn_stat_operands()
         ctx.in_link = in_link if in_stats is not None else None
         ctx.out_link = out_link if (save and training) else None
-        ctx.meta = meta
+        ctx.plans = plans
         ctx.bn_training = training
         ctx.eval_grad = eval_grad
         return cur
@@ -808,50 +826,34 @@ class ResStageFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         require_eval_backward(ctx)
-        t = ctx.saved_tensors
-        meta = ctx.meta
-        n_saved_total = sum(m[0] for m in meta)
-        in_stats = None
+        t, in_stats = ctx.saved_tensors, None
         if ctx.in_link is not None:
             t, in_stats = t[:-4], tuple(t[-4:])
-        saved_all, params_all = t[:n_saved_total], t[n_saved_total:]
-        need = ctx.needs_input_grad      # (x, blocks, training, in_link, out_link, grad, *params)
-        s_off = [0]
-        p_off = [0]
-        for m in meta:
-            s_off.append(s_off[-1] + m[0])
-            p_off.append(p_off[-1] + m[1])
-        grads_all: List[Optional[torch.Tensor]] = [None] * len(params_all)
+        need = ctx.needs_input_grad
+        first = len(need) - sum(p.n_params for p in ctx.plans)     # (x, blocks, training, in_link, out_link, grad, *params)
+        blocks = split_stage(ctx.plans, t, need, first)
+        grads_all = [[None] * p.n_params for p in ctx.plans]
         d, part = dout, None
         if ctx.out_link is not None:     # the next stage's backward ran before this one and took the statistics of `dout`
             part, ctx.out_link.partial = ctx.out_link.partial, None
         with wgrad_batch():              # one split-K reduction launch for the weight gradients of the whole stage
-            for k in range(len(meta) - 1, -1, -1):
-                n_saved, npar, geoms, n_main, has_down = meta[k]
-                saved = saved_all[s_off[k]:s_off[k + 1]]
-                params = params_all[p_off[k]:p_off[k + 1]]
+            for k in range(len(blocks) - 1, -1, -1):
+                saved, params, need_params = blocks[k]
                 if not ctx.bn_training:
                     # a block's dx feeds the blocks below it: not needed once nothing below needs a gradient
-                    need_dx = need[0] or any(need[6:6 + p_off[k]])
-                    d, grads, part = _block_backward_eval(saved, params, geoms, n_main, has_down, d,
-                                                          need[6 + p_off[k]:6 + p_off[k + 1]], need_dx)
-                    grads_all[p_off[k]:p_off[k + 1]] = grads
+                    need_dx = need[0] or any(any(n) for _, _, below in blocks[:k] for n in below)
+                    d, grads_all[k], part = _block_backward_eval(saved, params, ctx.plans[k], d, need_params, need_dx)
                     if d is None:
                         break
                     continue
-                prev_stats = in_stats if k == 0 else None
-                if k > 0:
-                    pm = meta[k - 1]
-                    prev_stats = _block_out_stats(saved_all[s_off[k - 1]:s_off[k]], pm[3])
-                need_dx = need[0] or k > 0
-                d, grads, part = _block_backward(saved, params, geoms, n_main, has_down, d, need[6 + p_off[k]:6 + p_off[k + 1]],
-                                                 need_dx, out_stat_partial=part, prev_stats=prev_stats)
-                grads_all[p_off[k]:p_off[k + 1]] = grads
+                prev_stats = blocks[k - 1][0].units[-1].bn_stat_operands() if k > 0 else in_stats
+                d, grads_all[k], part = _block_backward(saved, params, ctx.plans[k], d, need_params, need[0] or k > 0,
+                                                        out_stat_partial=part, prev_stats=prev_stats)
         if ctx.in_link is not None:
             ctx.in_link.partial = part   # tile sums of the statistics of `d` against the previous stage's last unit
         if not need[0]:
             join_side_stream(dout.device)    # nothing below needs a gradient (frozen stem / stages): the last backward node
-        return (d, None, None, None, None, None, *grads_all)
+        return (d, *[None] * (first - 1), *_flat(grads_all))
 
 
 class AvgPoolFn(torch.autograd.Function):

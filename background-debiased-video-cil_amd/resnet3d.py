@@ -143,16 +143,15 @@ class _Stem3dFn(torch.autograd.Function):
             a, mask = K.bn_apply(y, scale, shift, None, True, want_mask=True)
         else:
             a, mask = K.bn_apply(y, scale, shift, None, True), None
-            if mode == 'frozen' and Fn.RELU_MASK_TAP is not None:
-                Fn.RELU_MASK_TAP.append((tuple(y.shape), Fn._sign_bits(a)))
+            if mode == 'frozen':
+                Fn._tap_mask(y.shape, lambda: Fn._sign_bits(a))
         # pool1: temporal kernel 1, stride 2 -> the even frames; spatial 3x3 / 2
         Tp = (To - 1) // 2 + 1
         even = a.view(B, To, g.Ho, g.Wo, Cout)[:, ::2].contiguous().view(B * Tp, g.Ho, g.Wo, Cout)
         p, pidx = K.maxpool_fwd(even)
-        if Fn.RELU_MASK_TAP is not None and mask is not None:      # tests: the stem's ReLU sign bits / pool1's arg-max codes
-            Fn.RELU_MASK_TAP.append((tuple(y.shape), mask))
-        if Fn.POOL_IDX_TAP is not None:
-            Fn.POOL_IDX_TAP.append(pidx)
+        if mask is not None:                                        # tests: the stem's ReLU sign bits / pool1's arg-max codes
+            Fn._tap_mask(y.shape, mask)
+        Fn._tap_pool(pidx)
         ctx.meta = (g, B, To, Tp, kt, fused)
         ctx.bn_training = training
         ctx.eval_mode = mode
@@ -201,8 +200,7 @@ class _PoolT2Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         out, sel = K.maxpool_t2_fwd(x.contiguous())
-        if Fn.POOL_IDX_TAP is not None:                             # tests: which frame of each pair pool2 took
-            Fn.POOL_IDX_TAP.append(sel)
+        Fn._tap_pool(sel)                                           # tests: which frame of each pair pool2 took
         ctx.save_for_backward(sel)
         return out
 

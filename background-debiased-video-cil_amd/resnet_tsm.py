@@ -132,13 +132,14 @@ class _ResBlock(nn.Module):
     def unit_bns(self):
         return [m.bn for m in self.unit_modules]
 
+    def unit_params(self):
+        """(weight, gamma, beta) of every unit, flat: the trailing arguments of the autograd nodes."""
+        return [p for m in self.unit_modules for p in (m.raw_conv.weight, m.bn.weight, m.bn.bias)]
+
     def forward(self, x):
         """x: NCHW view over NHWC storage (or any NCHW tensor; converted once)."""
         xh = Fn.nchw_view_to_nhwc(x)
-        params = []
-        for m in self.unit_modules:
-            params += [m.raw_conv.weight, m.bn.weight, m.bn.bias]
-        out = Fn.ResBlockFn.apply(xh, self, self.bn_training(), torch.is_grad_enabled(), *params)
+        out = Fn.ResBlockFn.apply(xh, self, self.bn_training(), torch.is_grad_enabled(), *self.unit_params())
         return Fn.nhwc_to_nchw_view(out)
 
     def bn_training(self) -> bool:
@@ -178,10 +179,7 @@ class ResStage(nn.Sequential):
             return super().forward(x)
         xh = Fn.nchw_view_to_nhwc(x)
         blocks = list(self)
-        params = []
-        for b in blocks:
-            for m in b.unit_modules:
-                params += [m.raw_conv.weight, m.bn.weight, m.bn.bias]
+        params = [p for b in blocks for p in b.unit_params()]
         flags = {b.bn_training() for b in blocks}       # every unit of every block (a mixed block raises)
         if len(flags) != 1:
             return super().forward(x)

@@ -63,8 +63,9 @@ def _hip_model(ref, cfg, opts, dev):
 _ORACLE = {}
 
 
-def _oracle_step(depth, mode):
-    """fp32 and fp64 CPU steps of one (depth, mode): run once, shared by the conv arithmetics, never modified afterwards."""
+def _oracle_step(depth, mode, opts, freeze=None):
+    """fp32 and fp64 CPU steps of one (depth, mode): run once, shared by the conv arithmetics, never modified afterwards.
+    ``freeze``: applied to each oracle's backbone after the mode is set."""
     key = (depth, mode)
     if key not in _ORACLE:
         ref, cfg = _oracle_only(depth, 'SimpleLinear', 'CrossEntropyLoss', K=K_, want_cfg=True)
@@ -72,7 +73,9 @@ def _oracle_step(depth, mode):
         ref64 = copy.deepcopy(ref).double()
         imgs, labels = _clips(2, 8, 64, K_, seed=5)
         for m in (ref, ref64):
-            _set_oracle_mode(m, **MODES[mode])
+            _set_oracle_mode(m, **opts)
+            if freeze is not None:
+                freeze(m.backbone)
         with ReluRecorder() as rec32:
             rl = ref(imgs, labels)
         rl['loss_cls'].backward()
@@ -87,11 +90,19 @@ def _oracle_step(depth, mode):
 @pytest.mark.parametrize('mode', list(MODES))
 @pytest.mark.parametrize('depth', [18, 50])
 def test_train_step_through_eval_batchnorm(depth, mode, dev, conv_arith):
+    _check_train_step(depth, mode, MODES[mode], dev, conv_arith)
+
+
+def _check_train_step(depth, mode, opts, dev, conv_arith, freeze=None):
+    """One training step of the HIP model under the backbone options ``opts`` against the oracle's, by the rule in this file's
+    docstring.  ``freeze``: applied to every backbone (both oracles, the model) after ``train()``.  Returns (model, oracle step)."""
     from bdvcil_amd import functional as Fn
-    o = _oracle_step(depth, mode)
-    ref, ref64, opts = o['ref'], o['ref64'], MODES[mode]
+    o = _oracle_step(depth, mode, opts, freeze)
+    ref, ref64 = o['ref'], o['ref64']
     mod = _hip_model(_StateOnly(o['state']), o['cfg'], opts, dev)
     mod.train()
+    if freeze is not None:
+        freeze(mod.backbone)
     eval_bns = {n for n, m in mod.named_modules() if isinstance(m, torch.nn.BatchNorm2d) and not m.training}
     ref_eval = {n for n, m in ref.named_modules() if isinstance(m, torch.nn.BatchNorm2d) and not m.training}
     assert eval_bns == ref_eval and eval_bns
@@ -156,6 +167,48 @@ def test_train_step_through_eval_batchnorm(depth, mode, dev, conv_arith):
             assert int(ob[name].item()) == int(b.item()) == 1, name
         else:
             assert _rel(ob[name], b) <= 1e-4, name
+    return mod, o
+
+
+def _freeze_mixed(backbone):
+    """Live and frozen BatchNorm affines side by side inside the blocks of a TSM-R50.  Units (conv1, conv2, conv3) by block:
+    layer1 / layer2 / layer4 live-live-live in the even blocks and live-frozen-live in the odd ones, layer3 frozen-live-live and
+    frozen-frozen-live; conv3 frozen in layer2.0 and layer4.0, the downsample in layer3.0 and layer4.0, so that the four
+    downsample blocks cover the four (last unit, downsample) combinations.  Every block without a downsample branch ends in a
+    live unit: the all-frozen ending without one is ``partial_bn``'s."""
+    frozen = []
+    for li in range(1, 5):
+        for bi, blk in enumerate(getattr(backbone, f'layer{li}')):
+            frozen += [blk.conv2.bn] if bi % 2 else []
+            frozen += [blk.conv1.bn] if li == 3 else []
+            frozen += [blk.conv3.bn] if bi == 0 and li in (2, 4) else []
+            frozen += [blk.downsample.bn] if bi == 0 and li in (3, 4) else []
+    for bn in frozen:
+        bn.weight.requires_grad = False
+        bn.bias.requires_grad = False
+
+
+def test_train_step_with_mixed_affine_units(dev, conv_arith):
+    """``norm_eval`` with some BatchNorm affines frozen inside a block (``_freeze_mixed``): the gradient rule, ``grad is None``
+    for the frozen tensors and the untouched buffers of ``test_train_step_through_eval_batchnorm``; then the stage nodes and
+    the block nodes give the same bits."""
+    from bdvcil_amd import functional as Fn
+    mod, o = _check_train_step(50, 'mixed', dict(norm_eval=True), dev, conv_arith, freeze=_freeze_mixed)
+    bb = mod.backbone
+    live = lambda bn: bn.weight.requires_grad and bn.bias.requires_grad      # noqa: E731
+    assert [(live(getattr(bb, f'layer{li}')[0].conv3.bn), live(getattr(bb, f'layer{li}')[0].downsample.bn)) for li in range(1, 5)] \
+        == [(True, True), (False, True), (True, False), (False, False)]
+    assert Fn.FUSE_STAGE
+    l1, g1 = _grad_step(mod, o['imgs'], o['labels'], dev)
+    Fn.FUSE_STAGE = False
+    try:
+        l2, g2 = _grad_step(mod, o['imgs'], o['labels'], dev)
+    finally:
+        Fn.FUSE_STAGE = True
+    assert torch.equal(l1, l2)
+    assert g1.keys() == g2.keys() == {n for n, p in mod.named_parameters() if p.requires_grad}
+    for n in g1:
+        assert torch.equal(g1[n], g2[n]), f'{n}: stage node and block nodes differ'
 
 
 class _StateOnly:

@@ -41,8 +41,7 @@ def run(cfg, n):
     CS._MAIN_HIGH_PRIORITY = cfg['prio']
     Fn.BATCH_WGRAD_REDUCE = cfg['batch']
     os.environ['BDVCIL_BN_NT'] = str(cfg.get('nt', 2))
-    Fn.PRE_BN = cfg.get('pre', False) is True
-    Fn.PRE_BN_FWD = cfg.get('pre', False) == 'fwd'
+    Fn.PRE_BN = cfg.get('pre', False)
     Fn.CROSS_STAGE_STATS = cfg.get('xs', True)
     K.PRE_BN_1X1_ONLY = not cfg.get('k3', False)
     Fn.PRE_BN_WGRAD = cfg.get('wg', 'recompute')
