@@ -17,6 +17,7 @@ Import as ``bdvcil_amd`` (see ``bdvcil_amd.py`` at the repo root).  Layout:
 * ``representation``  predict_step / NME classifier / class means / herding
 * ``resnet3d``     I3D-ResNet50 (ResNet3d / I3DHead / Recognizer3D) on the same kernels (temporal convs as k x 1 convs)
 * ``task_loop``    the CIL task loop (CILTrainer + CILDataModule bookkeeping, same files on disk)
+* ``config_run``   a reference config file -> the clip loader that computes its pipelines (``tools/train_cil.py`` runs one)
 """
 import os as _os
 
@@ -52,7 +53,7 @@ from .hooks import OutputHook, rgetattr  # noqa: F401
 from .optim import (CILTSMOptimizerConstructor, CILTSMOptimizerConstructorImprovised, FusedSGD, build_lr_scheduler,  # noqa: F401
                     build_optimizer)
 from .frontend import BackgroundCropFrontEnd, BackgroundMixFrontEnd, CropFrontEnd, MultiScaleCropResize, TrainClipFrontEnd, crop_offsets  # noqa: F401
-from .decode import JpegDecoder, PrefetchLoader, RawFrameClipLoader, sample_frames  # noqa: F401
+from .decode import Draws, JpegDecoder, PrefetchLoader, RawFrameClipLoader, sample_frames  # noqa: F401
 from .actor_cut_mix import ActorCutMixClipLoader  # noqa: F401
 from .augment import RandAugment  # noqa: F401
 from .background import encode_jpeg, extract_background, resolve_bg_files, temporal_median  # noqa: F401
@@ -60,6 +61,7 @@ from .cil_step import (TrainEngine, base_training_step, icarl_training_step, ica
                        tubemix_draw)
 from .ddp import GradAllReducer, broadcast_parameters  # noqa: F401
 from .representation import Herding, ReprPredictor, class_means_from_repr, nme_classify  # noqa: F401
-from .task_loop import CILTaskLoop, CILWorkDir, RawframeRecords, SyntheticClipLoader, TaskSplits  # noqa: F401
+from .task_loop import AttrDict, CILTaskLoop, CILWorkDir, RawframeRecords, SyntheticClipLoader, TaskSplits  # noqa: F401
+from .config_run import build_clip_loader, clip_loader_spec, load_config  # noqa: F401
 
 __version__ = '0.1.0'

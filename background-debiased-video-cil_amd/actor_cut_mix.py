@@ -16,7 +16,6 @@ INTER_LINEAR, see include/bdvcil_hip.h) is unpinned, as for ``RawFrameClipLoader
 from __future__ import annotations
 
 import os.path as osp
-import random
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -129,11 +128,11 @@ class ActorCutMixClipLoader(RawFrameClipLoader):
 
     def __init__(self, det_file: str, acm_prob: float = 0.5, device='cuda', filename_tmpl: str = 'img_{:05}.jpg', num_segments: int = 8,
                  start_index: int = 1, short_edge: int = 256, input_size: int = 224, randAug=None, multi_scale_crop: dict = None,
-                 test_crop=('TenCrop', 256), threads: int = 8, det_thres: float = 0.4, flip_ratio: float = 0.5):
+                 test_crop=('TenCrop', 256), threads: int = 8, det_thres: float = 0.4, flip_ratio: float = 0.5, seed=None):
         from .augment import RandAugment
         super().__init__(device, filename_tmpl=filename_tmpl, num_segments=num_segments, start_index=start_index, short_edge=short_edge,
                          input_size=input_size, randAug=randAug if randAug is not None else RandAugment(2, 10, 1.0),
-                         multi_scale_crop=multi_scale_crop, test_crop=test_crop, threads=threads)
+                         multi_scale_crop=multi_scale_crop, test_crop=test_crop, threads=threads, seed=seed)
         self.det_file = str(det_file)
         self.detections = load_detections(self.det_file)
         self.acm_prob, self.det_thres, self.flip_ratio = float(acm_prob), float(det_thres), float(flip_ratio)
@@ -175,17 +174,18 @@ class ActorCutMixClipLoader(RawFrameClipLoader):
         H, W = frame_hw
         pool = self.scene_infos if self.scene_infos else list(video_infos)
         rows = []
+        random, np_random, d = self.draws.py, self.draws.np, self.draws
         for v in video_infos:
             total = int(v['total_frames'])
             if random.random() < self.acm_prob:
-                inds = sample_frames(total, self.T, start_index=self.start_index)
-                flip = bool(np.random.rand() < self.flip_ratio)
+                inds = sample_frames(total, self.T, start_index=self.start_index, draws=d)
+                flip = bool(np_random.rand() < self.flip_ratio)
                 si = random.randrange(len(pool))
-                sinds = sample_frames(int(pool[si]['total_frames']), self.T, start_index=self.start_index)
-                sflip = bool(np.random.rand() < self.flip_ratio)
+                sinds = sample_frames(int(pool[si]['total_frames']), self.T, start_index=self.start_index, draws=d)
+                sflip = bool(np_random.rand() < self.flip_ratio)
                 rows.append(AcmDraw(True, inds, flip, si, sinds, sflip))
             else:
-                inds = sample_frames(total, self.T, start_index=self.start_index)
+                inds = sample_frames(total, self.T, start_index=self.start_index, draws=d)
                 ra = self.train_front.randaug.draw(H, W)
                 crop = self.train_front.crop_resize.draw(W, H)
                 rows.append(AcmDraw(False, inds, randaug=ra, crop=crop))

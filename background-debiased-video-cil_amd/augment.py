@@ -11,7 +11,6 @@ in Python too, with the same expressions.
 from __future__ import annotations
 
 import math
-import random
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -117,18 +116,21 @@ class RandAugment:
     """``RandAugment(n, m, prob)`` of the reference for a batch: ``__call__(frames_u8 (B,T,H,W,3) cuda uint8)`` returns
     ``(augmented frames, randAug (B,) bool)``.  Sample b draws exactly what the reference's b-th ``__call__`` would."""
 
-    def __init__(self, n: int, m: int, prob: float = 0.5):
+    def __init__(self, n: int, m: int, prob: float = 0.5, draws=None):
+        from .decode import Draws
         self.n, self.m, self.prob = n, m, prob
+        self.draws = Draws.of(draws)         # ``draws``: a ``decode.Draws`` bundle or a seed; None = the global ``random`` / ``np.random``
         self.augment_list = augment_list()
 
     def draw(self, H: int, W: int):
         """The random decisions of one sample in the reference's order (rand_augment.py:230-245); None = not augmented."""
+        random, np_random = self.draws.py, self.draws.np
         if not (random.random() < self.prob):
             return None
         ops = random.choices(self.augment_list, k=self.n)
         flip_sign = random.random() > 0.5
-        x0 = np.random.uniform(W)                # sic: low = W, high = 1.0 (rand_augment.py:242-243)
-        y0 = np.random.uniform(H)
+        x0 = np_random.uniform(W)                # sic: low = W, high = 1.0 (rand_augment.py:242-243)
+        y0 = np_random.uniform(H)
         return ops, flip_sign, (x0, y0)
 
     def rows(self, draws, H: int, W: int):

@@ -118,6 +118,7 @@ class GradAllReducer:
         self._comm_stream = None
         self.timing = False         # bench.py: HIP events around the waits of finish() -> exposed_ms()
         self._exposed = []
+        self._sync = True           # set_sync / no_sync: False = this backward only accumulates into p.grad (gradient accumulation)
         self.reset()
 
     def describe(self) -> dict:
@@ -149,8 +150,33 @@ class GradAllReducer:
         for h in self._handles:
             h.remove()
 
+    def set_sync(self, sync: bool) -> None:
+        """Gradient accumulation (``accumulate_grad_batches``): ``set_sync(False)`` before the backward of a micro-batch that is not
+        the last of its optimizer step -- the hooks then neither count nor launch, and autograd accumulates into ``p.grad`` as on one
+        rank; ``set_sync(True)`` before the last one -- the hooks count and launch as always, and each bucket is packed from the
+        accumulated ``p.grad``: one all-reduce per bucket per optimizer step, in the usual order.  A parameter that received a
+        gradient only in an earlier micro-batch fires no hook in the last one; its bucket is completed by ``finish()`` (the path
+        of parameters without a gradient), which packs its accumulated ``p.grad`` like any other.  Every rank must make the same
+        sequence of calls."""
+        self._sync = bool(sync)
+
+    def no_sync(self):
+        """Context manager form of ``set_sync(False)`` (``torch.nn.parallel.DistributedDataParallel.no_sync``)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            prev, self._sync = self._sync, False
+            try:
+                yield self
+            finally:
+                self._sync = prev
+        return ctx()
+
     # autograd calls this right after p.grad has been written for this backward pass
     def _on_grad(self, p: torch.nn.Parameter):
+        if not self._sync:
+            return
         b = self.buckets[self._index[p]]
         b.pending -= 1
         if b.pending == 0:

@@ -135,20 +135,56 @@ def rescale_size(w: int, h: int, scale) -> Tuple[int, int]:
     return int(w * float(factor) + 0.5), int(h * float(factor) + 0.5)
 
 
+class Draws:
+    """The random state a loader draws from: ``py`` (the ``random`` module or a ``random.Random``), ``np`` (the ``np.random`` module or
+    an ``np.random.RandomState``) and ``torch`` (``None`` = torch's global CPU generator, or a CPU ``torch.Generator``).
+
+    ``Draws()`` is the three process-global generators: every draw lands where it always did, in the same order.  ``Draws(seed)`` owns
+    ``random.Random(seed)``, ``np.random.RandomState(seed)`` and ``torch.Generator().manual_seed(seed)`` -- the MT19937 / Philox streams
+    that ``random.seed(seed)``, ``np.random.seed(seed)`` and ``torch.manual_seed(seed)`` start -- so a loader built with ``seed=s`` returns
+    the batches the unseeded loader returns after seeding the globals with ``s``, without touching the globals.  A loader that runs on
+    a worker thread (``PrefetchLoader``) needs this to be reproducible: the training thread draws from the globals too
+    (``cil_step.tubemix_draw``)."""
+
+    def __init__(self, seed: int = None):
+        import random
+        self.seed = seed
+        if seed is None:
+            self.py, self.np, self.torch = random, np.random, None
+        else:
+            self.py, self.np, self.torch = random.Random(seed), np.random.RandomState(seed), torch.Generator().manual_seed(seed)
+
+    @staticmethod
+    def of(x) -> 'Draws':
+        """``None`` -> the globals, a ``Draws`` -> itself, anything else -> ``Draws(seed)``."""
+        if x is None:
+            return _GLOBAL_DRAWS
+        return x if isinstance(x, Draws) else Draws(int(x))
+
+    def randint(self, high: int, low: int = 0) -> int:
+        """``int(torch.randint(low, high, (1,)))`` on this bundle's torch generator."""
+        return int(torch.randint(low, high, (1,), generator=self.torch).item())
+
+
+_GLOBAL_DRAWS = Draws()
+
+
 def sample_frames(total_frames: int, num_clips: int = 8, clip_len: int = 1, frame_interval: int = 1, test_mode: bool = False,
-                  start_index: int = 1) -> np.ndarray:
+                  start_index: int = 1, draws=None) -> np.ndarray:
     """UPSTREAM mmaction2 0.24 ``SampleFrames`` as the configs use it (``clip_len=1, frame_interval=1, num_clips=8``, no temporal
-    jitter, ``out_of_bound_opt='loop'``): 1-based numbers of the ``img_{:05}.jpg`` files; the train form draws from ``np.random``."""
+    jitter, ``out_of_bound_opt='loop'``): 1-based numbers of the ``img_{:05}.jpg`` files; the train form draws from ``np.random``
+    (``draws``: a ``Draws`` bundle or a seed; ``None`` = the global generator)."""
     ori = clip_len * frame_interval
+    rs = Draws.of(draws).np
     if test_mode:
         avg = (total_frames - ori + 1) / float(num_clips)
         offsets = (np.arange(num_clips) * avg + avg / 2.0).astype(np.int64) if total_frames > ori - 1 else np.zeros((num_clips,), dtype=np.int64)
     else:
         avg = (total_frames - ori + 1) // num_clips
         if avg > 0:
-            offsets = np.arange(num_clips) * avg + np.random.randint(avg, size=num_clips)
+            offsets = np.arange(num_clips) * avg + rs.randint(avg, size=num_clips)
         elif total_frames > max(num_clips, ori):
-            offsets = np.sort(np.random.randint(total_frames - ori + 1, size=num_clips))
+            offsets = np.sort(rs.randint(total_frames - ori + 1, size=num_clips))
         elif avg == 0:
             offsets = np.around(np.arange(num_clips) * ((total_frames - ori + 1.0) / num_clips))
         else:
@@ -171,22 +207,41 @@ class RawFrameClipLoader:
     (frame offsets from ``np.random``; RandAugment's own draws; crop size and offset from ``random``; background index and crop from
     torch's generator), though a multi-worker DataLoader interleaves samples differently anyway.  ``bg_files``: JPEG backgrounds
     (``back_ground_from_bg_dir``); without it a random frame of a random video of the batch's dataset serves (comix_loader.py:134-137
-    draws it from the whole dataset: pass ``bg_video_infos``)."""
+    draws it from the whole dataset: pass ``bg_video_infos``).
+
+    The dataset families of the configs (``config_run.clip_loader_spec`` maps a config onto these):
+      ``with_randAug=True`` (default)   BackgroundMixDataset(with_randAug=True): a sample is mixed exactly when RandAugment skipped it
+      ``with_randAug=False, prob=p``    BackgroundMixDataset(with_randAug=False, prob=p): mixed with probability p, one ``random.random()`` each
+      ``bg_mix=False``                  plain RawframeDataset: RandAugment on its own, no background is read and nothing is blended
+    A setting under which no sample can be mixed (``bg_mix=False``; ``with_randAug`` with a RandAugment probability >= 1;
+    ``with_randAug=False`` with ``prob <= 0``) reads no background file and makes no background draw.
+
+    ``seed``: ``None`` = every draw goes to the process-global generators, in the order given above; an int (or a ``Draws``) = the loader
+    owns its generators (see ``Draws``) and passes them to every stage it builds, and to a ``randAug`` it was given."""
 
     def __init__(self, device='cuda', filename_tmpl: str = 'img_{:05}.jpg', num_segments: int = 8, start_index: int = 1,
                  short_edge: int = 256, input_size: int = 224, randAug=None, randAug_prob: float = 0.75, alpha: float = 0.5,
                  multi_scale_crop: dict = None, bg_files: Sequence[str] = None, bg_video_infos: Sequence[dict] = None,
-                 bg_resize: int = 256, test_crop=('TenCrop', 256), threads: int = 8):
+                 bg_resize: int = 256, test_crop=('TenCrop', 256), threads: int = 8, with_randAug: bool = True, prob: float = 0.25,
+                 bg_mix: bool = True, seed=None):
         from .augment import RandAugment
         from .frontend import BackgroundCropFrontEnd, BackgroundMixFrontEnd, CropFrontEnd, MultiScaleCropResize, TrainClipFrontEnd
         self.device = torch.device(device)
         self.tmpl, self.T, self.start_index, self.short_edge = filename_tmpl, int(num_segments), int(start_index), int(short_edge)
         self.decoder = JpegDecoder(self.device, threads)
+        self.draws = Draws.of(seed)
         msc = dict(input_size=input_size, scales=(1, 0.875, 0.75, 0.66), random_crop=False, max_wh_scale_gap=1, num_fixed_crops=13)
         msc.update(multi_scale_crop or {})
-        self.train_front = TrainClipFrontEnd(randAug if randAug is not None else RandAugment(2, 10, randAug_prob), alpha=alpha,
-                                             with_randAug=True, crop_resize=MultiScaleCropResize(**msc))
-        self.bg_front = BackgroundCropFrontEnd(bg_resize, (input_size, input_size))
+        if randAug is None:
+            randAug = RandAugment(2, 10, randAug_prob, draws=self.draws)
+        elif isinstance(randAug, dict):            # the stage's arguments, as a config spells them: dict(n=, m=, prob=)
+            randAug = RandAugment(**randAug, draws=self.draws)
+        elif seed is not None:
+            randAug.draws = self.draws
+        self.bg_mix = bool(bg_mix)
+        self.train_front = TrainClipFrontEnd(randAug, alpha=alpha, prob=prob, with_randAug=bool(with_randAug),
+                                             crop_resize=MultiScaleCropResize(**msc, draws=self.draws), bg_mix=self.bg_mix, draws=self.draws)
+        self.bg_front = BackgroundCropFrontEnd(bg_resize, (input_size, input_size), draws=self.draws)
         self.center = CropFrontEnd('CenterCrop', input_size)
         self.test = CropFrontEnd(*test_crop)
         self.bg_files, self.bg_video_infos = (list(bg_files) if bg_files else None), bg_video_infos
@@ -204,7 +259,8 @@ class RawFrameClipLoader:
 
     def _frames(self, video_infos: List[dict], test_mode: bool):
         import os.path as osp
-        inds = [sample_frames(int(v['total_frames']), self.T, test_mode=test_mode, start_index=self.start_index) for v in video_infos]
+        inds = [sample_frames(int(v['total_frames']), self.T, test_mode=test_mode, start_index=self.start_index, draws=self.draws)
+                for v in video_infos]
         paths = [osp.join(v['frame_dir'], self.tmpl.format(int(i))) for v, ii in zip(video_infos, inds) for i in ii]
         streams = list(self.decoder.pool.map(self._read, paths))
         clips = [streams[k * self.T:(k + 1) * self.T] for k in range(len(video_infos))]
@@ -213,14 +269,13 @@ class RawFrameClipLoader:
     def _backgrounds(self, B: int, video_infos: List[dict]) -> torch.Tensor:
         """One background per sample, cropped: (B, S, S, 3) fp32 pixel values (only the mixed samples' rows are read)."""
         import os.path as osp
-        import random
         paths = []
         for _ in range(B):
             if self.bg_files:
-                paths.append(self.bg_files[int(torch.randint(len(self.bg_files), (1,)).item())])
+                paths.append(self.bg_files[self.draws.randint(len(self.bg_files))])
             else:
-                v = random.choice(self.bg_video_infos or video_infos)
-                idx = random.randint(self.start_index, int(v['total_frames']) - 1 + self.start_index)
+                v = self.draws.py.choice(self.bg_video_infos or video_infos)
+                idx = self.draws.py.randint(self.start_index, int(v['total_frames']) - 1 + self.start_index)
                 paths.append(osp.join(v['frame_dir'], self.tmpl.format(idx)))
         streams = list(self.decoder.pool.map(self._read, paths))
         infos = [jpeg_parse(s) for s in streams]
@@ -242,7 +297,7 @@ class RawFrameClipLoader:
         frames = K.resize_linear_u8(frames, Hr, Wr)
         extra = {}
         if phase == 'train':
-            bg = self._backgrounds(B, video_infos)
+            bg = None if self.train_front.never_mixes() else self._backgrounds(B, video_infos)
             imgs, rand_flags, _ = self.train_front(frames, bg, as_nchw=True)
             extra['randAug'] = rand_flags
         elif phase == 'test':
@@ -260,16 +315,26 @@ class RawFrameClipLoader:
 
 
 class PrefetchLoader:
-    """Runs a ``clip_loader`` one batch ahead on a worker thread and its own HIP stream, so that reading, the Huffman stage, the
+    """Runs a ``clip_loader`` ahead on a worker thread and its own HIP stream, so that reading, the Huffman stage, the
     per-sample draws and the decode / augment kernels of batch i + 1 overlap the training step of batch i (the reference gets the same
     from its DataLoader workers).  ``submit(video_infos, phase)`` queues a batch, ``get()`` returns the oldest queued batch after making
-    the caller's stream wait for it; or iterate: ``for batch in PrefetchLoader(loader).iterate(list_of_video_info_lists, phase)``.
-    The batch's tensors are handed to the consumer's stream with ``record_stream`` (a handful of tensors per step)."""
+    the caller's stream wait for it; or iterate: ``for batch in PrefetchLoader(loader).iterate(list_of_video_info_lists, phase)``,
+    which keeps ``depth`` batches in flight and leaves nothing queued when it ends, however it ends.
+    The batch's tensors are handed to the consumer's stream with ``record_stream`` (a handful of tensors per step).
 
-    def __init__(self, loader, depth: int = 2):
+    Works with any loader.  Reproducibility needs a seeded one (``RawFrameClipLoader(..., seed=s)``): an unseeded loader draws from the
+    process-global ``random`` / ``np.random`` / torch generators on the worker thread while the training thread draws from the same
+    three (``cil_step.tubemix_draw``), so the order of the draws depends on timing.  With a seeded loader the batches are those of the
+    inline calls, bit for bit: one worker thread serves the batches in submission order.
+
+    An exception the loader raises on the worker thread is re-raised, unchanged, by the ``get()`` of its batch; the batches queued
+    behind it are cancelled (the one already running is waited for) before it propagates.  ``close()`` releases the thread; a later
+    ``submit`` starts a new one.  ``stream``: run the loader on this stream instead of one of the prefetcher's own."""
+
+    def __init__(self, loader, depth: int = 2, stream=None):
         self.loader, self.depth = loader, max(1, int(depth))
-        self.stream = torch.cuda.Stream()
-        self.pool = ThreadPoolExecutor(max_workers=1)
+        self.stream = stream if stream is not None else torch.cuda.Stream()
+        self.pool = None                # the worker thread, started by the first submit
         self.queue = []
         self._bg_files = None           # set_bg_files: the list handed to the loader with each batch submitted after it
         self._scene_infos = None        # set_scene_infos: handed to the loader once, with the first batch submitted after it
@@ -296,11 +361,18 @@ class PrefetchLoader:
         return batch, ev
 
     def submit(self, video_infos, phase: str):
+        if self.pool is None:
+            self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='bdv_prefetch')
         self.queue.append(self.pool.submit(self._work, video_infos, phase, self._bg_files, self._scene_infos))
         self._scene_infos = None
 
     def get(self):
-        batch, ev = self.queue.pop(0).result()
+        fut = self.queue.pop(0)
+        try:
+            batch, ev = fut.result()
+        except BaseException:
+            self.cancel()
+            raise
         cur = torch.cuda.current_stream()
         cur.wait_event(ev)
         for v in batch.values():
@@ -308,15 +380,38 @@ class PrefetchLoader:
                 v.record_stream(cur)
         return batch
 
+    def cancel(self) -> None:
+        """Drop every queued batch: those not started are cancelled, the one running is waited for (its result, or its exception,
+        is discarded).  Afterwards nothing of this prefetcher runs."""
+        queue, self.queue = self.queue, []
+        for fut in queue:
+            fut.cancel()
+        for fut in queue:
+            if not fut.cancelled():
+                try:
+                    fut.result()
+                except BaseException:      # discarded with the batch it belongs to
+                    pass
+
+    def close(self) -> None:
+        """``cancel()``, then end the worker thread (joined before this returns)."""
+        self.cancel()
+        if self.pool is not None:
+            self.pool.shutdown(wait=True)
+            self.pool = None
+
     def iterate(self, batches_of_infos, phase: str):
         it = iter(batches_of_infos)
-        for infos in it:
-            self.submit(infos, phase)
-            if len(self.queue) >= self.depth:
-                break
-        for infos in it:
-            out = self.get()
-            self.submit(infos, phase)
-            yield out
-        while self.queue:
-            yield self.get()
+        try:
+            for infos in it:
+                self.submit(infos, phase)
+                if len(self.queue) >= self.depth:
+                    break
+            for infos in it:
+                out = self.get()
+                self.submit(infos, phase)
+                yield out
+            while self.queue:
+                yield self.get()
+        finally:
+            self.cancel()       # a consumer that stopped early (an exception in its step) leaves nothing queued

@@ -43,7 +43,9 @@ class BackgroundCropFrontEnd:
     the crop's size -- so a seeded run picks the reference's crops.  Parity unpinned: torchvision is not importable here (its
     version is not pinned by the reference either); the resampling follows ATen's bilinear kernel, which torchvision calls."""
 
-    def __init__(self, resize: int = 256, crop_size=(224, 224)):
+    def __init__(self, resize: int = 256, crop_size=(224, 224), draws=None):
+        from .decode import Draws
+        self.draws = Draws.of(draws)         # ``draws``: a ``decode.Draws`` bundle or a seed; None = torch's global generator
         self.resize = int(resize)
         self.crop = (int(crop_size), int(crop_size)) if isinstance(crop_size, int) else (int(crop_size[0]), int(crop_size[1]))   # (h, w)
 
@@ -56,8 +58,8 @@ class BackgroundCropFrontEnd:
             if (h, w) == (th, tw):
                 i = j = 0
             else:
-                i = int(torch.randint(0, h - th + 1, size=(1,)).item())
-                j = int(torch.randint(0, w - tw + 1, size=(1,)).item())
+                i = self.draws.randint(h - th + 1)
+                j = self.draws.randint(w - tw + 1)
             tops.append(i)
             lefts.append(j)
         return tops, lefts
@@ -81,30 +83,50 @@ class TrainClipFrontEnd:
     ``random.random()`` per sample).  ``crop_resize`` is the hook for the stages the reference runs between the two
     (MultiScaleCrop + Resize, configs/...bgmix_plus_randAug.py:131-138), applied to the uint8 clips when given.
     Returns ``(Nhwc4Frames, randAug (B,) bool, mixed (B,) bool)``; ``randAug`` is what the reference collects into the
-    batch under that key."""
+    batch under that key.  ``bg_mix=False`` is the plain ``RawframeDataset``: RandAugment (when given) on its own, no decision, no draw
+    and no blend (``mixed`` is then None).  ``draws``: a ``decode.Draws`` bundle or a seed for the ``random.random()`` draws; None = the
+    global ``random``."""
 
-    def __init__(self, randaug=None, alpha: float = 0.5, prob: float = 0.25, with_randAug: bool = True, crop_resize=None):
+    def __init__(self, randaug=None, alpha: float = 0.5, prob: float = 0.25, with_randAug: bool = True, crop_resize=None,
+                 bg_mix: bool = True, draws=None):
+        from .decode import Draws
         self.randaug, self.prob, self.with_randAug, self.crop_resize = randaug, prob, with_randAug, crop_resize
+        self.bg_mix, self.draws = bool(bg_mix), Draws.of(draws)
         self.mix = BackgroundMixFrontEnd(alpha=alpha)
+
+    def never_mixes(self) -> bool:
+        """True when no sample can be mixed whatever is drawn, so that the caller need not produce backgrounds: no mixing at all, a
+        RandAugment that always fires (``random() < prob`` with prob >= 1), or a mix probability <= 0."""
+        if not self.bg_mix:
+            return True
+        if self.with_randAug:
+            return self.randaug is not None and self.randaug.prob >= 1
+        return self.prob <= 0
 
     def decide(self, frames_u8: torch.Tensor):
         B = frames_u8.shape[0]
+        if not self.bg_mix:
+            if self.randaug is None:
+                return frames_u8, torch.zeros(B, dtype=torch.bool, device=frames_u8.device), None
+            frames_u8, rand_flags = self.randaug(frames_u8)
+            return frames_u8, rand_flags, None
         if self.with_randAug:
             if self.randaug is None:
                 raise ValueError('with_randAug=True needs a RandAugment stage (comix_loader.py:109-111 reads result["randAug"])')
             frames_u8, rand_flags = self.randaug(frames_u8)
             return frames_u8, rand_flags, ~rand_flags
-        import random
         rand_flags = torch.zeros(B, dtype=torch.bool, device=frames_u8.device)
         if self.randaug is not None:
             frames_u8, rand_flags = self.randaug(frames_u8)
-        mixed = torch.tensor([random.random() < self.prob for _ in range(B)], dtype=torch.bool, device=frames_u8.device)
+        mixed = torch.tensor([self.draws.py.random() < self.prob for _ in range(B)], dtype=torch.bool, device=frames_u8.device)
         return frames_u8, rand_flags, mixed
 
     def __call__(self, frames_u8: torch.Tensor, bg_u8: torch.Tensor, as_nchw: bool = False):
         frames_u8, rand_flags, mixed = self.decide(frames_u8)
         if self.crop_resize is not None:
             frames_u8, bg_u8 = self.crop_resize(frames_u8, bg_u8)
+        if mixed is None or bg_u8 is None:        # nothing to blend (``never_mixes``): Normalize alone
+            bg_u8 = mixed = None
         out = self.mix.as_nchw(frames_u8, bg_u8, mixed) if as_nchw else self.mix(frames_u8, bg_u8, mixed)
         return out, rand_flags, mixed
 
@@ -169,7 +191,9 @@ class MultiScaleCropResize:
     ``cv2.resize(INTER_LINEAR)`` in one kernel (``bdv_resize_linear_u8``; parity unpinned, see include/bdvcil_hip.h)."""
 
     def __init__(self, input_size=224, scales=(1, 0.875, 0.75, 0.66), max_wh_scale_gap=1, random_crop=False, num_fixed_crops=5,
-                 out_size=None):
+                 out_size=None, draws=None):
+        from .decode import Draws
+        self.draws = Draws.of(draws)         # ``draws``: a ``decode.Draws`` bundle or a seed; None = the global ``random``
         self.input_size = (input_size, input_size) if isinstance(input_size, int) else tuple(input_size)       # (w, h)
         self.scales, self.gap, self.random_crop = tuple(scales), int(max_wh_scale_gap), bool(random_crop)
         if num_fixed_crops not in (5, 13):
@@ -178,7 +202,7 @@ class MultiScaleCropResize:
         self.out_size = self.input_size if out_size is None else tuple(out_size)                               # (w, h) of the Resize after it
 
     def draw(self, img_w: int, img_h: int):
-        import random
+        random = self.draws.py
         base = min(img_w, img_h)
         sizes = [int(base * s) for s in self.scales]
         cand = [[w, h] for i, h in enumerate(sizes) for j, w in enumerate(sizes) if abs(i - j) <= self.gap]

@@ -344,12 +344,28 @@ class CILTaskLoop:
     lr_scheduler, cbf_*, use_cbf, budget_size, storing_methods, budget_type, save_best, kd_modules_names,
     kd_weight_by_module, adaptive_scale_factors, repr_hook, data_root, train_ann_file, val_ann_file,
     cil_ann_file_template, model).  ``clip_loader(video_infos, phase) -> batch_data`` supplies the frames.
+
+    ``prefetch``: 0 = the loader is called inline, batch by batch.  n > 0 = every epoch of ``fit`` and every ``predict`` (validation,
+    feature extraction, class means, testing) draws its batches through one ``PrefetchLoader(clip_loader, depth=n)``, n batches ahead
+    on a worker thread and stream of its own, drained at the end of each epoch / predict call, so nothing is in flight across a fit
+    boundary or a phase change.  None (default) = the config's ``prefetch_batches`` key, 0 without it.  With a seeded loader the
+    batches, and so the files of the run, do not depend on ``prefetch``; an unseeded loader draws from the process-global generators
+    on the worker thread and is not reproducible under prefetch.  An exception the loader raises surfaces at its batch, on the
+    calling thread; the worker is shut down before it propagates.  ``close()`` releases the thread.
     """
 
-    def __init__(self, config, clip_loader: Callable[[List[dict], str], Dict], device='cuda', seed: int = 0, log: Callable = print):
+    def __init__(self, config, clip_loader: Callable[[List[dict], str], Dict], device='cuda', seed: int = 0, log: Callable = print,
+                 prefetch: Optional[int] = None):
         self.config = config = config if isinstance(config, AttrDict) else AttrDict(config)
         self.device = torch.device(device)
         self.clip_loader = clip_loader
+        self.prefetch = int(config.get('prefetch_batches', 0) if prefetch is None else prefetch)
+        if self.prefetch < 0:
+            raise ValueError(f'prefetch must be >= 0, got {self.prefetch}')
+        self._prefetcher = None
+        if self.prefetch > 0:
+            from .decode import PrefetchLoader
+            self._prefetcher = PrefetchLoader(clip_loader, depth=self.prefetch)
         self.log = log
         self.splits = TaskSplits(config.task_splits)
         self.files = CILWorkDir(config.work_dir, self.splits, config.get('cil_ann_file_template', '{}_task_{}.txt'))
@@ -407,6 +423,21 @@ class CILTaskLoop:
                                                      test_mode=True, phase='val'))
 
     # -- small helpers ---------------------------------------------------------------------------------------------------
+    def close(self) -> None:
+        """Release the prefetch thread (nothing to do with ``prefetch=0``).  The loop stays usable: the next batch starts a new one."""
+        if self._prefetcher is not None:
+            self._prefetcher.close()
+
+    def _load(self, records: 'RawframeRecords', batches: Sequence[Sequence[int]]):
+        """The batches of one epoch / one predict call, in order: inline, or through the prefetcher (which is empty again when this
+        generator ends, also when its consumer raised)."""
+        lists = ([records.video_infos[i] for i in idx] for idx in batches)
+        if self._prefetcher is None:
+            for infos in lists:
+                yield self.clip_loader(infos, records.phase)
+        else:
+            yield from self._prefetcher.iterate(lists, records.phase)
+
     def _barrier(self):
         if self.world > 1:
             dist.barrier()
@@ -544,7 +575,8 @@ class CILTaskLoop:
         optimizer = build_optimizer(self.current_model, dict(opt_cfg))
         scheduler = build_lr_scheduler(optimizer, sch_cfg) if sch_cfg else None
         reducer = None
-        if self.world > 1:
+        from . import ddp
+        if self.world > 1 or (ddp._FORCE and dist.is_initialized()):      # BDVCIL_FORCE_DIST: the exchange in a one-rank group too
             # DistributedDataParallel is constructed per fit and starts from rank 0's weights and buffers: this is what
             # makes the freshly initialised classifier rows of ``update_fc`` agree across ranks
             broadcast_parameters(self.current_model)
@@ -552,15 +584,18 @@ class CILTaskLoop:
             optimizer.set_grad_scale(reducer.grad_scale)
         clip = None if self._current_task == 0 else 1.0
         accum = int(cfg.get('accumulate_grad_batches', 1))
-        if accum > 1 and reducer is not None:
-            raise NotImplementedError('accumulate_grad_batches > 1 with several ranks (the 8-GPU setting of the configs uses 1)')
+        # with a prefetcher the lists travel with the batches submitted from here on (nothing is queued between fits)
+        front = self._prefetcher if self._prefetcher is not None else self.clip_loader
         if self._bg_config() is not None and hasattr(self.clip_loader, 'set_bg_files'):
-            self.clip_loader.set_bg_files(records.bg_files)
+            front.set_bg_files(records.bg_files)
         if hasattr(self.clip_loader, 'set_scene_infos'):           # ActorCutMix: scenes come from the whole (merged) training set
-            self.clip_loader.set_scene_infos(records.video_infos)
+            front.set_scene_infos(records.video_infos)
         epoch_losses = []
         try:
             self._fit_epochs(records, max_epochs, validate, optimizer, scheduler, reducer, clip, accum, epoch_losses)
+        except BaseException:
+            self.close()                # no worker thread outlives a failed fit
+            raise
         finally:
             if reducer is not None:
                 reducer.remove()        # also on an exception: stale post-accumulate hooks would fire collectives in the next fit
@@ -577,13 +612,17 @@ class CILTaskLoop:
             batches = epoch_batches(len(records), cfg.videos_per_gpu, True, self._shuffle_gen, self.rank, self.world)
             total, pending = 0.0, 0
             optimizer.zero_grad(set_to_none=True)
-            for bi, idx in enumerate(batches):
-                batch_data = self.clip_loader([records.video_infos[i] for i in idx], records.phase)
+            for bi, batch_data in enumerate(self._load(records, batches)):
                 losses = self._training_step(batch_data)
-                (losses['loss'] / accum if accum > 1 else losses['loss']).backward()
                 pending += 1
+                boundary = pending == accum or bi == len(batches) - 1
+                if reducer is not None:
+                    # gradient accumulation over several ranks: only the last micro-batch of an optimizer step is reduced, from the
+                    # accumulated p.grad (every rank has the same number of batches, so the ranks agree on the boundaries)
+                    reducer.set_sync(boundary)
+                (losses['loss'] / accum if accum > 1 else losses['loss']).backward()
                 total = total + losses['loss'].detach()
-                if pending == accum or bi == len(batches) - 1:
+                if boundary:
                     if reducer is not None:
                         reducer.finish()
                     if clip:
@@ -668,8 +707,11 @@ class CILTaskLoop:
         predictor = ReprPredictor(self.current_model, self.repr_module_name, extract_repr=extract_repr, extract_meta=extract_meta)
         out = []
         try:
-            for idx in epoch_batches(len(records), batch_size, False):
-                out.append(predictor.predict_step(self.clip_loader([records.video_infos[i] for i in idx], records.phase)))
+            for batch_data in self._load(records, epoch_batches(len(records), batch_size, False)):
+                out.append(predictor.predict_step(batch_data))
+        except BaseException:
+            self.close()
+            raise
         finally:
             predictor.close()
             self.current_model.train(was_training)

@@ -1,0 +1,74 @@
+"""Run a CIL config file end to end: train every task of the config, or re-test the checkpoints of a finished run.
+
+    VIDEO_CIL_ROOT=/data/ucf101 python tools/train_cil.py CONFIG [--test] [--test-nme] [--prefetch N] [--seed S] [--device D]
+
+CONFIG is a config file of the reference (configs/ucf101/..., self-contained Python that reads VIDEO_CIL_ROOT).  The clip loader is
+built from the config's ``data.train`` and its four pipelines (``bdvcil_amd.clip_loader_spec``; a stage the loaders cannot honour is an
+error, not a guess), and ``CILTaskLoop`` leaves the reference's files in the config's ``work_dir``; training ends with the re-test of
+every task's checkpoint (``cnn_result.txt``; with ``--test-nme`` also ``nme_result.txt``), and ``--test`` does only that.  ``--seed`` seeds the loader's own generators,
+the shuffle and the process-global generators the training step draws from, which makes a run reproducible at any ``--prefetch``.
+Several GPUs: start one process per GPU with torchrun; the process group is picked up from the environment."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('config')
+    ap.add_argument('--test', action='store_true', help='re-test the checkpoints of the work_dir instead of training')
+    ap.add_argument('--test-nme', action='store_true', help='test the nearest-mean-of-exemplars classifier too')
+    ap.add_argument('--prefetch', type=int, default=2, help='batches loaded ahead on a worker thread (0 = inline)')
+    ap.add_argument('--seed', type=int, default=None)
+    ap.add_argument('--device', default=None)
+    ap.add_argument('--threads', type=int, default=8, help='host threads of the JPEG entropy stage')
+    args = ap.parse_args(argv)
+
+    import bdvcil_amd as bd           # before the first torch.cuda call (GPU_MAX_HW_QUEUES)
+    import torch
+    import torch.distributed as dist
+    local = int(os.environ.get('LOCAL_RANK', 0))
+    device = args.device or f'cuda:{local}'
+    torch.cuda.set_device(torch.device(device))
+    if int(os.environ.get('WORLD_SIZE', 1)) > 1 and not dist.is_initialized():
+        dist.init_process_group('nccl')
+    if args.seed is not None:
+        import random
+        import numpy as np
+        random.seed(args.seed)
+        np.random.seed(args.seed)
+        torch.manual_seed(args.seed)
+    cfg = bd.load_config(args.config)
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    # each rank loads its own share of an epoch: its loader draws from its own stream
+    loader = bd.build_clip_loader(cfg, device=device, seed=None if args.seed is None else args.seed + rank, threads=args.threads)
+
+    def make_loop():
+        return bd.CILTaskLoop(cfg, loader, device=device, seed=args.seed or 0, prefetch=args.prefetch)
+
+    try:
+        if not args.test:
+            loop = make_loop()
+            try:
+                loop.train()
+            finally:
+                loop.close()
+        # the accuracy tables of every task's checkpoint: the last thing a training run does, and all that --test does
+        loop = make_loop()
+        try:
+            tables = loop.cil_testing(test_nme=args.test_nme)
+        finally:
+            loop.close()
+        if rank == 0:
+            for name in sorted(tables):
+                print(tables[name])
+    finally:
+        if dist.is_initialized():
+            dist.destroy_process_group()
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
