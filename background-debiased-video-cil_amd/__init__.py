@@ -10,7 +10,8 @@ Import as ``bdvcil_amd`` (see ``bdvcil_amd.py`` at the repo root).  Layout:
                    the reference's mmaction2-style plugin surface (same names / signatures / state_dict keys)
 * ``frontend``     fused background-mix + normalize; train front-end = RandAugment -> mix decision -> blend
 * ``actor_cut_mix``  ActorCutMix clip loader: detection boxes on the host, composite + normalize in csrc/actor_cut_mix.hip
-* ``background``   background extraction: temporal median + JPEG encode of the frames of a video (bg_extraction_tmf)
+* ``background``   background extraction: temporal median + JPEG encode of the frames of a video (bg_extraction_tmf); resized crop +
+                   NaN-aware median / mean for moving-camera videos (sim_cam_motion_bg_extract)
 * ``augment``      RandAugment for batches of uint8 clips (draws + device tables; pixels in csrc/augment.hip)
 * ``cil_step``     training-step arithmetic of BaseCIL / ICARLModel + a step engine
 * ``ddp``          bucketed gradient all-reduce over RCCL
@@ -56,7 +57,8 @@ from .frontend import BackgroundCropFrontEnd, BackgroundMixFrontEnd, CropFrontEn
 from .decode import Draws, JpegDecoder, PrefetchLoader, RawFrameClipLoader, sample_frames  # noqa: F401
 from .actor_cut_mix import ActorCutMixClipLoader  # noqa: F401
 from .augment import RandAugment  # noqa: F401
-from .background import encode_jpeg, extract_background, resolve_bg_files, temporal_median  # noqa: F401
+from .background import (encode_jpeg, extract_background, extract_backgrounds, random_resized_crop_boxes, resized_crop,  # noqa: F401
+                         resolve_bg_files, sim_cam_frame_files, temporal_median, temporal_nanreduce)
 from .cil_step import (TrainEngine, base_training_step, icarl_training_step, icarl_video_mix_training_step,  # noqa: F401
                        tubemix_draw)
 from .ddp import GradAllReducer, broadcast_parameters  # noqa: F401

@@ -122,6 +122,8 @@ SIGNATURES = {
     'bdv_jpeg_workspace_bytes': (c_size_t, [POINTER(JpegInfo), c_int]),
     'bdv_jpeg_reconstruct_u8': (c_int, [P, P, POINTER(JpegInfo), c_int, P, c_size_t, P, P]),
     'bdv_temporal_median_u8': (c_int, [P, c_int64, P, P, P, P, c_int, c_int, c_int, P, P]),
+    'bdv_resized_crop_f32': (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, c_int, P, P]),
+    'bdv_temporal_nanreduce_f32': (c_int, [P, c_int64, P, P, P, P, c_int, c_int64, c_int, c_int, P, P]),
     'bdv_jpeg_encode_info': (c_int, [c_int, c_int, c_int, POINTER(JpegInfo)]),
     'bdv_jpeg_forward_u8': (c_int, [P, c_int, c_int, c_int, c_int, P, P]),
     'bdv_jpeg_encode_bound': (c_size_t, [c_int, c_int]),
@@ -165,7 +167,7 @@ class HipExtensionError(RuntimeError):
 
 
 HASHED_SOURCES = ('conv_mfma.hip', 'bn.hip', 'pool_frontend.hip', 'head_loss.hip', 'repr.hip', 'augment.hip', 'optim.hip', 'jpeg.hip',
-                  'background.hip', 'actor_cut_mix.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
+                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
 
 
 def source_hash():

@@ -7,10 +7,20 @@ Here the frames are decoded by ``JpegDecoder`` (bit-exact with libjpeg-turbo), t
 (``bdv_temporal_median_u8``), the JPEG forward stage -- colour conversion, downsampling, DCT, quantisation -- as one more
 (``bdv_jpeg_forward_u8``), and the Huffman stage on host threads (``bdv_jpeg_entropy_encode_batch``): the written bytes are
 libjpeg-turbo's.  The reference works in BGR (cv2) and returns the BGR median; per-channel medians and the colour conversion of
-the encoder make the file the same, and the arrays returned here are RGB."""
+the encoder make the file the same, and the arrays returned here are RGB.
+
+``method='sim_cam'`` is the other extraction of the reference, ``sim_cam_motion_bg_extract`` (cil_tools/extract_background.py:78-99),
+for videos shot with a moving camera: the sorted files of the directory but the last, every ``interval``-th, at most ``max_frames``;
+each frame as a float image through torchvision's ``RandomResizedCrop(size=100)``; exact zeros become NaN; ``np.nanmedian`` or
+``np.nanmean`` over time; ``.astype(np.uint8)``; written as it is (the reference's BGR2RGB before ``cv2.imwrite`` undoes imwrite's
+own channel swap).  Here: one crop launch (``bdv_resized_crop_f32``) and one reduce launch (``bdv_temporal_nanreduce_f32``) per batch
+of videos.  The box draws restate UPSTREAM torchvision ``RandomResizedCrop.get_params`` from its published behaviour -- parity
+unpinned: torchvision is not importable here (its version is not pinned by the reference either); the resampling follows ATen's
+bilinear kernels, which torchvision calls, and is pinned by ``torch.nn.functional.interpolate`` on the CPU."""
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import pathlib
 import tempfile
@@ -23,6 +33,10 @@ from ._lib import JpegInfo, check, lib
 
 DEFAULT_QUALITY = 95                    # cv2.IMWRITE_JPEG_QUALITY's default
 MAX_BATCH_BYTES = 2 << 30               # device bytes of decoded frames per extraction launch
+METHODS = ('tmf', 'sim_cam')            # --method of cil_tools/extract_background.py
+AVG_METHODS = ('median', 'mean')        # --avg_method (sim_cam only: bg_extraction_tmf ignores it)
+SIM_CAM_SIZE = 100                      # RandomResizedCrop(size=100), extract_background.py:82
+SIM_CAM_MAX_FRAMES = 500                # --max_frames' default
 
 
 def _device(device) -> torch.device:
@@ -114,6 +128,105 @@ def temporal_median(frames_u8, counts: Sequence[int], device=None) -> torch.Tens
     return out
 
 
+def sim_cam_frame_files(frame_dir, interval: int = 1, max_frames: int = SIM_CAM_MAX_FRAMES) -> List[pathlib.Path]:
+    """The frames ``sim_cam_motion_bg_extract`` reads (extract_background.py:83-89): ``sorted(glob('*'))[:-1:interval]`` -- the last
+    file is always left out -- cut off after ``max_frames``.  A directory that yields no frame (a single file) raises ``ValueError``."""
+    d = pathlib.Path(frame_dir)
+    if not d.is_dir():
+        raise FileNotFoundError(f'extract_background: {d} is not a directory')
+    if int(interval) < 1 or int(max_frames) < 1:
+        raise ValueError(f'extract_background: interval {interval} and max_frames {max_frames} must be positive')
+    files = sorted(d.glob('*'))[:-1:int(interval)][:int(max_frames)]
+    if not files:
+        raise ValueError(f'extract_background: {d} yields no frames (sim_cam leaves the last file of a directory out)')
+    return files
+
+
+def random_resized_crop_boxes(n: int, height: int, width: int, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), draws=None) -> np.ndarray:
+    """``n`` boxes ``[top, left, h, w]`` (int32) as UPSTREAM torchvision ``RandomResizedCrop.get_params`` draws them for ``n`` frames
+    of ``height x width``, one frame after the other (parity unpinned, see the module docstring).  Per frame up to 10 attempts, each
+    two uniform draws on the torch generator -- the area fraction in ``scale``, then the log of the aspect ratio between the float32
+    logs of ``ratio`` -- ``w = round(sqrt(area * aspect))``, ``h = round(sqrt(area / aspect))``; the first pair that fits the frame
+    is placed with ``randint(0, height - h + 1)`` then ``randint(0, width - w + 1)``.  After 10 misses no further draw is made: the
+    frame is cut to the nearest allowed aspect ratio and the box centred.  ``draws``: a ``decode.Draws`` bundle or a seed; ``None`` =
+    torch's global generator."""
+    from .decode import Draws
+    d = Draws.of(draws)
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError(f'random_resized_crop_boxes: bad frame size {height} x {width}')
+    log_ratio = torch.log(torch.tensor([float(ratio[0]), float(ratio[1])]))
+    lo, hi = float(log_ratio[0]), float(log_ratio[1])
+    area = height * width
+    boxes = np.empty((int(n), 4), dtype=np.int32)
+    for k in range(int(n)):
+        for _ in range(10):
+            target_area = area * torch.empty(1).uniform_(float(scale[0]), float(scale[1]), generator=d.torch).item()
+            aspect = torch.exp(torch.empty(1).uniform_(lo, hi, generator=d.torch)).item()
+            w = int(round(math.sqrt(target_area * aspect)))
+            h = int(round(math.sqrt(target_area / aspect)))
+            if 0 < w <= width and 0 < h <= height:
+                top = d.randint(height - h + 1)
+                left = d.randint(width - w + 1)
+                break
+        else:
+            in_ratio = float(width) / float(height)
+            if in_ratio < min(ratio):
+                w = width
+                h = int(round(w / min(ratio)))
+            elif in_ratio > max(ratio):
+                h = height
+                w = int(round(h * max(ratio)))
+            else:
+                w, h = width, height
+            top, left = (height - h) // 2, (width - w) // 2
+        boxes[k] = (top, left, h, w)
+    return boxes
+
+
+def _size_hw(size) -> Tuple[int, int]:
+    hw = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if min(hw) < 1:
+        raise ValueError(f'resized_crop: bad output size {size}')
+    return hw
+
+
+def resized_crop(frames_u8, boxes, size=SIM_CAM_SIZE, antialias: bool = False, device=None) -> torch.Tensor:
+    """torchvision's ``resized_crop`` of float frames, bilinear: ``frames_u8`` ``(F, H, W, 3)`` uint8 (tensor or array), ``boxes``
+    ``(F, 4)`` ``[top, left, h, w]`` -> ``(F, size_h, size_w, 3)`` fp32 pixel values on the device.  ``antialias=False`` is the
+    torchvision of the reference's era (tensors were not antialiased), ``True`` the current default."""
+    from . import kernels as K
+    frames = torch.as_tensor(frames_u8)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f'resized_crop: expected (F, H, W, 3) uint8 frames, got {tuple(frames.shape)} {frames.dtype}')
+    b = np.asarray(boxes.cpu() if isinstance(boxes, torch.Tensor) else boxes, dtype=np.int64).reshape(-1, 4)
+    H, W = int(frames.shape[1]), int(frames.shape[2])
+    if b.shape[0] != frames.shape[0]:
+        raise ValueError(f'resized_crop: {b.shape[0]} boxes for {frames.shape[0]} frames')
+    if b.shape[0] and ((b[:, :2] < 0).any() or (b[:, 2:] < 1).any() or (b[:, 0] + b[:, 2] > H).any() or (b[:, 1] + b[:, 3] > W).any()):
+        raise ValueError(f'resized_crop: a box leaves the {H} x {W} frame')
+    dev = frames.device if frames.is_cuda else _device(device)
+    sh, sw = _size_hw(size)
+    return K.resized_crop_f32(frames.to(dev).contiguous(), b.astype(np.int32), sh, sw, bool(antialias))
+
+
+def temporal_nanreduce(frames_f32, counts: Sequence[int], avg_method: str = 'median', zero_is_missing: bool = True, device=None) -> torch.Tensor:
+    """``np.nanmedian(frames_v, axis=0).astype(np.uint8)`` (or ``np.nanmean``) for every video v of a ragged batch, after
+    ``frames_v[frames_v == 0] = nan`` when ``zero_is_missing``: ``frames_f32`` ``(sum(counts), ...)`` fp32 (tensor or array; the
+    videos' frames back to back) -> ``(V, ...)`` uint8 on the device.  A position missing in every frame gives 0."""
+    from . import kernels as K
+    if avg_method not in AVG_METHODS:
+        raise ValueError(f'temporal_nanreduce: avg_method {avg_method!r} (one of {AVG_METHODS})')
+    counts = [int(c) for c in counts]
+    frames = torch.as_tensor(frames_f32)
+    if frames.dtype != torch.float32 or frames.dim() < 2:
+        raise ValueError(f'temporal_nanreduce: expected (F, ...) float32 frames, got {tuple(frames.shape)} {frames.dtype}')
+    if not counts or min(counts) < 1 or max(counts) > 65535 or sum(counts) != frames.shape[0]:
+        raise ValueError(f'temporal_nanreduce: frame counts {counts} do not partition {frames.shape[0]} frames (1..65535 per video)')
+    dev = frames.device if frames.is_cuda else _device(device)
+    return K.temporal_nanreduce_f32(frames.to(dev).contiguous(), counts, AVG_METHODS.index(avg_method), bool(zero_is_missing))
+
+
 def _frame_files(frame_dir: pathlib.Path) -> List[pathlib.Path]:
     """Every regular file of the directory, as the reference's ``data_path.glob('*')`` (flow frames included); sorted, which the
     median does not see."""
@@ -125,10 +238,10 @@ def _frame_files(frame_dir: pathlib.Path) -> List[pathlib.Path]:
     return files
 
 
-def _read_frames(frame_dir: pathlib.Path) -> Tuple[List[bytes], Tuple[int, int]]:
+def _read_frames(frame_dir: pathlib.Path, files: Optional[List[pathlib.Path]] = None) -> Tuple[List[bytes], Tuple[int, int]]:
     from .decode import jpeg_parse
     streams, size = [], None
-    for p in _frame_files(frame_dir):
+    for p in (files if files is not None else _frame_files(frame_dir)):
         data = p.read_bytes()
         try:
             info = jpeg_parse(data)
@@ -157,42 +270,76 @@ def _write_atomic(dest: pathlib.Path, data: bytes) -> None:
         raise
 
 
+def _check_method(method: str, avg_method: str, interval: int, max_frames: int) -> None:
+    if method not in METHODS:
+        raise ValueError(f'extract_background: method {method!r} (one of {METHODS})')
+    if avg_method not in AVG_METHODS:
+        raise ValueError(f'extract_background: avg_method {avg_method!r} (one of {AVG_METHODS})')
+    if method == 'tmf' and (avg_method != 'median' or int(interval) != 1 or int(max_frames) != SIM_CAM_MAX_FRAMES):
+        raise ValueError("extract_background: method 'tmf' is the median of every frame; avg_method, interval and max_frames "
+                         "belong to method 'sim_cam'")
+
+
 def extract_backgrounds(jobs: Sequence[Tuple[str, str]], decoder=None, quality: int = DEFAULT_QUALITY,
-                        max_batch_bytes: int = MAX_BATCH_BYTES, return_arrays: bool = False) -> Optional[List[np.ndarray]]:
+                        max_batch_bytes: int = MAX_BATCH_BYTES, return_arrays: bool = False, method: str = 'tmf',
+                        avg_method: str = 'median', interval: int = 1, max_frames: int = SIM_CAM_MAX_FRAMES, size=SIM_CAM_SIZE,
+                        antialias: bool = False, draws=None) -> Optional[List[np.ndarray]]:
     """``bg_extraction_tmf`` for many ``(frame_dir, dest)`` pairs: videos of one frame size are batched into one median launch, one
     forward-stage launch and one threaded Huffman call, up to ``max_batch_bytes`` of decoded frames per batch (a single longer video
-    is a batch of its own).  A frame directory that fails its checks raises before its file is written."""
-    from .decode import JpegDecoder
+    is a batch of its own).  A frame directory that fails its checks raises before its file is written.
+
+    ``method='sim_cam'``: ``sim_cam_motion_bg_extract`` instead (see the module docstring) -- per batch decode, one crop launch, one
+    reduce launch (``avg_method`` 'median' | 'mean'), encode, write; a video's share of the budget is its selected frames plus their
+    fp32 crops.  The crop boxes are drawn video by video in job order from ``draws`` (a ``decode.Draws`` bundle or a seed; ``None`` =
+    torch's global generator); ``size`` (int or ``(h, w)``) and ``antialias`` as in ``resized_crop``."""
+    from .decode import Draws, JpegDecoder
+    _check_method(method, avg_method, interval, max_frames)
     decoder = decoder if decoder is not None else JpegDecoder('cuda')
     results: Optional[List[np.ndarray]] = [None] * len(jobs) if return_arrays else None
     pending: Dict[Tuple[int, int], List[tuple]] = {}
-    for pos, (d, dest) in enumerate(jobs):
-        streams, (H, W) = _read_frames(pathlib.Path(d))
-        item = (pathlib.Path(dest), streams, pos)
-        batch = pending.setdefault((H, W), [])
-        if batch and (sum(len(it[1]) for it in batch) + len(streams)) * H * W * 3 > max_batch_bytes:
+    if method == 'sim_cam':
+        draws = Draws.of(draws)
+        sh, sw = _size_hw(size)
+
+        def flush(batch, H, W):
+            _extract_batch_sim_cam(batch, H, W, decoder, quality, results, (sh, sw), antialias, avg_method)
+    else:
+        def flush(batch, H, W):
             _extract_batch(batch, H, W, decoder, quality, results)
+    for pos, (d, dest) in enumerate(jobs):
+        if method == 'sim_cam':
+            streams, (H, W) = _read_frames(pathlib.Path(d), sim_cam_frame_files(d, interval, max_frames))
+            item = (pathlib.Path(dest), streams, pos, random_resized_crop_boxes(len(streams), H, W, draws=draws))
+            per_frame = H * W * 3 + sh * sw * 3 * 4
+        else:
+            streams, (H, W) = _read_frames(pathlib.Path(d))
+            item = (pathlib.Path(dest), streams, pos)
+            per_frame = H * W * 3
+        batch = pending.setdefault((H, W), [])
+        if batch and (sum(len(it[1]) for it in batch) + len(streams)) * per_frame > max_batch_bytes:
+            flush(batch, H, W)
             batch.clear()
         batch.append(item)
     for (H, W), batch in pending.items():
         if batch:
-            _extract_batch(batch, H, W, decoder, quality, results)
+            flush(batch, H, W)
     return results
 
 
-def _extract_batch(items, H, W, decoder, quality, results):
-    counts = [len(it[1]) for it in items]
-    frames = torch.empty(sum(counts), H, W, 3, dtype=torch.uint8, device=decoder.device)
+def _decode_items(items, H, W, decoder) -> torch.Tensor:
+    frames = torch.empty(sum(len(it[1]) for it in items), H, W, 3, dtype=torch.uint8, device=decoder.device)
     at = 0
     for it in items:
         for s in range(0, len(it[1]), 256):                  # bounded staging buffers for the coefficient upload
             part = it[1][s:s + 256]
             frames[at:at + len(part)] = decoder.decode(part)
             at += len(part)
-    med = temporal_median(frames, counts)
-    del frames
-    files = encode_jpeg(med, quality, threads=decoder.threads)
-    host = med.cpu().numpy() if results is not None else None
+    return frames
+
+
+def _write_items(items, images, decoder, quality, results) -> None:
+    files = encode_jpeg(images, quality, threads=decoder.threads)
+    host = images.cpu().numpy() if results is not None else None
     for k, (it, data) in enumerate(zip(items, files)):
         it[0].parent.mkdir(parents=True, exist_ok=True)
         _write_atomic(it[0], data)
@@ -200,10 +347,30 @@ def _extract_batch(items, H, W, decoder, quality, results):
             results[it[2]] = host[k]
 
 
-def extract_background(frame_dir, dest, decoder=None, quality: int = DEFAULT_QUALITY) -> np.ndarray:
+def _extract_batch(items, H, W, decoder, quality, results):
+    frames = _decode_items(items, H, W, decoder)
+    med = temporal_median(frames, [len(it[1]) for it in items])
+    del frames
+    _write_items(items, med, decoder, quality, results)
+
+
+def _extract_batch_sim_cam(items, H, W, decoder, quality, results, size, antialias, avg_method):
+    frames = _decode_items(items, H, W, decoder)
+    crops = resized_crop(frames, np.concatenate([it[3] for it in items]), size, antialias)
+    del frames
+    bg = temporal_nanreduce(crops, [len(it[1]) for it in items], avg_method, zero_is_missing=True)
+    del crops
+    _write_items(items, bg, decoder, quality, results)
+
+
+def extract_background(frame_dir, dest, decoder=None, quality: int = DEFAULT_QUALITY, method: str = 'tmf', avg_method: str = 'median',
+                       interval: int = 1, max_frames: int = SIM_CAM_MAX_FRAMES, size=SIM_CAM_SIZE, antialias: bool = False,
+                       draws=None) -> np.ndarray:
     """``bg_extraction_tmf(data_path, dest)``: the median frame of every file of ``frame_dir``, written to ``dest`` as JPEG;
-    returns it as an ``(H, W, 3)`` uint8 RGB array."""
-    return extract_backgrounds([(str(frame_dir), str(dest))], decoder, quality, return_arrays=True)[0]
+    returns it as an ``(H, W, 3)`` uint8 RGB array.  ``method='sim_cam'``: ``sim_cam_motion_bg_extract`` with the keywords of
+    ``extract_backgrounds``; returns the ``(size_h, size_w, 3)`` image."""
+    return extract_backgrounds([(str(frame_dir), str(dest))], decoder, quality, return_arrays=True, method=method, avg_method=avg_method,
+                               interval=interval, max_frames=max_frames, size=size, antialias=antialias, draws=draws)[0]
 
 
 def bg_file_for(frame_dir: str, bg_dir: pathlib.Path, bg_image_extension: str = '.jpg') -> pathlib.Path:

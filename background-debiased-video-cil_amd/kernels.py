@@ -884,6 +884,47 @@ def bg_resize_crop_u8(bg, size, crop_h, crop_w, top, left):
     return out
 
 
+def resized_crop_f32(frames, boxes, out_h: int, out_w: int, antialias: bool = False):
+    """frames (F,H,W,3) u8 on the device; boxes (F,4) int32 ``[top, left, h, w]`` (host array / tensor) -> (F,out_h,out_w,3) fp32:
+    each frame's box resized as ``F.interpolate(mode='bilinear', align_corners=False, antialias=antialias)`` resizes the float crop
+    (torchvision's ``resized_crop`` of sim_cam_motion_bg_extract, cil_tools/extract_background.py:82)."""
+    _chk(frames, dtype=torch.uint8, name='frames')
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f'resized_crop_f32: expected (F,H,W,3), got {tuple(frames.shape)}')
+    F, H, W, _ = frames.shape
+    hb = torch.as_tensor(boxes).to('cpu', torch.int32).reshape(-1, 4).contiguous()
+    if hb.shape[0] != F:
+        raise ValueError(f'resized_crop_f32: {hb.shape[0]} boxes for {F} frames')
+    out = torch.empty((F, int(out_h), int(out_w), 3), dtype=torch.float32, device=frames.device)
+    db = hb.to(frames.device)
+    check(lib().bdv_resized_crop_f32(_p(frames), F, H, W, _p(db), hb.data_ptr(), int(out_h), int(out_w),
+                                     1 if antialias else 0, _p(out), _stream()), 'bdv_resized_crop_f32')
+    return out
+
+
+def temporal_nanreduce_f32(frames, counts, mode: int = 0, zero_is_missing: bool = True):
+    """frames (sum(counts), ...) fp32 on the device, the videos' frames back to back; counts: frames per video -> (V, ...) uint8:
+    ``np.nanmedian`` (mode 0) / ``np.nanmean`` (mode 1) over each video's frames, ``.astype(np.uint8)``; NaN, and 0 when
+    ``zero_is_missing``, count as missing (cil_tools/extract_background.py:92-98)."""
+    _chk(frames, dtype=torch.float32, name='frames')
+    if frames.dim() < 2:
+        raise ValueError(f'temporal_nanreduce_f32: expected (F, ...), got {tuple(frames.shape)}')
+    counts_h = torch.tensor([int(c) for c in counts], dtype=torch.int32)
+    V = int(counts_h.shape[0])
+    first_h = torch.zeros(V, dtype=torch.int64)
+    first_h[1:] = torch.cumsum(counts_h[:-1], 0)
+    P = 1
+    for d in frames.shape[1:]:
+        P *= int(d)
+    dev = frames.device
+    out = torch.empty((V,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=dev)
+    first_d, counts_d = first_h.to(dev), counts_h.to(dev)
+    check(lib().bdv_temporal_nanreduce_f32(_p(frames), int(frames.shape[0]), _p(first_d), _p(counts_d), first_h.data_ptr(),
+                                           counts_h.data_ptr(), V, P, int(mode), 1 if zero_is_missing else 0, _p(out), _stream()),
+          'bdv_temporal_nanreduce_f32')
+    return out
+
+
 def resize_linear_u8(frames, Hd: int, Wd: int, boxes=None):
     """``cv2.resize(..., INTER_LINEAR)`` of uint8 frames (.., Hs, Ws, 3) -> (.., Hd, Wd, 3).  ``boxes``: None, or for frames of shape
     (B, T, Hs, Ws, 3) a list / (B, 4) array of per-clip crops (x0, y0, w, h) that are cut out and resized in the same pass

@@ -545,6 +545,28 @@ int bdv_jpeg_reconstruct_u8(const short* coefs, const unsigned short* qts, const
  * of the mean of the two middle ones for an even count.  One launch; the frame stack is read twice. */
 int bdv_temporal_median_u8(const uint8_t* frames, int64_t total_frames, const int64_t* first, const int32_t* counts,
                            const int64_t* first_host, const int32_t* counts_host, int V, int H, int W, uint8_t* out, void* stream);
+/* Simulated-camera-motion backgrounds: sim_cam_motion_bg_extract (cil_tools/extract_background.py:78-99) passes every frame, as
+ * a float image, through torchvision's RandomResizedCrop(size=100), sets exact zeros to NaN and takes np.nanmedian / np.nanmean
+ * over time, .astype(np.uint8).
+ *
+ * bdv_resized_crop_f32 (device): frames (F, H, W, 3) uint8; boxes (F, 4) int32 [top, left, h, w] on the device and the same values
+ * on the host in boxes_host (every box is checked against the frame before the launch).  out (F, out_h, out_w, 3) fp32 = the box
+ * of each frame resized as torch.nn.functional.interpolate(mode='bilinear', align_corners=False, antialias=antialias) resizes the
+ * float crop on the CPU: antialias 0 = ATen's 2 x 2 bilinear (source index (dst + 0.5) * scale - 0.5, clamped at 0), 1 = its
+ * separable triangle filter (support widened by the scale when reducing, weights normalised to sum 1, horizontal pass first).
+ * Scales h / out_h and w / out_w are independent; no fused multiply-add.  A pixel whose source pixels are all 0 is exactly 0.0f. */
+int bdv_resized_crop_f32(const uint8_t* frames, int F, int H, int W, const int32_t* boxes, const int32_t* boxes_host, int out_h,
+                         int out_w, int antialias, float* out, void* stream);
+/* bdv_temporal_nanreduce_f32 (device): V stacks of fp32 frames of P elements each, laid out and described as for
+ * bdv_temporal_median_u8 (first / counts on the device and on the host; 1..65535 frames per video).  An element is missing when it
+ * is NaN, or when it is 0 and zero_is_missing is set.  out (V, P) uint8, per position over the n present values: mode 0 = the
+ * median (the middle one for odd n, (a + b) * 0.5f of the two middle ones for even n), mode 1 = the mean (fp32 sum in frame order,
+ * divided by n); the float is truncated to uint8 and saturated to 0..255; n = 0 gives 0.  Exactly np.nanmedian / np.nanmean
+ * (axis 0, float32) followed by .astype(np.uint8).  One launch; the median reads the stack eight times (a radix select on the
+ * floats' bits, most significant nibble first), the mean once. */
+int bdv_temporal_nanreduce_f32(const float* frames, int64_t total_frames, const int64_t* first, const int32_t* counts,
+                               const int64_t* first_host, const int32_t* counts_host, int V, int64_t P, int mode, int zero_is_missing,
+                               uint8_t* out, void* stream);
 /* The encoder's side of the bdv_jpeg_info struct, on the host: geometry of a YCbCr 4:2:0 stream of width x height (the layout
  * bdv_jpeg_entropy_decode produces) and the quantisation tables of jpeg_set_quality(quality) (tables 0 / 1 for Y / CbCr).
  * quality 25..100 (no entry exceeds 255 there, so force_baseline cannot matter); else BDV_EINVAL. */

@@ -8,7 +8,13 @@ job script can give each its own time limit:
     rocprofv3 --kernel-trace --stats --output-format csv -d S -- python tools/bench_background.py --phase kernels --data DIR
     python tools/bench_background.py --phase report  --out R --stats S > profiles/r04_background.txt
 
-The CPU path decodes with Pillow (cv2 is not installed; both run libjpeg-turbo with the same defaults)."""
+The CPU path decodes with Pillow (cv2 is not installed; both run libjpeg-turbo with the same defaults).
+
+``--method sim_cam`` (with ``--avg_method median|mean``) runs the same phases for sim_cam_motion_bg_extract: ``make --frames 121`` writes
+121 files per video, of which the extraction reads 120; ``cpu`` is the restatement (Pillow decode, torch crop + bilinear resize, zeros ->
+NaN, numpy nanmedian / nanmean, Pillow encode) on 16 processes with one torch thread each; ``gpu`` times the stages one by one (host
+read + decode, crop, reduce, encode) and then ``extract_backgrounds`` end to end, and sets the reduce kernel's time against its byte
+model (passes x F x P x 4 bytes at the achievable HBM rate); ``report`` prints both."""
 import argparse
 import glob
 import io
@@ -47,6 +53,80 @@ def _cpu_one(args):
     Image.fromarray(med).save(dest, quality=95)
 
 
+def _cpu_sim_cam(args):
+    d, dest, avg_method, seed = args
+    import warnings
+    import torch
+    import torch.nn.functional as Fn
+    from PIL import Image
+    from bdvcil_amd.background import random_resized_crop_boxes, sim_cam_frame_files
+    torch.set_num_threads(1)
+    files = sim_cam_frame_files(d)
+    boxes = random_resized_crop_boxes(len(files), H, W, draws=seed)
+    crops = []
+    for p, (t, l, h, w) in zip(files, boxes):
+        chw = torch.from_numpy(np.asarray(Image.open(p).convert('RGB'))).permute(2, 0, 1).float()[:, t:t + h, l:l + w].contiguous()
+        crops.append(Fn.interpolate(chw[None], size=(100, 100), mode='bilinear', align_corners=False)[0].permute(1, 2, 0).numpy())
+    stack = np.stack(crops)
+    stack[stack == 0] = np.nan
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)
+        r = (np.nanmedian if avg_method == 'median' else np.nanmean)(stack, axis=0)
+    Image.fromarray(np.nan_to_num(r).astype(np.uint8)).save(dest, quality=95)
+
+
+def _gpu_sim_cam(a):
+    """Stage times of the sim_cam path on the first-listed videos, then the whole call."""
+    import torch
+    from bdvcil_amd import background as BG
+    from bdvcil_amd.decode import JpegDecoder
+    dec = JpegDecoder('cuda', threads=16)
+    vids = _videos(a.data)
+    key = 'gpu_sim_cam_' + a.avg_method
+    BG.extract_backgrounds([(d, os.path.join(a.data, 'bg_gpu_warm', os.path.basename(d) + '.jpg')) for d in vids[:2]], dec, method='sim_cam',
+                           avg_method=a.avg_method, draws=0)                  # library load, kernel load, allocator warm-up
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, time.perf_counter() - t
+
+    files = [BG.sim_cam_frame_files(d) for d in vids]
+    counts = [len(f) for f in files]
+    boxes = np.concatenate([BG.random_resized_crop_boxes(n, H, W, draws=0) for n in counts])
+    streams, t_read = timed(lambda: [p.read_bytes() for f in files for p in f])
+    frames, t_dec = timed(lambda: torch.cat([dec.decode(streams[s:s + 256]) for s in range(0, len(streams), 256)]))
+    crops, t_crop = timed(lambda: BG.resized_crop(frames, boxes, 100, False))
+    bg, t_red = timed(lambda: BG.temporal_nanreduce(crops, counts, a.avg_method))
+    _, t_enc = timed(lambda: BG.encode_jpeg(bg, threads=16))
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    reps = 10
+    ev[0].record()
+    for _ in range(reps):
+        BG.temporal_nanreduce(crops, counts, a.avg_method)
+    ev[1].record()
+    torch.cuda.synchronize()
+    red_ms = ev[0].elapsed_time(ev[1]) / reps
+    ev[0].record()
+    for _ in range(reps):
+        BG.resized_crop(frames, boxes, 100, False)
+    ev[1].record()
+    torch.cuda.synchronize()
+    crop_ms = ev[0].elapsed_time(ev[1]) / reps
+    del frames, crops
+    dest = os.path.join(a.data, 'bg_gpu_sim_cam_' + a.avg_method)
+    _, t_all = timed(lambda: BG.extract_backgrounds([(d, os.path.join(dest, os.path.basename(d) + '.jpg')) for d in vids], dec, method='sim_cam',
+                                                    avg_method=a.avg_method, draws=0))
+    passes = 8 if a.avg_method == 'median' else 1
+    model = passes * sum(counts) * 100 * 100 * 3 * 4
+    res = dict(videos=len(vids), frames=sum(counts), read_s=t_read, decode_s=t_dec, crop_s=t_crop, reduce_s=t_red, encode_s=t_enc,
+               crop_kernel_ms=crop_ms, reduce_kernel_ms=red_ms, reduce_model_bytes=model, reduce_model_ms=model / 6.3e12 * 1e3, seconds=t_all)
+    _record(a.out, key, res)
+    print(key, json.dumps(res))
+
+
 def _videos(data):
     return sorted(glob.glob(os.path.join(data, 'frames', 'v_*')))
 
@@ -62,13 +142,20 @@ def _record(out, key, value):
 
 
 def main():
+    global FRAMES
     ap = argparse.ArgumentParser()
     ap.add_argument('--phase', required=True, choices=['make', 'cpu', 'gpu', 'kernels', 'report'])
     ap.add_argument('--data', default='bench_out/background')
     ap.add_argument('--out', default='bench_out/background.json')
     ap.add_argument('--stats', default=None)
     ap.add_argument('--procs', type=int, default=16)
+    ap.add_argument('--method', default='tmf', choices=['tmf', 'sim_cam'])
+    ap.add_argument('--avg_method', default='median', choices=['median', 'mean'])
+    ap.add_argument('--frames', type=int, default=FRAMES, help='files per video written by --phase make')
     a = ap.parse_args()
+    FRAMES = a.frames
+    if a.method == 'sim_cam' and a.phase in ('cpu', 'gpu', 'report'):
+        return _sim_cam_phase(a)
     frame_bytes, stack = H * W * 3, VIDEOS * FRAMES * H * W * 3
     if a.phase == 'make':
         with ProcessPoolExecutor(a.procs) as ex:
@@ -139,6 +226,37 @@ def main():
                             avg_ns = float(row['AverageNs'])
                             print(f'{k}: {int(row["Calls"])} calls, {avg_ns / 1e3:.1f} us average, {nbytes / 2**20:.1f} MiB moved '
                                   f'(minimum), {nbytes / avg_ns:.0f} GB/s = {nbytes / avg_ns / 8000 * 100:.0f} % of 8 TB/s HBM')
+
+
+def _sim_cam_phase(a):
+    key = 'sim_cam_' + a.avg_method
+    if a.phase == 'cpu':
+        dest = os.path.join(a.data, 'bg_cpu_' + key)
+        os.makedirs(dest, exist_ok=True)
+        jobs = [(d, os.path.join(dest, os.path.basename(d) + '.jpg'), a.avg_method, v) for v, d in enumerate(_videos(a.data))]
+        t = time.perf_counter()
+        with ProcessPoolExecutor(a.procs) as ex:
+            list(ex.map(_cpu_sim_cam, jobs))
+        dt = time.perf_counter() - t
+        _record(a.out, 'cpu_' + key, dict(seconds=dt, videos=len(jobs), procs=a.procs))
+        print(f'cpu {key}: {len(jobs)} videos in {dt:.2f} s on {a.procs} processes ({dt / len(jobs) * 1e3:.1f} ms per video)')
+    elif a.phase == 'gpu':
+        _gpu_sim_cam(a)
+    else:
+        with open(a.out) as f:
+            res = json.load(f)
+        c, g = res.get('cpu_' + key), res.get('gpu_' + key)
+        if c:
+            print(f'{key} cpu restatement (Pillow decode, torch crop + resize, numpy nan-reduce, Pillow encode; {c["procs"]} processes): '
+                  f'{c["seconds"]:.2f} s, {c["seconds"] / c["videos"] * 1e3:.1f} ms per video')
+        if g:
+            print(f'{key} gpu, {g["videos"]} videos / {g["frames"]} frames of {W} x {H}: extract_backgrounds {g["seconds"]:.2f} s '
+                  f'({g["seconds"] / g["videos"] * 1e3:.1f} ms per video); stages: read {g["read_s"] * 1e3:.0f} ms, decode {g["decode_s"] * 1e3:.0f} ms, '
+                  f'crop {g["crop_s"] * 1e3:.1f} ms, reduce {g["reduce_s"] * 1e3:.1f} ms, encode {g["encode_s"] * 1e3:.1f} ms')
+            print(f'{key} kernels (events, 10 launches): crop {g["crop_kernel_ms"]:.3f} ms; reduce {g["reduce_kernel_ms"]:.3f} ms against '
+                  f'{g["reduce_model_ms"]:.3f} ms for {g["reduce_model_bytes"] / 2**30:.2f} GiB at 6.3 TB/s')
+        if c and g:
+            print(f'{key} speed-up end to end: {c["seconds"] / g["seconds"]:.1f}x')
 
 
 if __name__ == '__main__':
