@@ -116,6 +116,8 @@ SIGNATURES = {
     'bdv_bgmix_normalize_u8': (c_int, [P, P, c_int, P, c_float, _F3, _F3, _F3, P, P, c_int, c_int, c_int, c_int, P]),
     'bdv_bg_resize_crop_u8': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, P]),
     'bdv_resize_linear_u8': (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, c_int, c_int, P]),
+    'bdv_resize_linear_ragged_u8': (c_int, [P, c_int64, P, P, c_int, c_int, P, c_int64, P]),
+    'bdv_crop_normalize_ragged_u8': (c_int, [P, c_int64, P, P, P, P, c_int, c_int, c_int, _F3, _F3, P, P, c_int, c_int, P]),
     'bdv_jpeg_parse': (c_int, [P, c_size_t, POINTER(JpegInfo)]),
     'bdv_jpeg_entropy_decode': (c_int, [P, c_size_t, POINTER(JpegInfo), P]),
     'bdv_jpeg_entropy_decode_batch': (c_int, [P, P, c_int, POINTER(JpegInfo), P, P, c_int]),
@@ -167,7 +169,7 @@ class HipExtensionError(RuntimeError):
 
 
 HASHED_SOURCES = ('conv_mfma.hip', 'bn.hip', 'pool_frontend.hip', 'head_loss.hip', 'repr.hip', 'augment.hip', 'optim.hip', 'jpeg.hip',
-                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
+                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'ragged.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
 
 
 def source_hash():

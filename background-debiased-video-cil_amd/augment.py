@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from .decode import RaggedClips
 
 FILL_COLOR = (124, 116, 104)                      # rand_augment.py:15
 
@@ -159,8 +160,26 @@ class RandAugment:
             cur = K.randaug_apply(cur, oi.to(frames_u8.device, non_blocking=True), od.to(frames_u8.device, non_blocking=True))
         return cur
 
-    def __call__(self, frames_u8: torch.Tensor):
+    def ragged(self, clips):
+        """``__call__`` for a ``decode.RaggedClips``: every sample draws with its own (H, W), in sample order; then one
+        ``apply_draws`` per size group on that group's view, the result written back into the packed buffer.  ``last_draws``
+        keeps the per-sample draws."""
+        draws = [self.draw(H, W) for H, W in clips.sizes]
+        self.last_draws = draws
+        for view, rows in zip(clips.groups, clips.layout.rows):
+            sub = [draws[b] for b in rows]
+            if all(d is None for d in sub):
+                continue
+            src = view if view.is_contiguous() else view.contiguous()
+            out = self.apply_draws(src, sub)
+            if out is not src:
+                view.copy_(out)
+        return clips, torch.tensor([d is not None for d in draws], dtype=torch.bool, device=clips.device)
+
+    def __call__(self, frames_u8):
+        if isinstance(frames_u8, RaggedClips):
+            return self.ragged(frames_u8)
         B, T, H, W, _ = frames_u8.shape
-        draws = [self.draw(H, W) for _ in range(B)]
+        draws = self.last_draws = [self.draw(H, W) for _ in range(B)]
         flags = torch.tensor([d is not None for d in draws], dtype=torch.bool, device=frames_u8.device)
         return self.apply_draws(frames_u8, draws), flags

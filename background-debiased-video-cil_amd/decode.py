@@ -39,11 +39,12 @@ def jpeg_entropy_decode(data: bytes, info: JpegInfo = None, out: np.ndarray = No
 
 
 class JpegDecoder:
-    """Batched decode of equal-geometry JPEG streams (the frames of a rawframe dataset share one size and sampling).
+    """Batched decode of JPEG streams (the frames of the UCF101 rawframe dataset share one size and sampling; those of HMDB51 and
+    Something-Something-v2 differ in width from video to video).
 
     ``decode(streams) -> (N, H, W, 3) uint8`` on ``device``; ``decode_clips(clips) -> (B, T, H, W, 3)``.  Streams of different
     geometry in one call are decoded group by group and must then share ``(H, W)`` (else ``ValueError``: a batch tensor needs one
-    size -- resize first, as the reference's pipeline does per sample)."""
+    size).  ``decode_clips_ragged(clips) -> RaggedClips`` takes clips of different sizes: one packed buffer, size group by size group."""
 
     def __init__(self, device='cuda', threads: int = 8):
         self.device = torch.device(device)
@@ -98,7 +99,8 @@ class JpegDecoder:
             out[torch.as_tensor(idx, device=self.device)] = rgb
         return out
 
-    def _decode_group(self, streams: List[bytes], infos: List[JpegInfo]) -> torch.Tensor:
+    def _decode_group(self, streams: List[bytes], infos: List[JpegInfo], out: torch.Tensor = None) -> torch.Tensor:
+        """``out``: a contiguous (n, H, W, 3) uint8 tensor on the device to decode into (a size group's slice of a packed buffer)."""
         n, info = len(streams), infos[0]
         coefs, qts, done = self._staging(n * info.coef_count, n * 192)
         coefs, qts = coefs[:n * info.coef_count].view(n, info.coef_count), qts[:n * 192].view(n, 3, 64)
@@ -109,8 +111,11 @@ class JpegDecoder:
         coefs_d, qts_d = coefs.to(self.device, non_blocking=True), qts.to(self.device, non_blocking=True)
         ws_bytes = lib().bdv_jpeg_workspace_bytes(ctypes.byref(info), n)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        rgb = torch.empty(n, info.height, info.width, 3, dtype=torch.uint8, device=self.device)
-        from .kernels import _p, _stream
+        from .kernels import _chk, _p, _stream
+        if out is None:
+            rgb = torch.empty(n, info.height, info.width, 3, dtype=torch.uint8, device=self.device)
+        else:
+            rgb = _chk(out, (n, info.height, info.width, 3), torch.uint8, 'out')
         check(lib().bdv_jpeg_reconstruct_u8(_p(coefs_d), _p(qts_d), ctypes.byref(info), n, _p(ws), ws_bytes, _p(rgb), _stream()),
               'bdv_jpeg_reconstruct_u8')
         if done is not None:
@@ -125,6 +130,156 @@ class JpegDecoder:
         flat = [s for c in clips for s in c]
         rgb = self.decode(flat)
         return rgb.view(len(clips), T, *rgb.shape[1:])
+
+    def decode_clips_ragged(self, clips: Sequence[Sequence[bytes]]) -> 'RaggedClips':
+        """``clips``: B lists of T streams each, the sizes differing from clip to clip (not inside one) -> ``RaggedClips``.  Each size
+        group is decoded by the two kernels of ``decode`` straight into its dense slice of the packed buffer (JPEG geometry by
+        geometry when a size group mixes samplings).  As in ``decode``, only one header per clip is parsed in Python: the batch
+        call checks every other frame against it, and only a clip whose frames disagree is parsed stream by stream."""
+        if len(clips) == 0:
+            raise ValueError('JpegDecoder.decode_clips_ragged: empty batch')
+        T = len(clips[0])
+        if T == 0 or any(len(c) != T for c in clips):
+            raise ValueError('JpegDecoder.decode_clips_ragged: clips of different lengths')
+        first = [jpeg_parse(c[0]) for c in clips]
+        out = RaggedClips(RaggedLayout([(inf.height, inf.width) for inf in first], T), device=self.device)
+        for g, rows in enumerate(out.layout.rows):
+            H, W = out.layout.groups[g]
+            geo = {}
+            for r, b in enumerate(rows):
+                geo.setdefault(first[b].geometry_key(), []).append(r)
+            dense = out.group_frames(g)            # None when the group's clips are padded apart
+            tmp = dense if dense is not None else torch.empty(len(rows) * T, H, W, 3, dtype=torch.uint8, device=self.device)
+            for rs in geo.values():
+                streams = [s for r in rs for s in clips[rows[r]]]
+                into = tmp if len(geo) == 1 else None
+                try:
+                    rgb = self._decode_group(streams, [first[rows[rs[0]]]], out=into)
+                except RuntimeError as e:
+                    if 'does not have the geometry' not in str(e):
+                        raise
+                    rgb = self._decode_one_size(streams, H, W, [rows[r] for r in rs], T, into)
+                if into is None:
+                    tmp.view(len(rows), T, H, W, 3)[torch.as_tensor(rs, device=self.device)] = rgb.view(len(rs), T, H, W, 3)
+            if dense is None:
+                out.groups[g].copy_(tmp.view(len(rows), T, H, W, 3))
+        return out
+
+    def _decode_one_size(self, streams: List[bytes], H: int, W: int, samples: List[int], T: int, out: torch.Tensor = None) -> torch.Tensor:
+        """The clips ``samples`` (T streams each) whose frames do not all have their first frame's geometry: JPEG geometry by
+        geometry, as long as every frame is H x W."""
+        infos, groups = self._group(streams)
+        for k, inf in enumerate(infos):
+            if (inf.height, inf.width) != (H, W):
+                raise ValueError(f'JpegDecoder.decode_clips_ragged: clip {samples[k // T]} has frames of different sizes: '
+                                 f'{sorted({(H, W), (inf.height, inf.width)})}')
+        rgb = out if out is not None else torch.empty(len(streams), H, W, 3, dtype=torch.uint8, device=self.device)
+        for idx in groups.values():
+            rgb[torch.as_tensor(idx, device=self.device)] = self._decode_group([streams[i] for i in idx], [infos[i] for i in idx])
+        return rgb
+
+
+RAGGED_ALIGN = 256      # every clip of a packed buffer starts at a multiple of this many bytes
+
+
+class RaggedLayout:
+    """Where the clips of a mixed-size batch lie in one packed uint8 buffer (host-side plan, no GPU): size group by size group in
+    order of first appearance, the clips of a group in sample order, ``clip_stride[g]`` bytes apart (the clip's ``T * H * W * 3``
+    bytes rounded up to ``align``, so that every clip starts aligned).
+
+      ``sizes[b] = (H, W)``    ``groups[g] = (H, W)``    ``rows[g]`` = the samples of group g    ``where[b] = (g, row)``
+      ``group_offsets[g]``, ``offsets[b]``: byte offsets    ``nbytes``: size of the buffer"""
+
+    def __init__(self, sizes, T: int, align: int = RAGGED_ALIGN):
+        self.T, self.align = int(T), int(align)
+        self.sizes = [(int(h), int(w)) for h, w in sizes]
+        if self.T <= 0 or not self.sizes or any(h <= 0 or w <= 0 for h, w in self.sizes):
+            raise ValueError(f'RaggedLayout: needs T > 0 and positive frame sizes, got T = {T}, sizes = {self.sizes}')
+        self.groups, self.rows, index = [], [], {}
+        for b, hw in enumerate(self.sizes):
+            if hw not in index:
+                index[hw] = len(self.groups)
+                self.groups.append(hw)
+                self.rows.append([])
+            self.rows[index[hw]].append(b)
+        self.group_offsets, self.clip_stride = [], []
+        self.offsets, self.where = [0] * len(self.sizes), [None] * len(self.sizes)
+        off = 0
+        for g, (h, w) in enumerate(self.groups):
+            stride = -(-(self.T * h * w * 3) // self.align) * self.align
+            self.group_offsets.append(off)
+            self.clip_stride.append(stride)
+            for r, b in enumerate(self.rows[g]):
+                self.offsets[b], self.where[b] = off + r * stride, (g, r)
+            off += len(self.rows[g]) * stride
+        self.nbytes = off
+
+    def clip_bytes(self, b: int) -> int:
+        return self.T * self.sizes[b][0] * self.sizes[b][1] * 3
+
+    def table(self) -> np.ndarray:
+        """(B, 3) int64 rows (byte offset, H, W): the per-clip source descriptor of ``bdv_crop_normalize_ragged_u8``."""
+        return np.array([[o, h, w] for o, (h, w) in zip(self.offsets, self.sizes)], dtype=np.int64)
+
+
+def plan_resize_stage(src: RaggedLayout, out_sizes=None, boxes=None, uniform=None):
+    """Plans one resize stage over a packed buffer on the host: the descriptor table of ``bdv_resize_linear_ragged_u8`` and the
+    layout of what it writes.  ``out_sizes``: per-sample ``(Hd, Wd)`` -> the destination is a second packed buffer (``Resize(-1, S)``);
+    ``uniform = (Hd, Wd)`` -> the destination is the dense ``(B, T, Hd, Wd, 3)`` tensor in sample order (MultiScaleCrop + Resize).
+    ``boxes``: per-sample ``(x0, y0, w, h)`` inside the source frame, default the whole frame.  Returns ``(dst_layout | None,
+    table (B, 10) int64)``; the rows are validated by the library at the launch, not here."""
+    B = len(src.sizes)
+    if (out_sizes is None) == (uniform is None):
+        raise ValueError('plan_resize_stage: give either per-sample out_sizes or one uniform size')
+    if boxes is None:
+        boxes = [(0, 0, w, h) for h, w in src.sizes]
+    if len(boxes) != B or (out_sizes is not None and len(out_sizes) != B):
+        raise ValueError(f'plan_resize_stage: {B} clips, {len(boxes)} boxes, {len(out_sizes) if out_sizes is not None else B} output sizes')
+    if uniform is not None:
+        dst, hd, wd = None, int(uniform[0]), int(uniform[1])
+        dst_sizes, dst_offsets = [(hd, wd)] * B, [b * src.T * hd * wd * 3 for b in range(B)]
+    else:
+        dst = RaggedLayout(out_sizes, src.T, src.align)
+        dst_sizes, dst_offsets = dst.sizes, dst.offsets
+    table = np.empty((B, 10), dtype=np.int64)
+    for b in range(B):
+        table[b] = (src.offsets[b], *src.sizes[b], *(int(v) for v in boxes[b]), dst_offsets[b], *dst_sizes[b])
+    return dst, table
+
+
+class RaggedClips:
+    """Clips of different sizes on the device: ``buffer`` (``layout.nbytes`` uint8) laid out by ``layout`` (a ``RaggedLayout``), and
+    ``groups[g]``: the ``(n_g, T, H_g, W_g, 3)`` view of size group g that the per-size kernels (decode, RandAugment) take.  A group's
+    view is contiguous when its clips need no padding between them (``T * H * W * 3`` a multiple of the alignment -- 240-high frames
+    of even width -- or a single clip); otherwise it is a strided view and ``group_frames`` / ``dense`` say so."""
+
+    def __init__(self, layout: RaggedLayout, buffer: torch.Tensor = None, device='cuda'):
+        self.layout = layout
+        if buffer is None:
+            buffer = torch.empty(layout.nbytes, dtype=torch.uint8, device=device)
+        if buffer.dtype != torch.uint8 or buffer.dim() != 1 or buffer.numel() != layout.nbytes or not buffer.is_contiguous():
+            raise ValueError(f'RaggedClips: the buffer must be {layout.nbytes} contiguous uint8 values')
+        self.buffer = buffer
+        T = layout.T
+        self.groups = [buffer.as_strided((len(rows), T, h, w, 3), (stride, h * w * 3, w * 3, 3, 1), buffer.storage_offset() + off)
+                       for (h, w), rows, stride, off in zip(layout.groups, layout.rows, layout.clip_stride, layout.group_offsets)]
+
+    T = property(lambda self: self.layout.T)
+    sizes = property(lambda self: self.layout.sizes)
+    device = property(lambda self: self.buffer.device)
+
+    def __len__(self) -> int:
+        return len(self.layout.sizes)
+
+    def clip(self, b: int) -> torch.Tensor:
+        """The ``(T, H, W, 3)`` view of sample b."""
+        g, r = self.layout.where[b]
+        return self.groups[g][r]
+
+    def group_frames(self, g: int):
+        """Group g as contiguous ``(n_g * T, H, W, 3)`` frames, or None when its clips are padded apart."""
+        v = self.groups[g]
+        return v.view(-1, *v.shape[2:]) if v.is_contiguous() else None
 
 
 def rescale_size(w: int, h: int, scale) -> Tuple[int, int]:
@@ -217,13 +372,20 @@ class RawFrameClipLoader:
     ``with_randAug=False`` with ``prob <= 0``) reads no background file and makes no background draw.
 
     ``seed``: ``None`` = every draw goes to the process-global generators, in the order given above; an int (or a ``Draws``) = the loader
-    owns its generators (see ``Draws``) and passes them to every stage it builds, and to a ``randAug`` it was given."""
+    owns its generators (see ``Draws``) and passes them to every stage it builds, and to a ``randAug`` it was given.
+
+    ``ragged``: a batch whose clips share one size (every UCF101 batch) runs on dense ``(B, T, H, W, 3)`` tensors.  A batch that mixes
+    sizes (HMDB51, Something-Something-v2: 240 high, the width differs per video) runs the same stages over packed buffers
+    (``RaggedClips``): decode per size group, ``Resize`` in one launch, RandAugment drawn per sample in sample order and applied per
+    size group, then MultiScaleCrop + Resize (train) or crop + Normalize (eval) in one launch into the uniform batch -- the same
+    arithmetic and the same draws in the same order.  ``'auto'`` (default) picks by the batch; ``'always'`` sends every batch through the
+    packed path (same bits on a same-size batch; for tests)."""
 
     def __init__(self, device='cuda', filename_tmpl: str = 'img_{:05}.jpg', num_segments: int = 8, start_index: int = 1,
                  short_edge: int = 256, input_size: int = 224, randAug=None, randAug_prob: float = 0.75, alpha: float = 0.5,
                  multi_scale_crop: dict = None, bg_files: Sequence[str] = None, bg_video_infos: Sequence[dict] = None,
                  bg_resize: int = 256, test_crop=('TenCrop', 256), threads: int = 8, with_randAug: bool = True, prob: float = 0.25,
-                 bg_mix: bool = True, seed=None):
+                 bg_mix: bool = True, seed=None, ragged: str = 'auto'):
         from .augment import RandAugment
         from .frontend import BackgroundCropFrontEnd, BackgroundMixFrontEnd, CropFrontEnd, MultiScaleCropResize, TrainClipFrontEnd
         self.device = torch.device(device)
@@ -246,6 +408,9 @@ class RawFrameClipLoader:
         self.test = CropFrontEnd(*test_crop)
         self.bg_files, self.bg_video_infos = (list(bg_files) if bg_files else None), bg_video_infos
         self.input_size = int(input_size)
+        if ragged not in ('auto', 'always'):
+            raise ValueError(f"RawFrameClipLoader: ragged must be 'auto' or 'always', got {ragged!r}")
+        self.ragged = ragged
 
     def set_bg_files(self, bg_files: Sequence[str]) -> None:
         """The background list of the dataset being trained on (``CILTaskLoop`` calls this before each fit when the config names
@@ -257,14 +422,33 @@ class RawFrameClipLoader:
         with open(path, 'rb') as f:
             return f.read()
 
-    def _frames(self, video_infos: List[dict], test_mode: bool):
+    def _clips(self, video_infos: List[dict], test_mode: bool):
+        """The sampled frame numbers (B, T) and their files' bytes, B lists of T streams."""
         import os.path as osp
         inds = [sample_frames(int(v['total_frames']), self.T, test_mode=test_mode, start_index=self.start_index, draws=self.draws)
                 for v in video_infos]
         paths = [osp.join(v['frame_dir'], self.tmpl.format(int(i))) for v, ii in zip(video_infos, inds) for i in ii]
         streams = list(self.decoder.pool.map(self._read, paths))
         clips = [streams[k * self.T:(k + 1) * self.T] for k in range(len(video_infos))]
-        return self.decoder.decode_clips(clips), np.stack(inds)
+        return clips, np.stack(inds)
+
+    def _resized(self, clips) -> torch.Tensor:
+        """decode + ``Resize(-1, short_edge)`` of a batch whose clips share one size: (B, T, Hr, Wr, 3)."""
+        from . import kernels as K
+        frames = self.decoder.decode_clips(clips)
+        H, W = int(frames.shape[2]), int(frames.shape[3])
+        Wr, Hr = rescale_size(W, H, (-1, self.short_edge))
+        return K.resize_linear_u8(frames, Hr, Wr)
+
+    def _resized_ragged(self, clips) -> RaggedClips:
+        """The same two stages for clips of different sizes: a packed buffer in, one launch, a second packed buffer out."""
+        from . import kernels as K
+        src = self.decoder.decode_clips_ragged(clips)
+        out_sizes = [rescale_size(w, h, (-1, self.short_edge))[::-1] for h, w in src.sizes]
+        layout, table = plan_resize_stage(src.layout, out_sizes=out_sizes)
+        dst = RaggedClips(layout, device=self.device)
+        K.resize_linear_ragged_u8(src.buffer, table, src.T, dst.buffer)
+        return dst
 
     def _backgrounds(self, B: int, video_infos: List[dict]) -> torch.Tensor:
         """One background per sample, cropped: (B, S, S, 3) fp32 pixel values (only the mixed samples' rows are read)."""
@@ -290,11 +474,13 @@ class RawFrameClipLoader:
 
     def __call__(self, video_infos: List[dict], phase: str):
         B = len(video_infos)
-        frames, inds = self._frames(video_infos, test_mode=phase != 'train')
-        H, W = int(frames.shape[2]), int(frames.shape[3])
-        Wr, Hr = rescale_size(W, H, (-1, self.short_edge))
-        from . import kernels as K
-        frames = K.resize_linear_u8(frames, Hr, Wr)
+        clips, inds = self._clips(video_infos, test_mode=phase != 'train')
+        # clips of one size (every UCF101 batch) take the dense path; a batch that mixes sizes goes through packed buffers, the
+        # stages below taking either form.  A clip's size is its first frame's (sizes do not differ inside a video)
+        if self.ragged == 'always' or len({(i.height, i.width) for i in (jpeg_parse(c[0]) for c in clips)}) > 1:
+            frames = self._resized_ragged(clips)
+        else:
+            frames = self._resized(clips)
         extra = {}
         if phase == 'train':
             bg = None if self.train_front.never_mixes() else self._backgrounds(B, video_infos)

@@ -12,6 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import kernels as K
+from .decode import RaggedClips, plan_resize_stage
 from .resnet_tsm import Nhwc4Frames
 
 IMG_MEAN = (123.675, 116.28, 103.53)
@@ -103,8 +104,9 @@ class TrainClipFrontEnd:
             return self.randaug is not None and self.randaug.prob >= 1
         return self.prob <= 0
 
-    def decide(self, frames_u8: torch.Tensor):
-        B = frames_u8.shape[0]
+    def decide(self, frames_u8):
+        """``frames_u8``: (B, T, H, W, 3), or a ``RaggedClips`` (RandAugment then draws all samples first, in sample order)."""
+        B = len(frames_u8)
         if not self.bg_mix:
             if self.randaug is None:
                 return frames_u8, torch.zeros(B, dtype=torch.bool, device=frames_u8.device), None
@@ -125,6 +127,8 @@ class TrainClipFrontEnd:
         frames_u8, rand_flags, mixed = self.decide(frames_u8)
         if self.crop_resize is not None:
             frames_u8, bg_u8 = self.crop_resize(frames_u8, bg_u8)
+        if isinstance(frames_u8, RaggedClips):
+            raise ValueError('TrainClipFrontEnd: clips of different sizes need a crop_resize stage that brings them to one size')
         if mixed is None or bg_u8 is None:        # nothing to blend (``never_mixes``): Normalize alone
             bg_u8 = mixed = None
         out = self.mix.as_nchw(frames_u8, bg_u8, mixed) if as_nchw else self.mix(frames_u8, bg_u8, mixed)
@@ -170,6 +174,11 @@ class CropFrontEnd:
         crop_offsets(kind, self.crop_h, self.crop_w, self.crop_h, self.crop_w)      # validates `kind` early
 
     def _run(self, frames_u8, nhwc4: bool):
+        if isinstance(frames_u8, RaggedClips):      # the offsets follow each clip's own size
+            crops = [crop_offsets(self.kind, H, W, self.crop_h, self.crop_w) for H, W in frames_u8.sizes]
+            o4, oc = K.crop_normalize_ragged_u8(frames_u8.buffer, frames_u8.layout.table(), frames_u8.T, crops, self.crop_h, self.crop_w,
+                                                self.mean, self.std, nhwc4, not nhwc4)
+            return (o4, oc, len(frames_u8), len(crops[0]) * frames_u8.T)
         B, T, H, W, _ = frames_u8.shape
         crops = crop_offsets(self.kind, H, W, self.crop_h, self.crop_w)
         o4, oc = K.crop_normalize_u8(frames_u8, crops, self.crop_h, self.crop_w, self.mean, self.std, nhwc4, not nhwc4)
@@ -220,7 +229,14 @@ class MultiScaleCropResize:
         x, y = random.choice(offs)
         return x, y, cw, ch
 
-    def __call__(self, frames_u8: torch.Tensor, bg=None, boxes=None):
+    def __call__(self, frames_u8, bg=None, boxes=None):
+        if isinstance(frames_u8, RaggedClips):      # one box per sample from its own (W, H), in sample order; one launch
+            if boxes is None:
+                boxes = [self.draw(W, H) for H, W in frames_u8.sizes]
+            self.last_boxes = boxes
+            _, table = plan_resize_stage(frames_u8.layout, boxes=boxes, uniform=(self.out_size[1], self.out_size[0]))
+            out = torch.empty(len(frames_u8), frames_u8.T, self.out_size[1], self.out_size[0], 3, dtype=torch.uint8, device=frames_u8.device)
+            return K.resize_linear_ragged_u8(frames_u8.buffer, table, frames_u8.T, out), bg
         B, _, H, W, _ = frames_u8.shape
         if boxes is None:
             boxes = [self.draw(W, H) for _ in range(B)]

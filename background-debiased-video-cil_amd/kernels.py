@@ -971,6 +971,49 @@ def crop_normalize_u8(frames, crops, crop_h, crop_w, mean, std, want_nhwc4=True,
     return o4, oc
 
 
+def _host_table(table, cols: int, dtype, name: str) -> torch.Tensor:
+    t = torch.as_tensor(table, dtype=dtype).contiguous()
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError(f'{name}: expected a (clips, {cols}) table, got {tuple(t.shape)}')
+    return t
+
+
+def resize_linear_ragged_u8(src, table, T: int, dst):
+    """``bdv_resize_linear_ragged_u8``: ``cv2.resize(..., INTER_LINEAR)`` of clips of different sizes in one launch.  ``src`` / ``dst``:
+    contiguous uint8 device tensors (a packed buffer of ``decode.RaggedClips``, or the uniform (B, T, S, S, 3) tensor); ``table``: host
+    (clips, 10) int64 rows (source byte offset, Hs, Ws, x0, y0, w, h, destination byte offset, Hd, Wd) as ``decode.plan_resize_stage``
+    writes them, validated by the library before the launch.  Returns ``dst``."""
+    _chk(src, dtype=torch.uint8, name='src')
+    _chk(dst, dtype=torch.uint8, name='dst')
+    host = _host_table(table, 10, torch.int64, 'resize_linear_ragged_u8')
+    dev = host.to(src.device)
+    check(lib().bdv_resize_linear_ragged_u8(_p(src), src.numel(), _p(dev), host.data_ptr(), int(host.shape[0]), int(T), _p(dst), dst.numel(),
+                                            _stream()), 'bdv_resize_linear_ragged_u8')
+    return dst
+
+
+def crop_normalize_ragged_u8(src, clips, T: int, crops, crop_h, crop_w, mean, std, want_nhwc4=True, want_nchw=False):
+    """``crop_normalize_u8`` for clips of different sizes in a packed uint8 buffer ``src``: ``clips`` host (B, 3) int64 rows (byte
+    offset, H, W); ``crops`` (B, n, 3): per clip [(x_offset, y_offset, flip), ...] -> (o4 (B*n*T, ch, cw, 4) | None,
+    oc (B, n*T, 3, ch, cw) | None), crop-major frame order."""
+    _chk(src, dtype=torch.uint8, name='src')
+    hc = _host_table(clips, 3, torch.int64, 'crop_normalize_ragged_u8')
+    B = int(hc.shape[0])
+    hk = torch.as_tensor(crops, dtype=torch.int32).contiguous()
+    if hk.dim() != 3 or hk.shape[0] != B or hk.shape[2] != 3:
+        raise ValueError(f'crop_normalize_ragged_u8: crops must be ({B}, n, 3), got {tuple(hk.shape)}')
+    n = int(hk.shape[1])
+    f3 = ctypes.c_float * 3
+    m = torch.tensor(list(mean), dtype=torch.float32)
+    inv = 1.0 / torch.tensor(list(std), dtype=torch.float32)      # fp32 reciprocal, as in crop_normalize_u8
+    o4 = torch.empty((B * n * T, crop_h, crop_w, 4), dtype=torch.float32, device=src.device) if want_nhwc4 else None
+    oc = torch.empty((B, n * T, 3, crop_h, crop_w), dtype=torch.float32, device=src.device) if want_nchw else None
+    dc, dk = hc.to(src.device), hk.to(src.device)
+    check(lib().bdv_crop_normalize_ragged_u8(_p(src), src.numel(), _p(dc), hc.data_ptr(), _p(dk), hk.data_ptr(), n, int(crop_h), int(crop_w),
+                                             f3(*m.tolist()), f3(*inv.tolist()), _p(o4), _p(oc), B, int(T), _stream()),
+          'bdv_crop_normalize_ragged_u8')
+    return o4, oc
+
 
 def actor_cut_mix_u8(actor, scene, plan, nclips: int, out, mean, std):
     """ActorCutMix composite + Normalize (``bdv_actor_cut_mix_u8``): actor (n_actor, T, Ha, Wa, 3) / scene (n_scene, T, Hs, Ws, 3) | None

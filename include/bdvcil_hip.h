@@ -499,6 +499,28 @@ int bdv_randaug_apply(const uint8_t* in, uint8_t* out, const int32_t* op_i, cons
 int bdv_resize_linear_u8(const uint8_t* src, int N, int Hs, int Ws, const int32_t* boxes, int frames_per_box,
                          const int32_t* boxes_host, uint8_t* dst, int Hd, int Wd, void* stream);
 
+/* The same stages for a batch whose clips differ in size (configs/HMDB51/bgmix_seed_1000_inc_5_stages_bgmix_plus_randAug.py:125
+ * Resize(-1, 256), :128-134 MultiScaleCrop + Resize(224, 224), :143-144 / :175-176 Resize + CenterCrop, :159-162 Resize + TenCrop;
+ * configs/sth-sthv2/seed_1000_inc_9_stages_bgmix_plus_randAug.py:131, :134-140, :149-150, :166-167, :182-183; the reference runs
+ * them per sample in its DataLoader workers, so a batch never holds two sizes there).  The clips lie in one packed byte buffer, T consecutive (H, W, 3) uint8 frames each.
+ * bdv_resize_linear_ragged_u8: one launch for the whole batch, per output pixel exactly bdv_resize_linear_u8.  table: nclips rows of
+ * BDV_RAGGED_RESIZE_COLS int64 -- source byte offset, Hs, Ws, box x0, y0, w, h (the whole frame: 0, 0, Ws, Hs), destination byte
+ * offset, Hd, Wd -- on the device (read by the kernel) AND on the host, where every row is validated before the launch: the box inside
+ * its frame, both byte ranges inside their buffers (src_bytes, dst_bytes), the destination ranges of different clips disjoint, clip
+ * starts 16-byte aligned (frames inside a clip need not be).  The destination is a second packed buffer (Resize: Hd, Wd differ per
+ * clip) or the uniform (nclips, T, S, S, 3) tensor (destination offsets clip * T * S * S * 3). */
+#define BDV_RAGGED_RESIZE_COLS 10
+int bdv_resize_linear_ragged_u8(const uint8_t* src, int64_t src_bytes, const int64_t* table, const int64_t* table_host, int nclips,
+                                int T, uint8_t* dst, int64_t dst_bytes, void* stream);
+/* bdv_crop_normalize_u8 over such a buffer: clips = B rows (byte offset, H, W) int64, crops = (B, ncrops, (x_offset, y_offset, flip))
+ * int32 -- the offsets of CenterCrop / ThreeCrop / FiveCrop / TenCrop depend on each clip's size -- both on the device AND on the host
+ * (byte ranges and crops validated before the launch).  Outputs as bdv_crop_normalize_u8: out_nhwc4 (B*ncrops*T, crop_h, crop_w, 4)
+ * and/or out_nchw (B, ncrops*T, 3, crop_h, crop_w), crop-major, values (x-mean)*inv_std. */
+int bdv_crop_normalize_ragged_u8(const uint8_t* src, int64_t src_bytes, const int64_t* clips, const int64_t* clips_host,
+                                 const int32_t* crops, const int32_t* crops_host, int ncrops, int crop_h, int crop_w,
+                                 const float mean[3], const float inv_std[3], float* out_nhwc4, float* out_nchw, int B, int T,
+                                 void* stream);
+
 /* ---- JPEG frame decode ----------------------------------------------
  * The first stage of every pipeline of the configs: RawFrameDecode (configs/ucf101/bgmix_plus_randAug/
  * bgmix_seed_1000_inc_10_stages_bgmix_plus_randAug.py:126, :144, :160; UPSTREAM mmaction2 RawFrameDecode ->
