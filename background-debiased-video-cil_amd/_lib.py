@@ -8,14 +8,14 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint16, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint16, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BDVCIL_LIB_PATH: load another build of the library (A/B runs of two kernel versions in one gpurun call); the source-hash check
 # is then the caller's business
 _OVERRIDE = os.environ.get('BDVCIL_LIB_PATH')
 LIB_PATH = _OVERRIDE or os.path.join(_HERE, 'csrc', 'libbdvcil_hip.so')
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 _lib = None
 
@@ -27,6 +27,11 @@ class ConvGeom(Structure):
 
     def key(self):
         return tuple(getattr(self, n) for n, _ in self._fields_)
+
+
+class ConvPlan(Structure):
+    """Mirror of ``bdv_conv_plan``: what ``bdv_conv_plan_query`` answers for one call."""
+    _fields_ = [(n, c_int32) for n in ('family', 'reads_planes', 'stat_rows', 'splits', 'pre_ok')] + [('kernel', c_char * 128)]
 
 
 P = c_void_p
@@ -60,29 +65,16 @@ SIGNATURES = {
     'bdv_abi_version': (c_int, []),
     'bdv_source_hash': (c_char_p, []),
     'bdv_conv_workspace_bytes': (c_size_t, [POINTER(ConvGeom), c_int]),
-    'bdv_conv_fprop_stat_rows': (c_int, [POINTER(ConvGeom)]),
+    'bdv_conv_plan_query': (c_int, [POINTER(ConvGeom), c_int, c_int, c_int, POINTER(ConvPlan)]),
     'bdv_conv_fprop': (c_int, [P, P, P, POINTER(ConvGeom), P, POINTER(ConvAffine), P, c_size_t, P]),
-    'bdv_conv_fprop_x3': (c_int, [P, P, P, POINTER(ConvGeom), P, POINTER(ConvAffine), P, c_size_t, P]),
-    'bdv_conv_dgrad_stat_rows': (c_int, [POINTER(ConvGeom)]),
     'bdv_conv_dgrad': (c_int, [P, P, P, P, P, POINTER(ConvGeom), POINTER(BnStatFuse), P, c_size_t, P]),
-    'bdv_conv_dgrad_x3': (c_int, [P, P, P, P, P, P, POINTER(ConvGeom), POINTER(BnStatFuse), P, c_size_t, P]),
     'bdv_conv_weight_planes_bytes': (c_size_t, [POINTER(ConvGeom)]),
     'bdv_conv_split_weights': (c_int, [P, POINTER(ConvGeom), P, P, P]),
-    'bdv_conv_fprop_pre_ok': (c_int, [POINTER(ConvGeom)]),
-    'bdv_conv_fprop_pre_stat_rows': (c_int, [POINTER(ConvGeom)]),
-    'bdv_conv_wgrad_pre_ok': (c_int, [POINTER(ConvGeom)]),
     'bdv_conv_debug_force_tile': (c_int, [c_int]),
-    'bdv_conv_uses_planes': (c_int, [POINTER(ConvGeom), c_int, c_int]),
-    'bdv_conv_kernel_name': (c_int, [POINTER(ConvGeom), c_int, c_int, c_char_p, c_size_t]),
-    'bdv_conv_fprop_pl_stat_rows': (c_int, [POINTER(ConvGeom), c_int]),
-    'bdv_conv_dgrad_pl_stat_rows': (c_int, [POINTER(ConvGeom), c_int]),
     'bdv_conv_fprop_pl': (c_int, [P, P, P, P, POINTER(ConvGeom), P, POINTER(ConvAffine), P, c_size_t, c_int, P, P, P]),
     'bdv_conv_dgrad_pl': (c_int, [P, P, P, P, P, P, POINTER(ConvGeom), POINTER(BnStatFuse), P, c_size_t, c_int, P]),
     'bdv_conv_wgrad': (c_int, [P, P, P, c_float, POINTER(ConvGeom), P, c_size_t, P]),
-    'bdv_conv_wgrad_splits': (c_int, [POINTER(ConvGeom)]),
     'bdv_conv_wgrad_partial': (c_int, [P, P, POINTER(ConvGeom), P, c_size_t, P]),
-    'bdv_conv_wgrad_partial_x3': (c_int, [P, P, POINTER(ConvGeom), P, c_size_t, P]),
-    'bdv_conv_wgrad_pl_splits': (c_int, [POINTER(ConvGeom)]),
     'bdv_conv_wgrad_partial_pl': (c_int, [P, P, POINTER(ConvGeom), P, c_size_t, c_int, P, P, P]),
     'bdv_wgrad_reduce_batched': (c_int, [P, P, P, P, c_int, c_float, P]),
     'bdv_bn_workspace_bytes': (c_size_t, [c_int64, c_int]),

@@ -19,6 +19,7 @@
 // instruction adds its issue cycles: utilisation ~ 64 / (64 + 4 * VALU-per-MFMA + 10)), hence the emphasis on
 // address arithmetic that folds into immediates or is carried incrementally.
 #include <stdlib.h>
+#include <string.h>
 #include "common.h"
 
 // ---- in-kernel time stamps (diagnostic builds only: make stamps -> libbdvcil_hip_stamps.so, tools/stamp_tiles.py) --------------
@@ -732,8 +733,6 @@ __global__ __launch_bounds__(256, 3) void conv_fprop_kernel(const float* __restr
 // to LDS as k-contiguous rows, and each 16-deep step accumulates the six piece products of relative weight >= 2^-16 with
 // v_mfma_f32_32x32x16_bf16 (smallest first).  The dropped products are below 2^-24 relative, the order of fp32 rounding.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 constexpr int X3_LDK = BK + 8;  // bf16 per LDS row: 80 bytes, the 16-byte fragment reads of 16 lanes cover all banks once
 
 // fp32 x 4 -> three bf16 pieces each, as packed pairs (x, y) and (z, w).  Written on pairs so that one v_cvt_pk_bf16_f32
@@ -924,75 +923,6 @@ __global__ __launch_bounds__(256, 2) void conv_fprop_x3_kernel(const float* __re
     return;
   }
   fprop_epilogue<BM, BN, WM, WN>(acc, smem, y, g, epi, mt, nt, tid);
-}
-
-// wgrad variant of the bf16-piece loop: both operands arrive contiguous along channels, not along the contraction (pixels).
-// A thread loads rows k and k + 1 of its 4 channels, and the LDS image of a plane is [16 k-pairs][COLS] 32-bit words, a word
-// holding the bf16 pieces of (k, k + 1) of one channel: written with 16-byte stores, and a lane collects its 8 consecutive k
-// of one channel with four ds_read_b32 whose words already have the element order of the MFMA operand (32 lanes read 128
-// contiguous bytes: conflict-free).  Four times the LDS read instructions of the row-major image of fprop / dgrad.
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-constexpr int X3_PAIR_ROWS = BK / 2;
-
-// v[2q], v[2q+1] = rows (k, k+1) of k-pair  kp = tid / V + 8 q, channels 4 (tid % V) .. + 3
-template <int COLS, int PASSES>
-__device__ __forceinline__ void store_split3_pairs(unsigned* __restrict__ dst, const float4 (&v)[PASSES], int tid) {
-  constexpr int V = COLS / 4, PLANE = X3_PAIR_ROWS * COLS;
-  static_assert(PASSES == 4 && 256 / V == 8, "row assignment below: 8 row groups x 2 rows x 2 halves");
-  const int c4 = tid % V, rg = tid / V;
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const f32x4_t e = {v[2 * q].x, v[2 * q].y, v[2 * q].z, v[2 * q].w};
-    const f32x4_t o = {v[2 * q + 1].x, v[2 * q + 1].y, v[2 * q + 1].z, v[2 * q + 1].w};
-    const bf16x4_t eh = __builtin_convertvector(e, bf16x4_t), oh = __builtin_convertvector(o, bf16x4_t);
-    const f32x4_t e1 = e - __builtin_convertvector(eh, f32x4_t), o1 = o - __builtin_convertvector(oh, f32x4_t);
-    const bf16x4_t em = __builtin_convertvector(e1, bf16x4_t), om = __builtin_convertvector(o1, bf16x4_t);
-    const f32x4_t e2 = e1 - __builtin_convertvector(em, f32x4_t), o2 = o1 - __builtin_convertvector(om, f32x4_t);
-    const bf16x4_t el = __builtin_convertvector(e2, bf16x4_t), ol = __builtin_convertvector(o2, bf16x4_t);
-    unsigned* w = dst + (rg + 8 * q) * COLS + 4 * c4;
-    *reinterpret_cast<bf16x8_t*>(w) = __builtin_shufflevector(eh, oh, 0, 4, 1, 5, 2, 6, 3, 7);
-    *reinterpret_cast<bf16x8_t*>(w + PLANE) = __builtin_shufflevector(em, om, 0, 4, 1, 5, 2, 6, 3, 7);
-    *reinterpret_cast<bf16x8_t*>(w + 2 * PLANE) = __builtin_shufflevector(el, ol, 0, 4, 1, 5, 2, 6, 3, 7);
-  }
-}
-
-template <int TM, int TN, int MS, int NS, int COLS_A, int COLS_B>
-__device__ __forceinline__ void mma_stage_x3_pairs(const unsigned* __restrict__ As, const unsigned* __restrict__ Bs,
-                                                   f32x16 (&acc)[TM][TN], int wm0, int wn0, int lane) {
-  constexpr int PA = X3_PAIR_ROWS * COLS_A, PB = X3_PAIR_ROWS * COLS_B;
-  const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int s = 0; s < BK / 16; ++s) {
-    bf16x8_t a[3][TM], b[3][TN];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        u32x4_t f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) f[e] = As[p * PA + (8 * s + 4 * h + e) * COLS_A + wm0 + MS * i + r];
-        a[p][i] = __builtin_bit_cast(bf16x8_t, f);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        u32x4_t f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) f[e] = Bs[p * PB + (8 * s + 4 * h + e) * COLS_B + wn0 + NS * j + r];
-        b[p][j] = __builtin_bit_cast(bf16x8_t, f);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][i], b[1][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], b[2][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][i], b[0][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], b[1][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][i], b[0][j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], b[0][j], acc[i][j], 0, 0, 0);
-      }
-  }
 }
 
 // fprop for the stem (Cin = 4 on NHWC4): one filter tap per 16-byte load, K = R*S*4 padded to a multiple of 32
@@ -1632,181 +1562,6 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_kernel(const float* __restr
       __syncthreads();
       if (kt + 1 < kt_end) load(kt + 1);
       mma_stage<LDA, LDB, TM, TN, 32 * WM, 32 * WN, false, false>(As, Bs, acc, wm0, wn0, lane);
-    }
-  }
-
-  float* out = slab + (size_t)split * g.Cout * g.Ktot;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    int col;
-    bool cok = true;
-    if (C4) {
-      col = nt * BN + wn0 + 32 * WN * j + (lane & 31);
-      cok = col < g.Ktot;
-    } else {
-      const int per_tap = g.Cin / BN;
-      const int tap = nt / per_tap;
-      col = tap * g.Cin + (nt - tap * per_tap) * BN + wn0 + 32 * WN * j + (lane & 31);
-    }
-    if (!cok) continue;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = mt * BM + wm0 + 32 * WM * i + acc_row(e, lane);
-        out[(size_t)row * g.Ktot + col] = acc[i][j][e];
-      }
-  }
-}
-
-template <int BM, int BN, int WM, int WN, bool C4, bool INCR>
-__global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                          float* __restrict__ slab, Geom g, int MTw, int NTw,
-                                                          int kt_per_split) {
-  // bf16-piece variant of conv_wgrad_kernel (see conv_fprop_x3_kernel / mma_stage_x3_pairs)
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int AP = BM / 32, BP = BN / 32;
-  constexpr int AV = BM / 4, BV = BN / 4;
-  static_assert(BM == 128 && BN == 128, "row-pair assignment of the loader");
-  __shared__ __attribute__((aligned(16))) unsigned smem32[3 * X3_PAIR_ROWS * (BM + BN)];
-  unsigned* const As = smem32;
-  unsigned* const Bs = smem32 + 3 * X3_PAIR_ROWS * BM;
-
-  // All tiles of one K slice read the same rows of dy and (up to the filter halo) of x.  Work index w = slice * tiles + tile,
-  // handed out so that one XCD gets a contiguous range of w: the tiles of a slice then run at the same time behind the
-  // same L2 and each operand row is fetched from the fabric about once instead of once per tile (measured before the
-  // remap: 0.77 GB fetched per launch of the 128x128 kernel, 2-4 GB for the 64-channel layers and the stem).
-  const int tiles = MTw * NTw;
-  const int wi = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = wi / tiles;
-  const int tile = wi - split * tiles;
-  const int mt = tile % MTw, nt = tile / MTw;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm0 = (wave / WN) * 32, wn0 = (wave % WN) * 32;  // tile i / j of the wave: + 32*WM*i / + 32*WN*j
-  const int HoWo = g.Ho * g.Wo;
-  const int frame_bytes = g.H * g.W * g.Cin * 4;
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, g.N * frame_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, g.M * g.Cout * 4, 0x00020000);
-
-  // A: dy rows m0 + krow, columns mt*BM + 4*c4
-  int a_off[AP];
-#pragma unroll
-  for (int p = 0; p < AP; ++p) {
-    const int c4 = tid % AV;
-    const int krow = 2 * (tid / AV) + (p & 1) + 16 * (p >> 1);  // rows (k, k+1) of a k-pair sit in one thread
-    a_off[p] = (krow * g.Cout + mt * BM + 4 * c4) * 4;
-  }
-  // B: column -> (tap, ci) for this thread's loads (fixed over the K loop)
-  int b_krow[BP], b_off[BP], b_r[BP], b_s[BP], b_cls[BP];
-  bool b_cok[BP];
-#pragma unroll
-  for (int p = 0; p < BP; ++p) {
-    const int c4 = tid % BV;
-    const int krow = 2 * (tid / BV) + (p & 1) + 16 * (p >> 1);
-    b_krow[p] = krow;
-    int tap, ci;
-    if (C4) {
-      const int ncol = nt * BN + 4 * c4;
-      tap = ncol / g.Cin;
-      ci = ncol - tap * g.Cin;
-      b_cok[p] = ncol < g.Ktot;
-    } else {
-      const int per_tap = g.Cin / BN;
-      tap = nt / per_tap;
-      ci = (nt - tap * per_tap) * BN + 4 * c4;
-      b_cok[p] = true;
-    }
-    b_r[p] = tap / g.S - g.pad;
-    b_s[p] = tap % g.S - g.pad_w;
-    b_cls[p] = shift_class(ci, g.fold);
-    b_off[p] = ((b_r[p] * g.W + b_s[p]) * g.Cin + ci) * 4 + b_cls[p] * frame_bytes;
-  }
-
-  const int kt_begin = split * kt_per_split;
-  const int nkt_all = (g.M + BK - 1) / BK;
-  const int kt_end = min(kt_begin + kt_per_split, nkt_all);
-
-  // INCR: the B rows of a thread advance by BK = 32 output pixels per K step, so the input position (hi, wi), the
-  // frame-in-clip index and the byte offset of the pixel are carried from step to step with two conditional wraps
-  // and additions only -- no division, modulo or integer multiply in the loop (the loader used to cost 325 VALU
-  // instructions per K step against 145 in fprop, and VALU issue is what holds the MFMA pipe of these kernels
-  // below 70 %).  The host selects INCR when a step spans less than one frame and at most Ho - 1 whole rows.
-  const int st = g.stride;
-  const int d_ho = BK / g.Wo, d_wo = BK - d_ho * g.Wo;
-  const int wrap_w = g.Wo * st, wrap_h = g.Ho * st;
-  const int px = g.Cin * 4;                                   // bytes per input pixel
-  const int inc0 = (d_ho * st * g.W + d_wo * st) * px;        // plain advance
-  const int inc1 = (st * g.W - wrap_w) * px;                  // extra when wo wraps into the next output row
-  const int inc2 = (g.H * g.W - wrap_h * g.W) * px;           // extra when ho wraps into the next frame
-  int s_hi[BP], s_wi[BP], s_t[BP], s_off[BP];
-  if (INCR) {
-#pragma unroll
-    for (int p = 0; p < BP; ++p) {
-      const int m = split * kt_per_split * BK + b_krow[p];
-      const int n = m / HoWo;
-      const int rem = m - n * HoWo;
-      const int ho = rem / g.Wo, wo = rem - ho * g.Wo;
-      s_hi[p] = ho * st;
-      s_wi[p] = wo * st;
-      s_t[p] = n % g.T;
-      s_off[p] = ((n * g.H + s_hi[p]) * g.W + s_wi[p]) * px + b_off[p];
-    }
-  }
-
-  float4 ra[AP], rb[BP];
-  auto load = [&](int kt) {
-    const int m0 = kt * BK;
-#pragma unroll
-    for (int p = 0; p < AP; ++p)  // rows past M lie past num_records (the range check covers the vector offset): zeros
-      ra[p] = buf_load16(yr, a_off[p] + m0 * g.Cout * 4, 0);
-#pragma unroll
-    for (int p = 0; p < BP; ++p) {
-      const int m = m0 + b_krow[p];
-      const bool mok = m < g.M;
-      int hi, wi, t, off;
-      if (INCR) {
-        hi = s_hi[p];
-        wi = s_wi[p];
-        t = s_t[p];
-        off = s_off[p];
-        const int w2 = wi + d_wo * st;
-        const bool c1 = w2 >= wrap_w;
-        s_wi[p] = c1 ? w2 - wrap_w : w2;
-        const int h2 = hi + d_ho * st + (c1 ? st : 0);
-        const bool c2 = h2 >= wrap_h;
-        s_hi[p] = c2 ? h2 - wrap_h : h2;
-        const int t2 = t + (c2 ? 1 : 0);
-        s_t[p] = t2 == g.T ? 0 : t2;
-        s_off[p] = off + inc0 + (c1 ? inc1 : 0) + (c2 ? inc2 : 0);
-      } else {  // exact integer divisions (tiny feature maps)
-        const int mm = mok ? m : 0;
-        const int n = mm / HoWo;
-        const int rem = mm - n * HoWo;
-        const int ho = rem / g.Wo;
-        hi = ho * st;
-        wi = (rem - ho * g.Wo) * st;
-        t = n % g.T;
-        off = ((n * g.H + hi) * g.W + wi) * px + b_off[p];
-      }
-      const bool v = mok && b_cok[p] && (unsigned)(hi + b_r[p]) < (unsigned)g.H && (unsigned)(wi + b_s[p]) < (unsigned)g.W &&
-                     (unsigned)(t + b_cls[p]) < (unsigned)g.T;
-      rb[p] = buf_load16(xr, off | (v ? 0 : kOOB), 0);
-    }
-  };
-
-  f32x16 acc[TM][TN];
-  zero_acc<TM, TN>(acc);
-
-  if (kt_begin < kt_end) {
-    load(kt_begin);
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-      __syncthreads();
-      store_split3_pairs<BM, AP>(As, ra, tid);
-      store_split3_pairs<BN, BP>(Bs, rb, tid);
-      __syncthreads();
-      if (kt + 1 < kt_end) load(kt + 1);
-      mma_stage_x3_pairs<TM, TN, 32 * WM, 32 * WN, BM, BN>(As, Bs, acc, wm0, wn0, lane);
     }
   }
 
@@ -3022,10 +2777,6 @@ PlPlan plan_pl(int cfg, int M, int ncols, int nk, size_t ws_bytes, bool ksplit_o
   return p;
 }
 
-// the two-workgroups-per-CU bf16-piece kernels read their weight operand from the planes as well (round 2's BDVCIL_R1_PLANES=0,
-// "split it in the K loop as in round 1", is gone: 14.56 -> 13.98 ms over all fprop sites was its A/B)
-constexpr bool r1_planes_enabled() { return true; }
-
 // the stem (Cin = 4) on the bf16-piece K loop (BDVCIL_C4_X3=0: on the fp32-MFMA kernel, as in round 1)
 bool c4_x3_enabled() {
   static const bool on = getenv("BDVCIL_C4_X3") == nullptr || atoi(getenv("BDVCIL_C4_X3")) != 0;
@@ -3040,7 +2791,6 @@ int pl_dgrad_cfg(const bdv_conv_geom* g, int pieces = 3) {
   if (g->Cout % BK != 0) return -1;
   return pl_pick(true, g->Cin, g->R * g->S * g->Cout / BK, g->R * g->S, g->stride, pieces, g->fold > 0);
 }
-bool pl_fprop_ok(const bdv_conv_geom* g, int pieces = 3) { return pl_fprop_cfg(g, pieces) >= 0; }
 // plane-kernel tile of a site whose input BatchNorm the loader applies (pre_scale): the planner's choice, or the widest tile that
 // divides the column count where the planner would have used a kernel that cannot do it
 int pl_fprop_cfg_pre(const bdv_conv_geom* g) {
@@ -3049,7 +2799,6 @@ int pl_fprop_cfg_pre(const bdv_conv_geom* g) {
   if (cfg >= 0) return cfg;
   return g->Cout % 256 == 0 ? 0 : g->Cout % 128 == 0 ? 1 : 3;
 }
-bool pl_dgrad_ok(const bdv_conv_geom* g, int pieces = 3) { return pl_dgrad_cfg(g, pieces) >= 0; }
 
 
 struct WgradPlan {
@@ -3118,7 +2867,6 @@ int pl_wgrad_form(const bdv_conv_geom* g) {
   if (g->act_dtype == BDV_ACT_BF16 && g->Cout % 64 == 0 && g->Cin % 64 == 0) return 2;
   return -1;
 }
-bool pl_wgrad_ok(const bdv_conv_geom* g) { return pl_wgrad_form(g) >= 0; }
 
 // wgrad of the P family: one workgroup per CU, tiles of 128 / 256 output channels x 128 / 256 input channels of a tap
 struct WgradPlPlan {
@@ -3163,53 +2911,191 @@ WgradPlPlan plan_wgrad_pl(const bdv_conv_geom* g) {
   return p;
 }
 
-}  // namespace
+// ---- the dispatch decision: one plan per call ------------------------------------------------------------------------
+// Which kernel family and tile run a call, whether it reads the weight planes, and how large its side buffers are (rows of the
+// fused-statistics partial, slices of the weight-gradient slab).  Every launch and every query below asks plan_conv and nothing
+// else, so the buffer a caller sizes from bdv_conv_plan_query is the buffer the kernel writes.  The rules themselves are the
+// functions above; only the K-split of the remainder tiles (Work) is left to the launch, which knows the real workspace.
+enum { kFprop = 0, kDgrad = 1, kWgrad = 2 };
 
-extern "C" size_t bdv_conv_workspace_bytes(const bdv_conv_geom* gg, int kind) {
-  if (check_geom(gg, "bdv_conv_workspace_bytes")) return 0;
-  if (kind == 2) {
-    const WgradPlan p = plan_wgrad(gg);
-    return (size_t)p.splits * gg->Cout * gg->R * gg->S * gg->Cin * sizeof(float);
-  }
+struct ConvPlan {
+  int family = -1;     // BDV_CONV_* of include/bdvcil_hip.h; -1: refused, the reason is in bdv_last_error()
+  int cfg = -1;        // BDV_CONV_PL: tile configuration (kPlCfg)
+  bool wide = false;   // the 4-wave fp32-MFMA / bf16-piece / stem kernels: 128 x 128 tile (else 128 x 64)
+  bool reads_planes = false;
+  bool pre_ok = false; // the producer's BatchNorm can be applied in the loader (pre = true on a shifted site still gives its tile)
+  int stat_rows = 0;   // fprop / dgrad: one row per row tile (stride-2 dgrad: per parity class and row tile)
+  int splits = 0;      // wgrad: slices of dw's size in the slab
+  WgradPlan wg = {};   // BDV_CONV_WGRAD_F32
+  WgradPlPlan wpl = {};  // BDV_CONV_WGRAD_PL
+  char kernel[128] = "";  // as rocprofv3 prints it, without the anonymous namespace (weight gradients: up to the tile)
+};
+
+Geom fprop_geom(const bdv_conv_geom* gg) {  // also the weight gradient's
   Geom g = make_geom(gg);
-  FdPlan p;
-  if (kind == 0) {
-    g.M = g.N * g.Ho * g.Wo;
-    g.Ktot = g.Rt * g.R * g.S * g.Cin;
-    p = plan_fprop(g, kMaxSplitWorkspace);
-  } else {
-    if (gg->Cin % 64 != 0) return 0;
-    g.M = g.N * g.H * g.W;
-    g.Ktot = g.R * g.S * g.Cout;
-    p = plan_dgrad(g, kMaxSplitWorkspace);
-  }
-  size_t need = p.wk.split > 1 ? (size_t)p.wk.rem_tiles * p.wk.split * p.seg_bytes : 0;
-  // the P kernels (bdv_conv_fprop_pl / bdv_conv_dgrad_pl) plan their own K-split
-  for (int pieces = 1; pieces <= 3; ++pieces) {
-    if (kind == 0 && (pl_fprop_ok(gg, pieces) || (pieces == 3 && pl_fprop_cfg_pre(gg) >= 0))) {
-      const PlPlan q = plan_pl(pl_fprop_ok(gg, pieces) ? pl_fprop_cfg(gg, pieces) : pl_fprop_cfg_pre(gg), g.M, g.Cout, g.Ktot / BK, kMaxSplitWorkspace, true);
-      const size_t n2 = q.wk.split > 1 ? (size_t)q.wk.rem_tiles * q.wk.split * q.seg_bytes : 0;
-      need = n2 > need ? n2 : need;
-    } else if (kind == 1 && pl_dgrad_ok(gg, pieces) && gg->stride == 1) {
-      const PlPlan q = plan_pl(pl_dgrad_cfg(gg, pieces), g.M, g.Cin, g.Ktot / BK, kMaxSplitWorkspace, true);
-      const size_t n2 = q.wk.split > 1 ? (size_t)q.wk.rem_tiles * q.wk.split * q.seg_bytes : 0;
-      need = n2 > need ? n2 : need;
-    }
-  }
-  return need > 16 ? need : 16;
+  g.M = g.N * g.Ho * g.Wo;
+  g.Ktot = g.Rt * g.R * g.S * g.Cin;
+  return g;
+}
+Geom dgrad_geom(const bdv_conv_geom* gg) {
+  Geom g = make_geom(gg);
+  g.M = g.N * g.H * g.W;
+  g.Ktot = g.R * g.S * g.Cout;
+  return g;
 }
 
-extern "C" int bdv_conv_fprop_stat_rows(const bdv_conv_geom* gg) {
-  if (check_geom(gg, "bdv_conv_fprop_stat_rows")) return 0;
-  const int64_t M = (int64_t)gg->N * gg->Ho * gg->Wo;
-  return (int)((M + 127) / 128);
+// GEMM of a fprop / dgrad site as plan_pl takes it (dgrad with stride 2: the largest parity class, no K split)
+struct PlGemm {
+  int M, ncols, nk;
+  bool ksplit_ok;
+};
+PlGemm pl_gemm(const bdv_conv_geom* g, int kind) {
+  if (kind == kFprop) return {g->N * g->Ho * g->Wo, g->Cout, g->R * g->S * g->Cin / BK, true};
+  const int st = g->stride;
+  const int Mc0 = g->N * ((g->H + st - 1) / st) * ((g->W + st - 1) / st);
+  return {st == 1 ? g->N * g->H * g->W : Mc0, g->Cin, g->R * g->S * g->Cout / BK, st == 1};
+}
+
+// arith: 0 = fp32 MFMA, 1 / 2 / 3 = bf16 pieces per operand; pre: the producer's BatchNorm + ReLU in the loader
+ConvPlan plan_conv(const bdv_conv_geom* g, int kind, int arith, bool pre) {
+  ConvPlan p;
+#define PLAN_REQUIRE(cond, ...)     \
+  do {                              \
+    if (!(cond)) {                  \
+      bdv_set_error(__VA_ARGS__);   \
+      return p;                     \
+    }                               \
+  } while (0)
+  if (check_geom(g, "bdv_conv")) return p;
+  PLAN_REQUIRE(kind >= kFprop && kind <= kWgrad && arith >= 0 && arith <= 3, "bdv_conv: kind %d (0 fprop, 1 dgrad, 2 wgrad), arith %d (0 fp32 MFMA, 1..3 bf16 pieces)", kind, arith);
+  PLAN_REQUIRE(g->act_dtype == BDV_ACT_F32 || g->act_dtype == BDV_ACT_BF16, "bdv_conv: act_dtype %d (BDV_ACT_F32 = 0 | BDV_ACT_BF16 = 1)", g->act_dtype);
+  const bool h16 = g->act_dtype == BDV_ACT_BF16;   // bf16 storage: the single-product plane kernels are the only ones that read / write it
+  const bool c4 = g->Cin % BK != 0;
+  if (kind == kWgrad) {
+    const int form = arith ? pl_wgrad_form(g) : -1;
+    p.pre_ok = form >= 0 && !c4 && g->fold == 0 && !h16;
+    PLAN_REQUIRE(!pre || p.pre_ok, "bdv_conv_wgrad: a producer BatchNorm in the loader needs the plane kernel, fp32 tensors, Cin %% 32 == 0 and no temporal shift");
+    PLAN_REQUIRE(!h16 || (arith == 1 && form >= 0 && !c4),
+                 "bdv_conv_wgrad: bf16 activation storage needs pieces = 1 and the plane kernel (Cin %% 32 == 0; Cin=%d Cout=%d)", g->Cin, g->Cout);
+    if (form >= 0) {
+      p.family = BDV_CONV_WGRAD_PL;
+      p.wpl = plan_wgrad_pl(g);
+      p.splits = p.wpl.splits;
+      snprintf(p.kernel, sizeof(p.kernel), "conv_wgrad_pl_kernel<%d, %d", p.wpl.BM, p.wpl.BN);
+    } else {
+      PLAN_REQUIRE(g->Rt <= 1, "bdv_conv_wgrad: temporal taps (Rt=%d) need the bf16-piece plane kernel (bdv_conv_wgrad_partial_pl, BDVCIL_C4_X3)", g->Rt);
+      p.family = BDV_CONV_WGRAD_F32;
+      p.wg = plan_wgrad(g);
+      p.splits = p.wg.splits;
+      snprintf(p.kernel, sizeof(p.kernel), "conv_wgrad_kernel<%d, %d, 2, 2", p.wg.small ? 64 : 128, p.wg.small ? 64 : 128);
+    }
+    return p;
+  }
+  const bool dgrad = kind == kDgrad;
+  const char* const dir = dgrad ? "dgrad" : "fprop";
+  PLAN_REQUIRE(!dgrad || g->Cin % 64 == 0, "bdv_conv_dgrad: Cin=%d must be a multiple of 64", g->Cin);
+  // a consumer of a raw conv output: the planner's tile, or the widest plane tile where it would pick a kernel that cannot do it
+  const int cfg_pre = !dgrad && arith == 3 && !h16 ? pl_fprop_cfg_pre(g) : -1;
+  p.pre_ok = cfg_pre >= 0 && g->fold == 0;
+  PLAN_REQUIRE(!pre || cfg_pre >= 0, "bdv_conv_%s: a producer BatchNorm in the loader needs the plane kernels (fprop, pieces 3, fp32 tensors, Cin %% 32 == 0)", dir);
+  const int cfg = pre ? cfg_pre : !arith ? -1 : dgrad ? pl_dgrad_cfg(g, arith) : pl_fprop_cfg(g, arith);
+  PLAN_REQUIRE(!h16 || (arith == 1 && cfg >= 0),
+               "bdv_conv_%s: bf16 activation storage needs pieces = 1 and a geometry of the plane kernels (Cin=%d Cout=%d)", dir, g->Cin, g->Cout);
+  const int ncols = dgrad ? g->Cin : g->Cout;
+  const int st = g->stride, classes = dgrad ? st * st : 1;
+  if (cfg >= 0) {
+    const PlGemm m = pl_gemm(g, kind);
+    p.family = BDV_CONV_PL;
+    p.cfg = cfg;
+    p.reads_planes = true;
+    p.stat_rows = classes * plan_pl(cfg, m.M, m.ncols, m.nk, 0, false).MT;
+    snprintf(p.kernel, sizeof(p.kernel), "conv_%s_pl_kernel<%d, %d, %d, %d, %d, %d%s>", dir, kPlCfg[cfg].BM, kPlCfg[cfg].BN, pl_cfg_wm(cfg),
+             pl_cfg_wn(cfg), kPlCfg[cfg].nbuf, arith, pre ? ", true" : "");
+    return p;
+  }
+  p.wide = ncols % 128 == 0;
+  if (c4) {  // the stem (fprop only: dgrad needs Cin % 64 == 0), on the bf16-piece K loop unless BDVCIL_C4_X3=0
+    const bool x3 = arith && c4_x3_enabled();
+    PLAN_REQUIRE(g->Rt <= 1 || x3, "bdv_conv_fprop: temporal taps (Rt=%d) need the bf16-piece stem kernel (bdv_conv_fprop_pl)", g->Rt);
+    p.family = x3 ? BDV_CONV_C4_X3 : BDV_CONV_C4;
+    snprintf(p.kernel, sizeof(p.kernel), "conv_fprop_c4_%skernel<128, %d, 2, 2>", p.family == BDV_CONV_C4_X3 ? "x3_" : "", p.wide ? 128 : 64);
+  } else if (arith && p.wide) {  // two workgroups per CU, the weight operand from the planes
+    p.family = BDV_CONV_X3;
+    p.reads_planes = true;
+    snprintf(p.kernel, sizeof(p.kernel), "conv_%s_x3_kernel<128, 128, 2, 2, true>", dir);
+  } else {
+    p.family = BDV_CONV_F32;
+    snprintf(p.kernel, sizeof(p.kernel), "conv_%s_kernel<128, %d, 2, 2>", dir, p.wide ? 128 : 64);
+  }
+  // 128-row tiles; a stride-2 dgrad has them per parity class, sized by the largest
+  const int64_t rows = !dgrad ? (int64_t)g->N * g->Ho * g->Wo : (int64_t)g->N * ((g->H + st - 1) / st) * ((g->W + st - 1) / st);
+  p.stat_rows = (int)(classes * ((rows + 127) / 128));
+  return p;
+#undef PLAN_REQUIRE
+}
+
+// bytes of K-split slab a launch of plan `p` can use at most.  The 4-wave kernels are sized by the fp32-MFMA plan (three blocks
+// per CU) whatever their family: the bf16-piece ones split within what they are given.
+size_t ksplit_bytes(const bdv_conv_geom* gg, int kind, const ConvPlan& p) {
+  Work wk;
+  size_t seg;
+  if (p.family == BDV_CONV_PL) {
+    const PlGemm m = pl_gemm(gg, kind);
+    const PlPlan q = plan_pl(p.cfg, m.M, m.ncols, m.nk, kMaxSplitWorkspace, m.ksplit_ok);
+    wk = q.wk;
+    seg = q.seg_bytes;
+  } else {
+    const FdPlan q = kind == kFprop ? plan_fprop(fprop_geom(gg), kMaxSplitWorkspace) : plan_dgrad(dgrad_geom(gg), kMaxSplitWorkspace);
+    wk = q.wk;
+    seg = q.seg_bytes;
+  }
+  return wk.split > 1 ? (size_t)wk.rem_tiles * wk.split * seg : 0;
+}
+
+}  // namespace
+
+extern "C" int bdv_conv_plan_query(const bdv_conv_geom* gg, int kind, int arith, int pre, bdv_conv_plan* out) {
+  BDV_REQUIRE(out != nullptr, "bdv_conv_plan_query: out is NULL");
+  const ConvPlan p = plan_conv(gg, kind, arith, pre != 0);
+  if (p.family < 0) return BDV_EINVAL;
+  BDV_REQUIRE(!pre || p.pre_ok, "bdv_conv_plan_query: a producer BatchNorm in the loader needs a site without temporal shift");
+  out->family = p.family;
+  out->reads_planes = p.reads_planes;
+  out->stat_rows = p.stat_rows;
+  out->splits = p.splits;
+  out->pre_ok = p.pre_ok;
+  static_assert(sizeof(out->kernel) == sizeof(p.kernel), "bdv_conv_plan.kernel");
+  memcpy(out->kernel, p.kernel, sizeof(p.kernel));
+  return BDV_OK;
+}
+
+// Covers every arithmetic a caller may choose for this geometry (the entry points take one workspace whatever the mode).
+extern "C" size_t bdv_conv_workspace_bytes(const bdv_conv_geom* gg, int kind) {
+  if (kind == kWgrad) {
+    const ConvPlan p = plan_conv(gg, kWgrad, 0, false);
+    return p.family < 0 ? 0 : (size_t)p.splits * gg->Cout * gg->R * gg->S * gg->Cin * sizeof(float);
+  }
+  size_t need = 0;
+  bool any = false;
+  for (int arith = 0; arith <= 3; ++arith)
+    for (int pre = 0; pre <= (kind == kFprop ? 1 : 0); ++pre) {
+      const ConvPlan p = plan_conv(gg, kind, arith, pre != 0);
+      if (p.family < 0) continue;
+      any = true;
+      const size_t n = ksplit_bytes(gg, kind, p);
+      need = n > need ? n : need;
+    }
+  if (!any) return 0;
+  return need > 16 ? need : 16;
 }
 
 namespace {
 int conv_fprop_impl(const float* x, const float* w, float* y, const bdv_conv_geom* gg, float* bn_partial,
-                    const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, void* stream, bool x3,
+                    const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, void* stream, int arith,
                     const void* planes_f = nullptr) {
-  if (int e = check_geom(gg, "bdv_conv_fprop")) return e;
+  const ConvPlan cp = plan_conv(gg, kFprop, arith, false);
+  if (cp.family < 0) return BDV_EINVAL;
+  BDV_REQUIRE(!cp.reads_planes || planes_f != nullptr, "bdv_conv_fprop: this site runs on the weight planes (bdv_conv_plan_query: reads_planes), planes_fprop is NULL");
   BDV_REQUIRE(x && w && y, "bdv_conv_fprop: null pointer");
   FpropEpi epi = {bn_partial, 0, nullptr, nullptr, nullptr, 0};
   if (affine != nullptr) {
@@ -3228,30 +3114,26 @@ int conv_fprop_impl(const float* x, const float* w, float* y, const bdv_conv_geo
   g.M = g.N * g.Ho * g.Wo;
   g.Ktot = g.Rt * g.R * g.S * g.Cin;
   hipStream_t s = (hipStream_t)stream;
-  const bool c4 = (g.Cin % BK) != 0;
-  const FdPlan p = plan_fprop(g, workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, x3 && !c4);
+  const FdPlan p = plan_fprop(g, workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, cp.family == BDV_CONV_X3);
+  BDV_REQUIRE(p.MT == cp.stat_rows && p.wide == cp.wide, "bdv_conv_fprop: row tiles %d != planned %d", p.MT, cp.stat_rows);
   const int blocks = p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split;
   epi.MT = p.MT;
   float* slab = (float*)workspace;
   if (debug_plan())
     fprintf(stderr, "[bdv plan] fprop %dx%d Cin %d Cout %d k%d s%d: tiles %d nk %d -> dp %d rem %d split %d\n", g.H, g.W,
             g.Cin, g.Cout, g.R, g.stride, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split);
-  BDV_REQUIRE(gg->Rt <= 1 || (c4 && x3 && c4_x3_enabled()), "bdv_conv_fprop: temporal taps (Rt=%d) need the bf16-piece stem kernel (bdv_conv_fprop_x3)", gg->Rt);
-  if (c4 && x3 && c4_x3_enabled()) {
+  if (cp.family == BDV_CONV_C4_X3) {
     if (p.wide)
       hipLaunchKernelGGL((conv_fprop_c4_x3_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, epi);
     else
       hipLaunchKernelGGL((conv_fprop_c4_x3_kernel<128, 64, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, epi);
-  } else if (c4) {
+  } else if (cp.family == BDV_CONV_C4) {
     if (p.wide)
       hipLaunchKernelGGL((conv_fprop_c4_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, epi);
     else
       hipLaunchKernelGGL((conv_fprop_c4_kernel<128, 64, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, epi);
-  } else if (p.wide && x3) {
-    if (planes_f != nullptr)
-      hipLaunchKernelGGL((conv_fprop_x3_kernel<128, 128, 2, 2, true>), dim3(blocks), dim3(256), 0, s, x, (const float*)planes_f, y, g, p.NT, p.wk, slab, epi);
-    else
-      hipLaunchKernelGGL((conv_fprop_x3_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, p.wk, slab, epi);
+  } else if (cp.family == BDV_CONV_X3) {
+    hipLaunchKernelGGL((conv_fprop_x3_kernel<128, 128, 2, 2, true>), dim3(blocks), dim3(256), 0, s, x, (const float*)planes_f, y, g, p.NT, p.wk, slab, epi);
   } else if (p.wide) {
     hipLaunchKernelGGL((conv_fprop_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, p.wk, slab, epi);
   } else {
@@ -3272,28 +3154,16 @@ int conv_fprop_impl(const float* x, const float* w, float* y, const bdv_conv_geo
 
 extern "C" int bdv_conv_fprop(const float* x, const float* w, float* y, const bdv_conv_geom* gg, float* bn_partial,
                               const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, void* stream) {
-  return conv_fprop_impl(x, w, y, gg, bn_partial, affine, workspace, workspace_bytes, stream, false);
-}
-
-extern "C" int bdv_conv_fprop_x3(const float* x, const float* w, float* y, const bdv_conv_geom* gg, float* bn_partial,
-                                 const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, void* stream) {
-  return conv_fprop_impl(x, w, y, gg, bn_partial, affine, workspace, workspace_bytes, stream, true);
-}
-
-extern "C" int bdv_conv_dgrad_stat_rows(const bdv_conv_geom* gg) {
-  if (check_geom(gg, "bdv_conv_dgrad_stat_rows")) return 0;
-  const int st = gg->stride;
-  if (st == 1) return (int)(((int64_t)gg->N * gg->H * gg->W + 127) / 128);
-  const int64_t Mc0 = (int64_t)gg->N * ((gg->H + st - 1) / st) * ((gg->W + st - 1) / st);  // largest parity class
-  return (int)(st * st * ((Mc0 + 127) / 128));
+  return conv_fprop_impl(x, w, y, gg, bn_partial, affine, workspace, workspace_bytes, stream, 0);
 }
 
 namespace {
-// w_t != nullptr: the bf16-piece kernel on the per-tap transposed weights (wide tiles only), else the fp32-MFMA kernels
-int conv_dgrad_impl(const float* dy, const float* w, const float* w_t, float* dx, const float* add_src,
+int conv_dgrad_impl(const float* dy, const float* w, float* dx, const float* add_src,
                     const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat, void* workspace,
-                    size_t workspace_bytes, void* stream, const void* planes_d = nullptr) {
-  if (int e = check_geom(gg, "bdv_conv_dgrad")) return e;
+                    size_t workspace_bytes, void* stream, int arith, const void* planes_d = nullptr) {
+  const ConvPlan cp = plan_conv(gg, kDgrad, arith, false);
+  if (cp.family < 0) return BDV_EINVAL;
+  BDV_REQUIRE(!cp.reads_planes || planes_d != nullptr, "bdv_conv_dgrad: this site runs on the weight planes (bdv_conv_plan_query: reads_planes), planes_dgrad is NULL");
   BnStat stat = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
   if (bn_stat != nullptr) {
     BDV_REQUIRE(gg->stride == 1 || (gg->R >= gg->stride && gg->S >= gg->stride),
@@ -3309,8 +3179,8 @@ int conv_dgrad_impl(const float* dy, const float* w, const float* w_t, float* dx
     stat.partial = bn_stat->partial;
     stat.rscale = bn_stat->relu_mask == nullptr ? bn_stat->relu_scale : nullptr;
     stat.rshift = bn_stat->relu_shift;
-    stat.MT = bdv_conv_dgrad_stat_rows(gg);
-    BDV_REQUIRE(stat.rscale == nullptr || w_t != nullptr || planes_d != nullptr || gg->Cin % 128 != 0,
+    stat.MT = cp.stat_rows;
+    BDV_REQUIRE(stat.rscale == nullptr || cp.family != BDV_CONV_F32 || !cp.wide,
                 "bdv_conv_dgrad: a ReLU sign derived from y (relu_scale) is not compiled into the 128-wide fp32-MFMA kernel");
     if (gg->stride != 1)  // parity classes of odd-sized inputs have fewer row tiles than the largest: their rows stay zero
       (void)hipMemsetAsync(bn_stat->partial, 0, (size_t)2 * stat.MT * gg->Cin * sizeof(float), (hipStream_t)stream);
@@ -3318,26 +3188,22 @@ int conv_dgrad_impl(const float* dy, const float* w, const float* w_t, float* dx
   BDV_REQUIRE(dy && w && dx, "bdv_conv_dgrad: null pointer");
   BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(w) && bdv_aligned16(dx) && bdv_aligned16(workspace),
               "bdv_conv_dgrad: pointers must be 16-byte aligned");
-  BDV_REQUIRE(gg->Cin % 64 == 0, "bdv_conv_dgrad: Cin=%d must be a multiple of 64", gg->Cin);
   BDV_REQUIRE(add_src != nullptr || add_mask_src == nullptr, "bdv_conv_dgrad: add_mask_src without add_src");
   Geom g = make_geom(gg);
   g.M = g.N * g.H * g.W;
   g.Ktot = g.R * g.S * g.Cout;
   hipStream_t s = (hipStream_t)stream;
   const int st = g.stride;
-  const bool x3 = (w_t != nullptr || planes_d != nullptr) && (g.Cin % 128) == 0;
-  BDV_REQUIRE(w_t == nullptr || bdv_aligned16(w_t), "bdv_conv_dgrad_x3: w_t must be 16-byte aligned");
+  const bool x3 = cp.family == BDV_CONV_X3;
   const FdPlan p = plan_dgrad(g, workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, x3);
+  BDV_REQUIRE(st * st * p.MT == cp.stat_rows && p.wide == cp.wide, "bdv_conv_dgrad: row tiles %d != planned %d", st * st * p.MT, cp.stat_rows);
   const dim3 grid(p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split, st * st);
   float* slab = (float*)workspace;
   if (debug_plan())
     fprintf(stderr, "[bdv plan] dgrad %dx%d Cin %d Cout %d k%d s%d: tiles %d nk %d -> dp %d rem %d split %d\n", g.H, g.W,
             g.Cin, g.Cout, g.R, g.stride, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split);
-  if (p.wide && x3)
-    if (planes_d != nullptr)
-      hipLaunchKernelGGL((conv_dgrad_x3_kernel<128, 128, 2, 2, true>), grid, dim3(256), 0, s, dy, (const float*)planes_d, dx, add_src, add_mask_src, g, p.NT, p.wk, slab, stat);
-    else
-      hipLaunchKernelGGL((conv_dgrad_x3_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, dy, w_t, dx, add_src, add_mask_src, g, p.NT, p.wk, slab, stat);
+  if (x3)
+    hipLaunchKernelGGL((conv_dgrad_x3_kernel<128, 128, 2, 2, true>), grid, dim3(256), 0, s, dy, (const float*)planes_d, dx, add_src, add_mask_src, g, p.NT, p.wk, slab, stat);
   else if (p.wide)
     hipLaunchKernelGGL((conv_dgrad_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, dy, w, dx, add_src, add_mask_src, g, p.NT, p.wk, slab, stat);
   else
@@ -3358,14 +3224,7 @@ int conv_dgrad_impl(const float* dy, const float* w, const float* w_t, float* dx
 extern "C" int bdv_conv_dgrad(const float* dy, const float* w, float* dx, const float* add_src,
                               const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  return conv_dgrad_impl(dy, w, nullptr, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, stream);
-}
-
-extern "C" int bdv_conv_dgrad_x3(const float* dy, const float* w, const float* w_t, float* dx, const float* add_src,
-                                 const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
-  BDV_REQUIRE(w_t != nullptr, "bdv_conv_dgrad_x3: w_t is null");
-  return conv_dgrad_impl(dy, w, w_t, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, stream);
+  return conv_dgrad_impl(dy, w, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, stream, 0);
 }
 
 // ---- weights as bf16 planes + the P kernels --------------------------------------------------------------------------
@@ -3390,79 +3249,6 @@ extern "C" int bdv_conv_debug_force_tile(int cfg) {
   return BDV_OK;
 }
 
-// Name of the main kernel a call will launch (as rocprofv3 prints it, without the anonymous namespace): for profiles and
-// bench.py's per-kernel accounting.  kind 0 = fprop, 1 = dgrad, 2 = wgrad; arith 0 = fp32 MFMA entry points, 1 = the default
-// bf16-piece entry points (bdv_conv_fprop_pl / bdv_conv_dgrad_pl / bdv_conv_wgrad_partial_pl), 2 = the same with pieces = 1,
-// 3 = with pieces = 2.
-extern "C" int bdv_conv_kernel_name(const bdv_conv_geom* gg, int kind, int arith, char* out, size_t n) {
-  if (int e = check_geom(gg, "bdv_conv_kernel_name")) return e;
-  BDV_REQUIRE(out && n > 0 && kind >= 0 && kind <= 2, "bdv_conv_kernel_name: bad argument");
-  const bool c4 = gg->Cin % BK != 0;
-  const int pieces = arith == 2 ? 1 : arith == 3 ? 2 : 3;
-  if (kind == 0) {
-    const int cfg = arith ? pl_fprop_cfg(gg, pieces) : -1;
-    if (cfg >= 0) {
-      snprintf(out, n, "conv_fprop_pl_kernel<%d, %d, %d, %d, %d, %d>", kPlCfg[cfg].BM, kPlCfg[cfg].BN, pl_cfg_wm(cfg), pl_cfg_wn(cfg), kPlCfg[cfg].nbuf, pieces);
-    } else if (c4) {
-      snprintf(out, n, "conv_fprop_c4_%skernel<128, %d, 2, 2>", arith && c4_x3_enabled() ? "x3_" : "", gg->Cout % 128 == 0 ? 128 : 64);
-    } else if (gg->Cout % 128 == 0 && arith) {
-      snprintf(out, n, "conv_fprop_x3_kernel<128, 128, 2, 2, %s>", r1_planes_enabled() ? "true" : "false");
-    } else {
-      snprintf(out, n, "conv_fprop_kernel<128, %d, 2, 2>", gg->Cout % 128 == 0 ? 128 : 64);
-    }
-  } else if (kind == 1) {
-    const int cfg = arith ? pl_dgrad_cfg(gg, pieces) : -1;
-    if (cfg >= 0) {
-      snprintf(out, n, "conv_dgrad_pl_kernel<%d, %d, %d, %d, %d, %d>", kPlCfg[cfg].BM, kPlCfg[cfg].BN, pl_cfg_wm(cfg), pl_cfg_wn(cfg), kPlCfg[cfg].nbuf, pieces);
-    } else if (gg->Cin % 128 == 0 && arith) {
-      snprintf(out, n, "conv_dgrad_x3_kernel<128, 128, 2, 2, %s>", r1_planes_enabled() ? "true" : "false");
-    } else {
-      snprintf(out, n, "conv_dgrad_kernel<128, %d, 2, 2>", gg->Cin % 128 == 0 ? 128 : 64);
-    }
-  } else {
-    if (arith && pl_wgrad_ok(gg)) {
-      const WgradPlPlan p = plan_wgrad_pl(gg);
-      snprintf(out, n, "conv_wgrad_pl_kernel<%d, %d", p.BM, p.BN);
-    } else {
-      const WgradPlan p = plan_wgrad(gg);
-      snprintf(out, n, "conv_wgrad_kernel<%d, %d, 2, 2", p.small ? 64 : 128, p.small ? 64 : 128);
-    }
-  }
-  return BDV_OK;
-}
-
-extern "C" int bdv_conv_uses_planes(const bdv_conv_geom* gg, int kind, int pieces) {
-  if (check_geom(gg, "bdv_conv_uses_planes")) return 0;
-  if (kind == 0) return pl_fprop_ok(gg, pieces) || (pieces >= 2 && r1_planes_enabled() && gg->Cin % BK == 0 && gg->Cout % 128 == 0) ? 1 : 0;
-  if (kind == 1) return pl_dgrad_ok(gg, pieces) || (pieces >= 2 && r1_planes_enabled() && gg->Cout % BK == 0 && gg->Cin % 128 == 0) ? 1 : 0;
-  return 0;
-}
-
-extern "C" int bdv_conv_fprop_pl_stat_rows(const bdv_conv_geom* gg, int pieces) {
-  if (check_geom(gg, "bdv_conv_fprop_pl_stat_rows")) return 0;
-  if (!pl_fprop_ok(gg, pieces)) return bdv_conv_fprop_stat_rows(gg);
-  const PlPlan p = plan_pl(pl_fprop_cfg(gg, pieces), gg->N * gg->Ho * gg->Wo, gg->Cout, gg->R * gg->S * gg->Cin / BK, kMaxSplitWorkspace, true);
-  return p.cfg >= 0 ? p.MT : 0;
-}
-
-extern "C" int bdv_conv_fprop_pre_stat_rows(const bdv_conv_geom* gg) {
-  if (check_geom(gg, "bdv_conv_fprop_pre_stat_rows")) return 0;
-  const int cfg = pl_fprop_cfg_pre(gg);
-  if (cfg < 0) return 0;
-  const PlPlan p = plan_pl(cfg, gg->N * gg->Ho * gg->Wo, gg->Cout, gg->R * gg->S * gg->Cin / BK, kMaxSplitWorkspace, true);
-  return p.MT;
-}
-
-extern "C" int bdv_conv_dgrad_pl_stat_rows(const bdv_conv_geom* gg, int pieces) {
-  if (check_geom(gg, "bdv_conv_dgrad_pl_stat_rows")) return 0;
-  if (!pl_dgrad_ok(gg, pieces)) return bdv_conv_dgrad_stat_rows(gg);
-  const int st = gg->stride;
-  const int Mc0 = gg->N * ((gg->H + st - 1) / st) * ((gg->W + st - 1) / st);
-  const PlPlan p = plan_pl(pl_dgrad_cfg(gg, pieces), st == 1 ? gg->N * gg->H * gg->W : Mc0, gg->Cin, gg->R * gg->S * gg->Cout / BK,
-                           kMaxSplitWorkspace, st == 1);
-  return p.cfg >= 0 ? st * st * p.MT : 0;
-}
-
 extern "C" int bdv_conv_split_weights(const float* w, const bdv_conv_geom* gg, void* planes_fprop, void* planes_dgrad, void* stream) {
   if (int e = check_geom(gg, "bdv_conv_split_weights")) return e;
   BDV_REQUIRE(w && (planes_fprop || planes_dgrad), "bdv_conv_split_weights: null pointer");
@@ -3475,31 +3261,23 @@ extern "C" int bdv_conv_split_weights(const float* w, const bdv_conv_geom* gg, v
   return BDV_OK;
 }
 
-extern "C" int bdv_conv_fprop_pre_ok(const bdv_conv_geom* gg) {
-  if (check_geom(gg, "bdv_conv_fprop_pre_ok")) return 0;
-  return pl_fprop_cfg_pre(gg) >= 0 && gg->fold == 0 ? 1 : 0;
-}
-
 extern "C" int bdv_conv_fprop_pl(const void* x, const float* w, const void* planes_fprop, void* y, const bdv_conv_geom* gg,
                                  float* bn_partial, const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes,
                                  int pieces, const float* pre_scale, const float* pre_shift, void* stream) {
   if (int e = check_geom(gg, "bdv_conv_fprop_pl")) return e;
   BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_fprop_pl: pieces = %d (3, 2 or 1)", pieces);
   const bool pre = pre_scale != nullptr;
+  const ConvPlan cp = plan_conv(gg, kFprop, pieces, pre);
+  if (cp.family < 0) return BDV_EINVAL;
   const bool h16 = gg->act_dtype == BDV_ACT_BF16;
-  BDV_REQUIRE_ACT(gg->act_dtype, "bdv_conv_fprop_pl");
-  if (h16)   // bf16 storage: the single-product plane kernels are the only kernels that read / write it
-    BDV_REQUIRE(pieces == 1 && !pre && planes_fprop != nullptr && pl_fprop_ok(gg, 1),
-                "bdv_conv_fprop_pl: bf16 activation storage needs pieces = 1, the weight planes, Cin %% 32 == 0 and Cout %% 64 == 0 (Cin=%d Cout=%d)", gg->Cin, gg->Cout);
   if (pre) {
-    BDV_REQUIRE(pre_shift != nullptr && planes_fprop != nullptr && pieces == 3 && gg->fold == 0 && pl_fprop_cfg_pre(gg) >= 0,
+    BDV_REQUIRE(pre_shift != nullptr && cp.pre_ok,
                 "bdv_conv_fprop_pl: a producer BatchNorm in the loader needs the plane kernels (pieces 3, no temporal shift, Cin %% 32 == 0)");
     BDV_REQUIRE(bdv_aligned16(pre_scale) && bdv_aligned16(pre_shift), "bdv_conv_fprop_pl: pre_scale / pre_shift must be 16-byte aligned");
   }
-  if (!pre && (planes_fprop == nullptr || !pl_fprop_ok(gg, pieces)))  // sites of the two-workgroups-per-CU kernels (weights from the planes too)
-    return conv_fprop_impl((const float*)x, w, (float*)y, gg, bn_partial, affine, workspace, workspace_bytes, stream, true,
-                           gg->Cin % BK == 0 && r1_planes_enabled() ? planes_fprop : nullptr);
-  BDV_REQUIRE(x && y, "bdv_conv_fprop_pl: null pointer");
+  if (cp.family != BDV_CONV_PL)  // sites of the two-workgroups-per-CU kernels (weights from the planes too), the stem, 64 columns behind 1x1
+    return conv_fprop_impl((const float*)x, w, (float*)y, gg, bn_partial, affine, workspace, workspace_bytes, stream, pieces, planes_fprop);
+  BDV_REQUIRE(x && y && planes_fprop, "bdv_conv_fprop_pl: null pointer");
   FpropEpi epi = {bn_partial, 0, nullptr, nullptr, nullptr, 0, pre_scale, pre_shift};
   if (affine != nullptr) {
     BDV_REQUIRE(bn_partial == nullptr, "bdv_conv_fprop_pl: batch statistics and the folded eval-mode BatchNorm exclude each other");
@@ -3518,9 +3296,8 @@ extern "C" int bdv_conv_fprop_pl(const void* x, const float* w, const void* plan
   g.Ktot = g.Rt * g.R * g.S * g.Cin;
   BDV_REQUIRE((int64_t)3 * g.Cout * g.Ktot * 2 < (1ll << 31), "bdv_conv_fprop_pl: weight planes exceed 2^31 bytes");
   hipStream_t s = (hipStream_t)stream;
-  const PlPlan p = plan_pl(pre ? pl_fprop_cfg_pre(gg) : pl_fprop_cfg(gg, pieces), g.M, g.Cout, g.Ktot / BK, workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, !h16);  // (no K split with bf16 storage: the fix-up kernels are fp32)
-  BDV_REQUIRE(p.cfg >= 0, "bdv_conv_fprop_pl: no tile configuration for Cout=%d", g.Cout);
-  // bn_partial has one row per row tile of THIS kernel: bdv_conv_fprop_pl_stat_rows(g)
+  const PlPlan p = plan_pl(cp.cfg, g.M, g.Cout, g.Ktot / BK, workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, !h16);  // (no K split with bf16 storage: the fix-up kernels are fp32)
+  BDV_REQUIRE(p.MT == cp.stat_rows, "bdv_conv_fprop_pl: row tiles %d != planned %d", p.MT, cp.stat_rows);  // bn_partial has one row per row tile of THIS kernel
   const int blocks = p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split;
   epi.MT = p.MT;
   float* slab = (float*)workspace;
@@ -3566,14 +3343,12 @@ extern "C" int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* pla
                                  void* workspace, size_t workspace_bytes, int pieces, void* stream) {
   if (int e = check_geom(gg, "bdv_conv_dgrad_pl")) return e;
   BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_dgrad_pl: pieces = %d (3, 2 or 1)", pieces);
+  const ConvPlan cp = plan_conv(gg, kDgrad, pieces, false);
+  if (cp.family < 0) return BDV_EINVAL;
   const bool h16 = gg->act_dtype == BDV_ACT_BF16;
-  BDV_REQUIRE_ACT(gg->act_dtype, "bdv_conv_dgrad_pl");
-  if (h16)
-    BDV_REQUIRE(pieces == 1 && planes_dgrad != nullptr && pl_dgrad_ok(gg, 1),
-                "bdv_conv_dgrad_pl: bf16 activation storage needs pieces = 1, the weight planes, Cout %% 32 == 0 and Cin %% 64 == 0 (Cin=%d Cout=%d)", gg->Cin, gg->Cout);
-  if (planes_dgrad == nullptr || !pl_dgrad_ok(gg, pieces))
-    return conv_dgrad_impl((const float*)dy, w, nullptr, (float*)dx, (const float*)add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, stream,
-                           gg->Cout % BK == 0 && r1_planes_enabled() ? planes_dgrad : nullptr);
+  if (cp.family != BDV_CONV_PL)
+    return conv_dgrad_impl((const float*)dy, w, (float*)dx, (const float*)add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, stream,
+                           pieces, planes_dgrad);
   BnStat stat = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
   if (bn_stat != nullptr) {
     BDV_REQUIRE(gg->stride == 1 || (gg->R >= gg->stride && gg->S >= gg->stride),
@@ -3590,7 +3365,7 @@ extern "C" int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* pla
     stat.rscale = bn_stat->relu_mask == nullptr ? bn_stat->relu_scale : nullptr;
     stat.rshift = bn_stat->relu_shift;
   }
-  BDV_REQUIRE(dy && dx, "bdv_conv_dgrad_pl: null pointer");
+  BDV_REQUIRE(dy && dx && planes_dgrad, "bdv_conv_dgrad_pl: null pointer");
   BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(planes_dgrad) && bdv_aligned16(dx) && bdv_aligned16(workspace),
               "bdv_conv_dgrad_pl: pointers must be 16-byte aligned");
   BDV_REQUIRE(add_src != nullptr || add_mask_src == nullptr, "bdv_conv_dgrad_pl: add_mask_src without add_src");
@@ -3601,9 +3376,9 @@ extern "C" int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* pla
   hipStream_t s = (hipStream_t)stream;
   const int st = g.stride;
   const int Mc0 = g.N * ((g.H + st - 1) / st) * ((g.W + st - 1) / st);  // largest parity class
-  PlPlan p = plan_pl(pl_dgrad_cfg(gg, pieces), st == 1 ? g.M : Mc0, g.Cin, g.Ktot / BK,
+  PlPlan p = plan_pl(cp.cfg, st == 1 ? g.M : Mc0, g.Cin, g.Ktot / BK,
                      workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, st == 1 && !h16);
-  BDV_REQUIRE(p.cfg >= 0, "bdv_conv_dgrad_pl: no tile configuration for Cin=%d", g.Cin);
+  BDV_REQUIRE(st * st * p.MT == cp.stat_rows, "bdv_conv_dgrad_pl: row tiles %d != planned %d", st * st * p.MT, cp.stat_rows);
   if (st != 1) p.wk.dp_tiles = ((p.MT + 7) / 8) * 8 * p.NT;  // padded grid per parity class
   // the statistics partial has one row per row tile of THIS kernel (stride 2: per parity class and row tile)
   stat.MT = st * st * p.MT;
@@ -3649,11 +3424,10 @@ extern "C" int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* pla
 
 namespace {
 
-// main kernel of a weight gradient: split-K partial products into `slab` (plan_wgrad(gg).splits slices of dw's size)
+// main kernel of a BDV_CONV_WGRAD_F32 plan: split-K partial products into `slab` (the plan's `splits` slices of dw's size)
 int wgrad_partial(const char* who, const float* dy, const float* x, const bdv_conv_geom* gg, void* workspace, size_t workspace_bytes,
-                  hipStream_t s, int* splits_out, bool x3 = false) {
-  BDV_REQUIRE(gg == nullptr || gg->Rt <= 1, "%s: temporal taps (Rt=%d) need the bf16-piece plane kernel (bdv_conv_wgrad_partial_pl, BDVCIL_C4_X3)", who, gg->Rt);
-  const WgradPlan p = plan_wgrad(gg);
+                  hipStream_t s, int* splits_out, const ConvPlan& cp) {
+  const WgradPlan& p = cp.wg;
   const size_t need = (size_t)p.splits * gg->Cout * gg->R * gg->S * gg->Cin * sizeof(float);
   if (workspace_bytes < need) {
     bdv_set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
@@ -3677,14 +3451,7 @@ int wgrad_partial(const char* who, const float* dy, const float* x, const bdv_co
       hipLaunchKernelGGL((conv_wgrad_kernel<BMN, BMN, 2, 2, C4F, false>), grid, dim3(256), 0, s, dy, x, slab, g, p.MTw, p.NTw,  \
                          p.kt_per_split);                                                                                      \
   } while (0)
-  if (!p.small && x3) {  // experimental bf16-piece K loop (128x128 tiles only)
-    if (incr)
-      hipLaunchKernelGGL((conv_wgrad_x3_kernel<128, 128, 2, 2, false, true>), grid, dim3(256), 0, s, dy, x, slab, g, p.MTw, p.NTw,
-                         p.kt_per_split);
-    else
-      hipLaunchKernelGGL((conv_wgrad_x3_kernel<128, 128, 2, 2, false, false>), grid, dim3(256), 0, s, dy, x, slab, g, p.MTw, p.NTw,
-                         p.kt_per_split);
-  } else if (!p.small) {
+  if (!p.small) {
     BDV_WGRAD(128, false);
   } else if (p.c4) {
     BDV_WGRAD(64, true);
@@ -3701,13 +3468,14 @@ int wgrad_partial(const char* who, const float* dy, const float* x, const bdv_co
 
 extern "C" int bdv_conv_wgrad(const float* dy, const float* x, float* dw, float beta, const bdv_conv_geom* gg,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_wgrad")) return e;
+  const ConvPlan cp = plan_conv(gg, kWgrad, 0, false);
+  if (cp.family < 0) return BDV_EINVAL;
   BDV_REQUIRE(dy && x && dw && workspace, "bdv_conv_wgrad: null pointer");
   BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(x) && bdv_aligned16(dw) && bdv_aligned16(workspace),
               "bdv_conv_wgrad: pointers must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   int splits = 0;
-  if (int e = wgrad_partial("bdv_conv_wgrad", dy, x, gg, workspace, workspace_bytes, s, &splits)) return e;
+  if (int e = wgrad_partial("bdv_conv_wgrad", dy, x, gg, workspace, workspace_bytes, s, &splits, cp)) return e;
   const int64_t numel4 = (int64_t)gg->Cout * gg->R * gg->S * gg->Cin / 4;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((int)((numel4 + 63) / 64)), dim3(256), 0, s, (const float*)workspace, dw, beta, splits,
                      numel4);
@@ -3715,57 +3483,30 @@ extern "C" int bdv_conv_wgrad(const float* dy, const float* x, float* dw, float 
   return BDV_OK;
 }
 
-extern "C" int bdv_conv_wgrad_splits(const bdv_conv_geom* gg) {
-  if (check_geom(gg, "bdv_conv_wgrad_splits")) return 0;
-  return plan_wgrad(gg).splits;
-}
-
 extern "C" int bdv_conv_wgrad_partial(const float* dy, const float* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes,
                                       void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_wgrad_partial")) return e;
+  const ConvPlan cp = plan_conv(gg, kWgrad, 0, false);
+  if (cp.family < 0) return BDV_EINVAL;
   BDV_REQUIRE(dy && x && slab, "bdv_conv_wgrad_partial: null pointer");
   BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(x) && bdv_aligned16(slab), "bdv_conv_wgrad_partial: pointers must be 16-byte aligned");
   int splits = 0;
-  return wgrad_partial("bdv_conv_wgrad_partial", dy, x, gg, slab, slab_bytes, (hipStream_t)stream, &splits);
-}
-
-extern "C" int bdv_conv_wgrad_partial_x3(const float* dy, const float* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes,
-                                         void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_wgrad_partial_x3")) return e;
-  BDV_REQUIRE(dy && x && slab, "bdv_conv_wgrad_partial_x3: null pointer");
-  BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(x) && bdv_aligned16(slab), "bdv_conv_wgrad_partial_x3: pointers must be 16-byte aligned");
-  int splits = 0;
-  return wgrad_partial("bdv_conv_wgrad_partial_x3", dy, x, gg, slab, slab_bytes, (hipStream_t)stream, &splits, true);
-}
-
-extern "C" int bdv_conv_wgrad_pl_splits(const bdv_conv_geom* gg) {
-  if (check_geom(gg, "bdv_conv_wgrad_pl_splits")) return 0;
-  return pl_wgrad_ok(gg) ? plan_wgrad_pl(gg).splits : plan_wgrad(gg).splits;
-}
-
-extern "C" int bdv_conv_wgrad_pre_ok(const bdv_conv_geom* gg) {
-  if (check_geom(gg, "bdv_conv_wgrad_pre_ok")) return 0;
-  return pl_wgrad_ok(gg) && gg->Cin % BK == 0 && gg->fold == 0 ? 1 : 0;
+  return wgrad_partial("bdv_conv_wgrad_partial", dy, x, gg, slab, slab_bytes, (hipStream_t)stream, &splits, cp);
 }
 
 extern "C" int bdv_conv_wgrad_partial_pl(const void* dy, const void* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes,
                                          int pieces, const float* pre_scale, const float* pre_shift, void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_wgrad_partial_pl")) return e;
-  BDV_REQUIRE(pre_scale == nullptr || (pre_shift != nullptr && pl_wgrad_ok(gg) && gg->Cin % BK == 0 && gg->fold == 0),
-              "bdv_conv_wgrad_partial_pl: a producer BatchNorm in the loader needs the plane kernel, Cin %% 32 == 0 and no temporal shift");
   BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_wgrad_partial_pl: pieces = %d (3, 2 or 1)", pieces);
+  const ConvPlan cp = plan_conv(gg, kWgrad, pieces, pre_scale != nullptr);
+  if (cp.family < 0) return BDV_EINVAL;
+  BDV_REQUIRE(pre_scale == nullptr || pre_shift != nullptr, "bdv_conv_wgrad_partial_pl: pre_scale without pre_shift");
   BDV_REQUIRE(dy && x && slab, "bdv_conv_wgrad_partial_pl: null pointer");
   BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(x) && bdv_aligned16(slab), "bdv_conv_wgrad_partial_pl: pointers must be 16-byte aligned");
   const bool h16 = gg->act_dtype == BDV_ACT_BF16;
-  BDV_REQUIRE_ACT(gg->act_dtype, "bdv_conv_wgrad_partial_pl");
-  if (h16)
-    BDV_REQUIRE(pieces == 1 && pre_scale == nullptr && pl_wgrad_ok(gg) && gg->Cin % BK == 0,
-                "bdv_conv_wgrad_partial_pl: bf16 activation storage needs pieces = 1 and the plane kernel (Cin %% 32 == 0; Cin=%d Cout=%d)", gg->Cin, gg->Cout);
-  if (!pl_wgrad_ok(gg)) {
+  if (cp.family != BDV_CONV_WGRAD_PL) {
     int splits = 0;
-    return wgrad_partial("bdv_conv_wgrad_partial_pl", (const float*)dy, (const float*)x, gg, slab, slab_bytes, (hipStream_t)stream, &splits, pieces >= 2);
+    return wgrad_partial("bdv_conv_wgrad_partial_pl", (const float*)dy, (const float*)x, gg, slab, slab_bytes, (hipStream_t)stream, &splits, cp);
   }
-  const WgradPlPlan p = plan_wgrad_pl(gg);
+  const WgradPlPlan& p = cp.wpl;
   const size_t need = (size_t)p.splits * gg->Cout * (gg->Rt > 1 ? gg->Rt : 1) * gg->R * gg->S * gg->Cin * sizeof(float);
   if (slab_bytes < need) {
     bdv_set_error("bdv_conv_wgrad_partial_pl: slab %zu < required %zu bytes", slab_bytes, need);

@@ -11,7 +11,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from ._lib import BnStatFuse, ConvAffine, ConvGeom, check, lib
+from ._lib import BnStatFuse, ConvAffine, ConvGeom, ConvPlan, check, lib
 
 _WS = {}  # (device index, tag) -> workspace tensor (grown on demand, never shrunk)
 
@@ -184,8 +184,6 @@ CHECK_PLANES = _os.environ.get('BDVCIL_CHECK_PLANES', '0') != '0'
 
 def _weight_checksum(w: torch.Tensor) -> int:
     return int(w.contiguous().view(torch.int32).to(torch.int64).sum().item())
-USE_PL = _os.environ.get('BDVCIL_PL', '1') != '0'       # 0: the round-1 bf16-piece kernels (operands split in the K loop)
-USE_PL_WGRAD = _os.environ.get('BDVCIL_PL_WGRAD', '1') != '0'
 
 
 def bump_weight_epoch(params=None):
@@ -283,21 +281,35 @@ def refresh_weight_planes(stream: Optional[torch.cuda.Stream] = None) -> int:
     return n
 
 
+_KINDS = {'fprop': 0, 'dgrad': 1, 'wgrad': 2}
+
+
+def conv_plan(g: ConvGeom, kind: str, x3: Optional[bool] = None, pre: bool = False) -> ConvPlan:
+    """The library's plan of ``conv_fprop`` / ``conv_dgrad`` / ``conv_wgrad(_partial)`` for this geometry in the current arithmetic
+    (``x3``: instead of the direction's flag; ``g.act_dtype`` as the caller set it; ``pre``: with ``pre_bn``): ``kernel``,
+    ``reads_planes``, ``stat_rows``, ``splits``, ``pre_ok``.  The launches follow the same plan, so the side buffers are sized from
+    it.  Raises where the library has no kernel for the request."""
+    k = _KINDS[kind]
+    flag = (FPROP_X3, DGRAD_X3, WGRAD_X3)[k] if x3 is None else x3
+    plan = ConvPlan()
+    check(lib().bdv_conv_plan_query(ctypes.byref(g), k, PIECES if flag else 0, int(pre), ctypes.byref(plan)), 'bdv_conv_plan_query')
+    return plan
+
+
+def _chk_bf16_arith(g: ConvGeom, x3, who: str):
+    if g.act_dtype == 1 and not (x3 and PIECES == 1):
+        raise ValueError(f"{who}: bf16 tensors need set_conv_arith('bf16') and a geometry of the plane kernels")
+
+
 def conv_kernel_name(g: ConvGeom, kind: str, x3: Optional[bool] = None) -> str:
     """Name of the main kernel ``conv_fprop`` / ``conv_dgrad`` / ``conv_wgrad(_partial)`` launches for this geometry."""
-    k = {'fprop': 0, 'dgrad': 1, 'wgrad': 2}[kind]
-    flag = (FPROP_X3, DGRAD_X3, WGRAD_X3)[k] if x3 is None else x3
-    buf = ctypes.create_string_buffer(128)
-    check(lib().bdv_conv_kernel_name(ctypes.byref(g), k, {3: 1, 1: 2, 2: 3}[PIECES] if flag else 0, buf, 128), 'bdv_conv_kernel_name')
-    return buf.value.decode()
+    return conv_plan(g, kind, x3).kernel.decode()
 
 
 def conv_uses_planes(g: ConvGeom, kind: str) -> bool:
     """True when ``conv_fprop`` / ``conv_dgrad`` of this geometry read the cached bf16 weight planes (the cache that
     ``bump_weight_epoch`` invalidates) in the current arithmetic."""
-    k = {'fprop': 0, 'dgrad': 1}[kind]
-    flag = (FPROP_X3, DGRAD_X3)[k]
-    return bool(flag and USE_PL and lib().bdv_conv_uses_planes(ctypes.byref(g), k, PIECES))
+    return bool(conv_plan(g, kind).reads_planes)
 
 
 PRE_BN_1X1_ONLY = _os.environ.get('BDVCIL_PRE_BN_3X3', '0') == '0'
@@ -308,9 +320,9 @@ def fprop_pre_ok(g: ConvGeom) -> bool:
     loaders for this geometry (bf16-piece arithmetic with the plane kernels; no temporal shift)."""
     if PRE_BN_1X1_ONLY and (g.R != 1 or g.S != 1):   # a 3x3 consumer re-applies the BatchNorm once per filter tap: measured slower
         return False
-    return bool(PIECES == 3 and FPROP_X3 and WGRAD_X3 and DGRAD_X3 and USE_PL and USE_PL_WGRAD and g.fold == 0 and g.Rt <= 1
-                and not getattr(g, 'frames_view', False)
-                and lib().bdv_conv_fprop_pre_ok(ctypes.byref(g)) and lib().bdv_conv_wgrad_pre_ok(ctypes.byref(g)))
+    if not (PIECES == 3 and FPROP_X3 and WGRAD_X3 and DGRAD_X3) or g.Rt > 1 or g.act_dtype != 0 or getattr(g, 'frames_view', False):
+        return False
+    return bool(conv_plan(g, 'fprop').pre_ok and conv_plan(g, 'wgrad').pre_ok)
 
 
 def conv_fprop(x: torch.Tensor, w: torch.Tensor, g: ConvGeom, out: Optional[torch.Tensor] = None,
@@ -326,26 +338,18 @@ def conv_fprop(x: torch.Tensor, w: torch.Tensor, g: ConvGeom, out: Optional[torc
     _chk(w, (g.Cout, _taps_r(g), g.S, g.Cin), name='w')
     y = out if out is not None else torch.empty((g.N, g.Ho, g.Wo, g.Cout), dtype=x.dtype, device=x.device)
     _chk_conv(y, (g.N, g.Ho, g.Wo, g.Cout), g, 'y')
+    use_x3 = FPROP_X3 if x3 is None else x3
+    _chk_bf16_arith(g, use_x3, 'conv_fprop')
+    plan = conv_plan(g, 'fprop', use_x3, pre_bn is not None)
     ws = _conv_ws(g, 0, x.device, ws_tag)
     part = aff = None
-    use_x3 = FPROP_X3 if x3 is None else x3
-    use_pl = bool(use_x3 and USE_PL and lib().bdv_conv_uses_planes(ctypes.byref(g), 0, PIECES))
-    if g.act_dtype == 1 and not (use_pl and PIECES == 1):
-        raise ValueError("conv_fprop: bf16 tensors need set_conv_arith('bf16') and a geometry of the plane kernels (Cin % 32 == 0, Cout % 64 == 0)")
     if pre_bn is not None:
-        if not (use_x3 and USE_PL and PIECES == 3 and lib().bdv_conv_fprop_pre_ok(ctypes.byref(g))):
-            raise ValueError('conv_fprop: pre_bn needs the bf16-piece plane kernels for this geometry (fprop_pre_ok)')
         _chk(pre_bn[0], (g.Cin,), name='pre_scale')
         _chk(pre_bn[1], (g.Cin,), name='pre_shift')
-        use_pl = True
     if bn_stats:
         if affine is not None:
             raise ValueError('conv_fprop: bn_stats and affine exclude each other')
-        rows = lib().bdv_conv_fprop_pre_stat_rows(ctypes.byref(g)) if pre_bn is not None else \
-            lib().bdv_conv_fprop_pl_stat_rows(ctypes.byref(g), PIECES) if use_pl else lib().bdv_conv_fprop_stat_rows(ctypes.byref(g))
-        if rows <= 0:
-            check(-1, 'bdv_conv_fprop_stat_rows')
-        part = torch.empty((2, rows, g.Cout), dtype=torch.float32, device=x.device)
+        part = torch.empty((2, plan.stat_rows, g.Cout), dtype=torch.float32, device=x.device)
     if affine is not None:
         scale, shift, res, relu = affine
         _chk(scale, (g.Cout,), name='scale')
@@ -353,16 +357,15 @@ def conv_fprop(x: torch.Tensor, w: torch.Tensor, g: ConvGeom, out: Optional[torc
         if res is not None:
             _chk_conv(res, (g.N, g.Ho, g.Wo, g.Cout), g, 'residual')
         aff = ConvAffine(scale.data_ptr(), shift.data_ptr(), res.data_ptr() if res is not None else None, int(bool(relu)))
-    if use_pl:
-        planes_f, _ = weight_planes(w, g)
+    if use_x3:
+        planes_f = weight_planes(w, g)[0] if plan.reads_planes else None
         check(lib().bdv_conv_fprop_pl(_p(x), _p(w), _p(planes_f), _p(y), ctypes.byref(g), _p(part),
                                       ctypes.byref(aff) if aff is not None else None, _p(ws), ws.numel(), PIECES,
                                       _p(pre_bn[0] if pre_bn is not None else None), _p(pre_bn[1] if pre_bn is not None else None),
                                       _stream()), 'bdv_conv_fprop_pl')
-        return (y, part) if bn_stats else y
-    fn = lib().bdv_conv_fprop_x3 if use_x3 else lib().bdv_conv_fprop
-    check(fn(_p(x), _p(w), _p(y), ctypes.byref(g), _p(part), ctypes.byref(aff) if aff is not None else None,
-             _p(ws), ws.numel(), _stream()), 'bdv_conv_fprop')
+    else:
+        check(lib().bdv_conv_fprop(_p(x), _p(w), _p(y), ctypes.byref(g), _p(part), ctypes.byref(aff) if aff is not None else None,
+                                   _p(ws), ws.numel(), _stream()), 'bdv_conv_fprop')
     return (y, part) if bn_stats else y
 
 
@@ -386,11 +389,10 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, g: ConvGeom, add_src: Optional
             raise ValueError('conv_dgrad: in-place add_src is not allowed with a temporal shift (scatter epilogue)')
     if add_mask_src is not None:
         _chk(add_mask_src, (g.N * g.H * g.W * g.Cin // 32,), dtype=torch.int32, name='add_mask_src')
+    use_x3 = DGRAD_X3 if x3 is None else x3
+    _chk_bf16_arith(g, use_x3, 'conv_dgrad')
+    plan = conv_plan(g, 'dgrad', use_x3)
     fuse = partial = None
-    use_x3 = (DGRAD_X3 if x3 is None else x3) and g.Cin % 64 == 0
-    use_pl = bool(use_x3 and USE_PL and lib().bdv_conv_uses_planes(ctypes.byref(g), 1, PIECES))
-    if g.act_dtype == 1 and not (use_pl and PIECES == 1):
-        raise ValueError("conv_dgrad: bf16 tensors need set_conv_arith('bf16') and a geometry of the plane kernels (Cout % 32 == 0, Cin % 64 == 0)")
     relu_affine = None
     if bn_stats is not None:
         if len(bn_stats) == 5:      # (y, None, mean, invstd, (scale, shift)): the unit's ReLU sign is derived from y
@@ -402,10 +404,7 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, g: ConvGeom, add_src: Optional
         _chk(invstd, (g.Cin,), name='invstd')
         if mask is not None:
             _chk(mask, (y.numel() // 32,), dtype=torch.int32, name='relu_mask')
-        rows = lib().bdv_conv_dgrad_pl_stat_rows(ctypes.byref(g), PIECES) if use_pl else lib().bdv_conv_dgrad_stat_rows(ctypes.byref(g))
-        if rows <= 0:
-            check(-1, 'bdv_conv_dgrad_stat_rows')
-        partial = torch.empty((2, rows, g.Cin), dtype=torch.float32, device=dy.device)
+        partial = torch.empty((2, plan.stat_rows, g.Cin), dtype=torch.float32, device=dy.device)
         if relu_affine is not None:
             if mask is not None:
                 raise ValueError('conv_dgrad: a ReLU mask and a derived ReLU sign exclude each other')
@@ -415,20 +414,14 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, g: ConvGeom, add_src: Optional
                           partial.data_ptr(), relu_affine[0].data_ptr() if relu_affine is not None else None,
                           relu_affine[1].data_ptr() if relu_affine is not None else None)
     ws = _conv_ws(g, 1, dy.device, ws_tag)
-    if use_pl:
-        _, planes_d = weight_planes(w, g)
+    if use_x3:
+        planes_d = weight_planes(w, g)[1] if plan.reads_planes else None
         check(lib().bdv_conv_dgrad_pl(_p(dy), _p(w), _p(planes_d), _p(dx), _p(add_src), _p(add_mask_src), ctypes.byref(g),
                                       ctypes.byref(fuse) if fuse is not None else None, _p(ws), ws.numel(), PIECES, _stream()),
               'bdv_conv_dgrad_pl')
-        return dx if bn_stats is None else (dx, partial)
-    if use_x3 and g.Cin % 128 == 0:
-        w_t = w.permute(1, 2, 3, 0).contiguous()            # (R, S, Cin, Cout): contraction index contiguous
-        check(lib().bdv_conv_dgrad_x3(_p(dy), _p(w), _p(w_t), _p(dx), _p(add_src), _p(add_mask_src), ctypes.byref(g),
-                                      ctypes.byref(fuse) if fuse is not None else None, _p(ws), ws.numel(), _stream()),
-              'bdv_conv_dgrad_x3')
-        return dx if bn_stats is None else (dx, partial)
-    check(lib().bdv_conv_dgrad(_p(dy), _p(w), _p(dx), _p(add_src), _p(add_mask_src), ctypes.byref(g),
-                               ctypes.byref(fuse) if fuse is not None else None, _p(ws), ws.numel(), _stream()), 'bdv_conv_dgrad')
+    else:
+        check(lib().bdv_conv_dgrad(_p(dy), _p(w), _p(dx), _p(add_src), _p(add_mask_src), ctypes.byref(g),
+                                   ctypes.byref(fuse) if fuse is not None else None, _p(ws), ws.numel(), _stream()), 'bdv_conv_dgrad')
     return dx if bn_stats is None else (dx, partial)
 
 
@@ -446,8 +439,8 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, g: ConvGeom, dw: Optional[torc
         slab, _ = conv_wgrad_partial(dy, x, g, x3=True, dw=dw, pre_bn=pre_bn)
         wgrad_reduce_batched([(slab, dw)], beta=beta)
         return dw
-    if pre_bn is not None:
-        raise ValueError('conv_wgrad: pre_bn needs the bf16-piece plane kernel')
+    _chk_bf16_arith(g, False, 'conv_wgrad')
+    conv_plan(g, 'wgrad', False, pre_bn is not None)       # refuses pre_bn, temporal taps: the fp32-MFMA kernel has neither
     ws = _conv_ws(g, 2, dy.device, ws_tag)
     check(lib().bdv_conv_wgrad(_p(dy), _p(x), _p(dw), float(beta), ctypes.byref(g), _p(ws), ws.numel(), _stream()),
           'bdv_conv_wgrad')
@@ -1055,24 +1048,18 @@ def conv_wgrad_partial(dy: torch.Tensor, x: torch.Tensor, g: ConvGeom, x3: Optio
     _chk_conv(dy, (g.N, g.Ho, g.Wo, g.Cout), g, 'dy')
     _chk_conv(x, (_in_frames(g), g.H, g.W, g.Cin), g, 'x')
     use_x3 = WGRAD_X3 if x3 is None else x3
-    use_pl = use_x3 and USE_PL_WGRAD
-    if g.act_dtype == 1 and not (use_pl and PIECES == 1 and pre_bn is None):
-        raise ValueError("conv_wgrad_partial: bf16 tensors need set_conv_arith('bf16') and the plane kernel")
+    _chk_bf16_arith(g, use_x3, 'conv_wgrad_partial')
+    plan = conv_plan(g, 'wgrad', use_x3, pre_bn is not None)
     if pre_bn is not None:      # x = the producer's raw conv output; its BatchNorm + ReLU is applied in the loader
-        if not (use_pl and lib().bdv_conv_wgrad_pre_ok(ctypes.byref(g))):
-            raise ValueError('conv_wgrad_partial: pre_bn needs the bf16-piece plane kernel for this geometry')
         _chk(pre_bn[0], (g.Cin,), name='pre_scale')
         _chk(pre_bn[1], (g.Cin,), name='pre_shift')
-    splits = (lib().bdv_conv_wgrad_pl_splits if use_pl else lib().bdv_conv_wgrad_splits)(ctypes.byref(g))
-    if splits <= 0:
-        check(-1, 'bdv_conv_wgrad_splits')
-    slab = torch.empty((splits, g.Cout, _taps_r(g), g.S, g.Cin), dtype=torch.float32, device=dy.device)
-    fn = lib().bdv_conv_wgrad_partial_pl if use_pl else lib().bdv_conv_wgrad_partial_x3 if use_x3 else lib().bdv_conv_wgrad_partial
-    if use_pl:
-        check(fn(_p(dy), _p(x), ctypes.byref(g), _p(slab), slab.numel() * 4, PIECES, _p(pre_bn[0] if pre_bn is not None else None),
-                 _p(pre_bn[1] if pre_bn is not None else None), _stream()), 'bdv_conv_wgrad_partial_pl')
+    slab = torch.empty((plan.splits, g.Cout, _taps_r(g), g.S, g.Cin), dtype=torch.float32, device=dy.device)
+    if use_x3:
+        check(lib().bdv_conv_wgrad_partial_pl(_p(dy), _p(x), ctypes.byref(g), _p(slab), slab.numel() * 4, PIECES,
+                                              _p(pre_bn[0] if pre_bn is not None else None), _p(pre_bn[1] if pre_bn is not None else None),
+                                              _stream()), 'bdv_conv_wgrad_partial_pl')
     else:
-        check(fn(_p(dy), _p(x), ctypes.byref(g), _p(slab), slab.numel() * 4, _stream()), 'bdv_conv_wgrad_partial')
+        check(lib().bdv_conv_wgrad_partial(_p(dy), _p(x), ctypes.byref(g), _p(slab), slab.numel() * 4, _stream()), 'bdv_conv_wgrad_partial')
     if dw is None:
         dw = torch.empty((g.Cout, _taps_r(g), g.S, g.Cin), dtype=torch.float32, device=dy.device)
     return slab, dw

@@ -95,7 +95,7 @@ class _Stem3dFn(torch.autograd.Function):
         # One kernel over all kt x kh x kw taps (the stem kernels of the bf16-piece arithmetic take temporal taps: output frame n
         # reads the input frames 2 n + dt - kt // 2 of its clip) when the clip length fits (T = 2 To); otherwise kt accumulated 2-D
         # convolutions over gathered frames.
-        fused = (T == 2 * To and K.FPROP_X3 and K.WGRAD_X3 and K.USE_PL_WGRAD and os.environ.get('BDVCIL_C4_X3', '1') != '0'
+        fused = (T == 2 * To and K.FPROP_X3 and K.WGRAD_X3 and os.environ.get('BDVCIL_C4_X3', '1') != '0'
                  and os.environ.get('BDVCIL_STEM3D_FUSED', '1') != '0')
         taps = []
         if fused:

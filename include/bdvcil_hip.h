@@ -59,7 +59,7 @@ typedef struct bdv_conv_geom {
                    * storage: N = B, H = T, W = H*W, R = k, S = 1, pad = k / 2, pad_w = 0. */
   int32_t Rt;     /* temporal filter taps of the I3D stem (UPSTREAM ResNet3d.conv1, conv1_kernel = (5, 7, 7),
                    * configs/_base_/models/i3d_r50.py:7); 0 or 1 = a 2-D convolution.  Rt > 1: Cin = 4 only, the bf16-piece
-                   * kernels only (bdv_conv_fprop_x3, bdv_conv_wgrad_partial_pl).  N = OUTPUT frames, T = output frames per
+                   * kernels only (bdv_conv_fprop_pl, bdv_conv_wgrad_partial_pl).  N = OUTPUT frames, T = output frames per
                    * clip; the input holds N * st_t frames and output frame n reads the input frames n * st_t + dt - Rt / 2 of
                    * its clip (zeros outside).  Weights [Cout][Rt][R][S][4]. */
   int32_t st_t;   /* temporal stride (1 or 2) when Rt > 1 */
@@ -73,20 +73,47 @@ int bdv_abi_version(void);
  * the sources it finds in-tree and refuses a stale build. */
 const char* bdv_source_hash(void);
 
-/* ---- convolution = implicit GEMM on v_mfma_f32_32x32x2_f32 --------------------------------
+/* ---- convolution = implicit GEMM on the MFMA pipes ------------------------------------------
  * fprop replaces F.conv2d inside ConvModule (+ UPSTREAM TemporalShift.shift when fold > 0:
  * channels [0,fold) read frame t+1, [fold,2fold) read frame t-1, zero at clip ends).
  * x [N,H,W,Cin], w [Cout,R,S,Cin], y [N,Ho,Wo,Cout].
  *
- * Workspaces: bdv_conv_workspace_bytes(g, kind) with kind 0 = fprop, 1 = dgrad, 2 = wgrad.  fprop/dgrad use it
- * for the K-split partial accumulators of the remainder tiles (tile counts that do not fill whole rounds of
- * co-resident workgroups on the 256 CUs); passing NULL disables the split (correct, slower on such shapes). */
+ * Two sets of entry points, one per arithmetic:
+ *   bdv_conv_fprop / _dgrad / _wgrad / _wgrad_partial        fp32 MFMA (v_mfma_f32_32x32x2_f32, an exact fp32 FMA chain);
+ *   bdv_conv_fprop_pl / _dgrad_pl / _wgrad_partial_pl        the bf16-piece entry points (`pieces` = 3, 2 or 1, below).
+ * Which kernel a call runs, whether it reads the weight planes and how large its side buffers are is ONE decision,
+ * bdv_conv_plan_query; the launches follow the same plan, so a buffer sized from the query is the buffer the kernel writes.
+ *
+ * Workspaces: bdv_conv_workspace_bytes(g, kind) with kind 0 = fprop, 1 = dgrad, 2 = wgrad (the fp32-MFMA bdv_conv_wgrad), for
+ * every arithmetic.  fprop/dgrad use it for the K-split partial accumulators of the remainder tiles (tile counts that do not
+ * fill whole rounds of co-resident workgroups on the 256 CUs); passing NULL disables the split (correct, slower on such shapes). */
 size_t bdv_conv_workspace_bytes(const bdv_conv_geom* g, int kind);
-/* bn_partial (optional): float[2][rows][Cout], rows = bdv_conv_fprop_stat_rows(g).  When given, the epilogue also
- * writes per-row-tile column sums of y and y*y (the BatchNorm batch statistics, fused: y is not re-read);
- * bdv_bn_train_finalize reduces them in fixed order. */
-int bdv_conv_fprop_stat_rows(const bdv_conv_geom* g);
-/* affine (optional, excludes bn_partial): eval-mode BatchNorm folded into the epilogue,
+
+/* The plan of one call.  kind: 0 fprop, 1 dgrad, 2 wgrad.  arith: 0 = the fp32-MFMA entry points, 1 / 2 / 3 = the bf16-piece
+ * entry points with that many pieces.  pre: the producer's BatchNorm is applied in the loader (pre_scale, below).
+ * Returns BDV_EINVAL (reason in bdv_last_error) where the library has no kernel for the request: dgrad of the Cin = 4 stem,
+ * bf16 storage (g->act_dtype) outside pieces = 1 or on a geometry without a plane kernel, pre on a shifted site, ... */
+#define BDV_CONV_F32 0       /* 4 waves, fp32 MFMA, 128 x 128 / 128 x 64 tiles */
+#define BDV_CONV_C4 1        /* the stem (Cin = 4) on fp32 MFMA */
+#define BDV_CONV_C4_X3 2     /* the stem on the bf16-piece K loop (also its temporal taps, Rt > 1) */
+#define BDV_CONV_X3 3        /* 4 waves, two workgroups per CU, bf16 pieces, the weight operand from the planes */
+#define BDV_CONV_PL 4        /* the plane kernels (8 waves, or the 4-wave 64 x 128 / 128 x 128 tiles) */
+#define BDV_CONV_WGRAD_F32 5 /* weight gradient on fp32 MFMA */
+#define BDV_CONV_WGRAD_PL 6  /* weight gradient, bf16 pieces split in the loader */
+typedef struct bdv_conv_plan {
+  int32_t family;       /* BDV_CONV_* */
+  int32_t reads_planes; /* fprop / dgrad: the launch needs planes_fprop / planes_dgrad (else they may be NULL and w is read) */
+  int32_t stat_rows;    /* fprop / dgrad: rows of the fused-statistics partial, float[2][stat_rows][C] (one per row tile of the
+                         * kernel that runs; a stride-2 dgrad has one block of rows per input-parity class) */
+  int32_t splits;       /* wgrad: the slab holds this many partial products of dw's size */
+  int32_t pre_ok;       /* fprop / wgrad: the same call with pre = 1 is available */
+  char kernel[128];     /* the main kernel as a profiler prints it, without the namespace (wgrad: up to the tile size) */
+} bdv_conv_plan;
+int bdv_conv_plan_query(const bdv_conv_geom* g, int kind, int arith, int pre, bdv_conv_plan* out);
+
+/* bn_partial (optional): float[2][stat_rows][Cout].  When given, the epilogue also writes per-row-tile column sums of y and
+ * y*y (the BatchNorm batch statistics, fused: y is not re-read); bdv_bn_train_finalize reduces them in fixed order.
+ * affine (optional, excludes bn_partial): eval-mode BatchNorm folded into the epilogue,
  * y = relu?(conv * scale[c] + shift[c] (+ residual)) with scale/shift from bdv_bn_eval_params: the inference and
  * frozen-teacher forwards (UPSTREAM Recognizer2D._do_test, libs/cil/cil.py:520-522) then have no bn_apply pass. */
 typedef struct bdv_conv_affine {
@@ -97,30 +124,21 @@ typedef struct bdv_conv_affine {
 } bdv_conv_affine;
 int bdv_conv_fprop(const float* x, const float* w, float* y, const bdv_conv_geom* g, float* bn_partial,
                    const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, void* stream);
-/* EXPERIMENTAL (off by default in the Python layer, BDVCIL_FPROP_X3=1): the same convolution with every fp32 product formed
- * from bf16 pieces -- each operand value is split in the loader into three round-to-nearest bf16 terms and six
- * v_mfma_f32_32x32x16_bf16 products per K-step are accumulated in fp32 (error of the order of fp32
- * rounding).  Same arguments, workspace and epilogues as bdv_conv_fprop; used for Cout % 128 == 0 and Cin % 32 == 0,
- * other shapes run the fp32-MFMA kernels. */
-int bdv_conv_fprop_x3(const float* x, const float* w, float* y, const bdv_conv_geom* g, float* bn_partial,
-                      const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, void* stream);
 
 /* BatchNorm-backward statistics fused into dgrad: dx (the gradient w.r.t. the BN(+ReLU) output of the PREVIOUS conv unit,
  * whose saved conv output is y) is reduced in the dgrad epilogue to partial[0][r][c] = sum(g), partial[1][r][c] =
- * sum(g * xhat) per 128-row tile r (g = dx * mask, xhat = (y - mean) * invstd; rows = bdv_conv_dgrad_stat_rows(g));
+ * sum(g * xhat) per row tile r (g = dx * mask, xhat = (y - mean) * invstd; stat_rows of the plan);
  * bdv_bn_backward(stat_partial = ...) then skips its own statistics pass.  Stride 2 needs a filter that
- * reaches every input pixel (R, S >= 2); the partial then has one block of rows per input-parity class
- * (bdv_conv_dgrad_stat_rows / bdv_conv_dgrad_pl_stat_rows give the total) and is zeroed by the call. */
+ * reaches every input pixel (R, S >= 2); the partial then has one block of rows per input-parity class and is zeroed by the call. */
 typedef struct bdv_bn_stat_fuse {
   const void* y;             /* [N,H,W,Cin] conv output of the previous unit (element type: the geometry's act_dtype) */
   const uint32_t* relu_mask; /* 1 bit per element of dx, or NULL (no ReLU, or the sign is derived: relu_scale) */
   const float* mean;         /* [Cin] saved batch mean */
   const float* invstd;       /* [Cin] */
-  float* partial;            /* float[2][rows][Cin] */
+  float* partial;            /* float[2][stat_rows][Cin] */
   const float* relu_scale;   /* optional [Cin] pair with relu_mask == NULL: the unit's ReLU sign is y * relu_scale + relu_shift > 0 */
   const float* relu_shift;   /* (units whose activation and mask were never written: bdv_conv_fprop_pl(pre_scale)) */
 } bdv_bn_stat_fuse;
-int bdv_conv_dgrad_stat_rows(const bdv_conv_geom* g);
 
 /* dgrad: dx[N,H,W,Cin] = unshift(conv_transpose(dy, w)) + (add_src ? add_src * mask : 0),
  * mask = bit e of add_mask_src (the ReLU sign mask written by bdv_bn_apply) when add_mask_src != NULL
@@ -129,12 +147,6 @@ int bdv_conv_dgrad_stat_rows(const bdv_conv_geom* g);
 int bdv_conv_dgrad(const float* dy, const float* w, float* dx, const float* add_src,
                    const uint32_t* add_mask_src, const bdv_conv_geom* g, const bdv_bn_stat_fuse* bn_stat, void* workspace,
                    size_t workspace_bytes, void* stream);
-/* EXPERIMENTAL counterpart of bdv_conv_fprop_x3 for the data gradient.  w_t = the weights transposed per filter tap,
- * (R*S, Cin, Cout) contiguous, so that both operands are contiguous along the contraction; used when Cin % 128 == 0,
- * other shapes run bdv_conv_dgrad's kernels on w. */
-int bdv_conv_dgrad_x3(const float* dy, const float* w, const float* w_t, float* dx, const float* add_src,
-                      const uint32_t* add_mask_src, const bdv_conv_geom* g, const bdv_bn_stat_fuse* bn_stat, void* workspace,
-                      size_t workspace_bytes, void* stream);
 
 /* Weights as bf16 planes for the default conv arithmetic (every fp32 product from three bf16 pieces per operand, six
  * v_mfma_f32_32x32x16_bf16 products, fp32 accumulate; replaces the same F.conv2d / autograd call sites as bdv_conv_fprop and
@@ -144,10 +156,9 @@ int bdv_conv_dgrad_x3(const float* dy, const float* w, const float* w_t, float* 
  *   planes_fprop  [piece][K-step = (ci / 32) * R*S + tap][co][ci % 32]
  *   planes_dgrad  [piece][tap][co / 32][ci][co % 32]
  * (either may be NULL; Cin and Cout multiples of 32).  bdv_conv_fprop_pl / bdv_conv_dgrad_pl take the planes beside w and
- * behave like bdv_conv_fprop / bdv_conv_dgrad (same epilogues, workspace = bdv_conv_workspace_bytes); shapes their
- * 8-wave kernels do not cover (Cout resp. Cin not a multiple of 128, the stem) run the other kernels on w.  The fused
- * statistics partials have bdv_conv_fprop_pl_stat_rows(g, pieces) / bdv_conv_dgrad_pl_stat_rows(g, pieces) rows (one per row
- * tile of the kernel that will run, 128 or 256 rows).
+ * behave like bdv_conv_fprop / bdv_conv_dgrad (same epilogues, workspace = bdv_conv_workspace_bytes).  They are THE bf16-piece
+ * entry points: sites without a plane kernel (the stem, 64 columns behind a 1x1 filter) run the bf16-piece stem kernel resp. the
+ * fp32-MFMA kernels on w, and for those (reads_planes = 0) the planes may be NULL -- what the former bdv_conv_*_x3 aliases ran.
  * pieces = 3 is the arithmetic described above.  pieces = 1 is the REDUCED-PRECISION arithmetic of BASELINE config 5 ("MFMA
  * fp16 tiles"; the reference's trainer is precision 32, libs/cil/cil.py:744-756, so there are no reference numerics for it):
  * each operand value is rounded to bf16 (only the hi plane is used), one v_mfma_f32_32x32x16_bf16 product per step, fp32
@@ -163,29 +174,17 @@ int bdv_conv_split_weights(const float* w, const bdv_conv_geom* g, void* planes_
  * (0 = 128x256, 1 = 256x128, 2 = 256x256, 3 = 256x64, 4 = 64x128 (dgrad, stride 1), 5 = 128x128 with four waves and two
  * workgroups per CU, where the tile divides the column count; 6 = none of them; -1 = the planner's rules). */
 int bdv_conv_debug_force_tile(int cfg);
-/* 1 when bdv_conv_fprop_pl (kind 0) / bdv_conv_dgrad_pl (kind 1) will read the weight planes for this geometry, 0 when it
- * runs a kernel that takes w (the caller then need not build the planes). */
-int bdv_conv_uses_planes(const bdv_conv_geom* g, int kind, int pieces);
-/* Name of the main kernel that a call with this geometry launches, as a profiler prints it (kind 0 fprop, 1 dgrad, 2 wgrad;
- * arith 0 = the fp32-MFMA entry points, 1 = the *_pl entry points, 2 = the same with pieces = 1, 3 = with pieces = 2).  For profiles and per-kernel
- * accounting. */
-int bdv_conv_kernel_name(const bdv_conv_geom* g, int kind, int arith, char* out, size_t n);
-int bdv_conv_fprop_pl_stat_rows(const bdv_conv_geom* g, int pieces);
-int bdv_conv_dgrad_pl_stat_rows(const bdv_conv_geom* g, int pieces);
 /* pre_scale / pre_shift (optional, [Cin] each): x is then the RAW output of the producing conv and the producer's train-mode
  * BatchNorm + ReLU, a = max(x * pre_scale[ci] + pre_shift[ci], 0), is applied in the loader (the same fused multiply-add as
  * bdv_bn_apply, bit-identical activations; halo / ragged lanes stay zero): the apply pass between the two convs, the activation
  * tensor and its ReLU mask are not needed for this consumer (UPSTREAM ConvModule conv -> bn -> relu chains inside Bottleneck /
- * BasicBlock).  Needs pieces = 3, no temporal shift, and bdv_conv_fprop_pre_ok(g); the statistics partial then has
- * bdv_conv_fprop_pre_stat_rows(g) rows. */
+ * BasicBlock).  Needs pieces = 3, no temporal shift, and a plan with pre = 1 (pre_ok), which also gives the statistics rows. */
 /* g->act_dtype = BDV_ACT_BF16: x, y and affine->residual are bf16 tensors (pieces = 1 only; the accumulators, the fused batch
  * statistics and the folded BatchNorm arithmetic stay fp32, y is rounded to nearest-even on store); same for dy / dx / add_src /
  * bn_stat->y of bdv_conv_dgrad_pl and dy / x of bdv_conv_wgrad_partial_pl (weight-gradient slabs stay fp32). */
 int bdv_conv_fprop_pl(const void* x, const float* w, const void* planes_fprop, void* y, const bdv_conv_geom* g,
                       float* bn_partial, const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, int pieces,
                       const float* pre_scale, const float* pre_shift, void* stream);
-int bdv_conv_fprop_pre_ok(const bdv_conv_geom* g);
-int bdv_conv_fprop_pre_stat_rows(const bdv_conv_geom* g);
 int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* planes_dgrad, void* dx, const void* add_src,
                       const uint32_t* add_mask_src, const bdv_conv_geom* g, const bdv_bn_stat_fuse* bn_stat, void* workspace,
                       size_t workspace_bytes, int pieces, void* stream);
@@ -195,30 +194,23 @@ int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* planes_dgrad, 
 int bdv_conv_wgrad(const float* dy, const float* x, float* dw, float beta, const bdv_conv_geom* g, void* workspace,
                    size_t workspace_bytes, void* stream);
 /* The same weight gradient in two steps, so that the split-K reductions of several layers run as ONE launch (a ResNet
- * stage's backward issues one instead of up to 19): bdv_conv_wgrad_partial leaves bdv_conv_wgrad_splits(g) partial
+ * stage's backward issues one instead of up to 19): bdv_conv_wgrad_partial leaves the plan's `splits` partial
  * products of dw's size in `slab` (caller-owned, alive until reduced); bdv_wgrad_reduce_batched computes
  * dws[k] = beta * dws[k] + sum of the splits[k] slices of slabs[k] for n <= BDV_MAX_REDUCE_ITEMS items (HOST arrays;
  * numels[k] = elements of dws[k], a multiple of 4), with the per-element summation order of bdv_conv_wgrad. */
 #define BDV_MAX_REDUCE_ITEMS 32
-int bdv_conv_wgrad_splits(const bdv_conv_geom* g);
 int bdv_conv_wgrad_partial(const float* dy, const float* x, const bdv_conv_geom* g, void* slab, size_t slab_bytes,
                            void* stream);
 int bdv_wgrad_reduce_batched(const float* const* slabs, float* const* dws, const int* splits, const int64_t* numels, int n,
                              float beta, void* stream);
-/* The weight gradient's main kernel of the default arithmetic for Cout and Cin multiples of 128 (other shapes run the kernels of
- * bdv_conv_wgrad_partial): 8 waves per workgroup, tiles of 128 / 256 output channels x 128 / 256 input channels of one tap,
- * both operand tiles split into bf16 pieces in the loader and read from LDS with ds_read_b64_tr_b16.  The slab holds
- * bdv_conv_wgrad_pl_splits(g) partial products of dw's size; reduce with bdv_wgrad_reduce_batched. */
-int bdv_conv_wgrad_pl_splits(const bdv_conv_geom* g);
-/* pre_scale / pre_shift as for bdv_conv_fprop_pl: x is the producer's raw conv output and the activation
- * max(x * pre_scale[ci] + pre_shift[ci], 0) is formed in the loader (needs bdv_conv_wgrad_pre_ok(g)). */
+/* The weight gradient's main kernel of the bf16-piece arithmetic: 8 waves per workgroup, tiles of 128 / 256 output channels x
+ * 128 / 256 input channels of one tap (4-wave forms for the 64-channel layers and the stem), both operand tiles split into bf16
+ * pieces in the loader and read from LDS with ds_read_b64_tr_b16; geometries without such a tile run bdv_conv_wgrad_partial's
+ * kernels.  The slab holds the plan's `splits` partial products of dw's size; reduce with bdv_wgrad_reduce_batched.
+ * pre_scale / pre_shift as for bdv_conv_fprop_pl: x is the producer's raw conv output and the activation
+ * max(x * pre_scale[ci] + pre_shift[ci], 0) is formed in the loader (a plan with pre = 1). */
 int bdv_conv_wgrad_partial_pl(const void* dy, const void* x, const bdv_conv_geom* g, void* slab, size_t slab_bytes,
                               int pieces, const float* pre_scale, const float* pre_shift, void* stream);
-int bdv_conv_wgrad_pre_ok(const bdv_conv_geom* g);
-/* EXPERIMENTAL counterpart of bdv_conv_fprop_x3 for the weight gradient's main kernel (128x128 tiles, i.e. Cout and Cin
- * multiples of 128; other shapes run the fp32-MFMA kernels).  Same slab layout and split count as bdv_conv_wgrad_partial. */
-int bdv_conv_wgrad_partial_x3(const float* dy, const float* x, const bdv_conv_geom* g, void* slab, size_t slab_bytes,
-                              void* stream);
 
 /* ---- BatchNorm2d (train + eval), fused with ReLU / residual add --------------------------
  * Replaces UPSTREAM ConvModule.bn (+ .activate, + block `out + identity`) and their autograd.

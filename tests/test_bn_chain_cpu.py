@@ -37,7 +37,7 @@ def test_header_binding_and_library_agree_on_the_new_symbols():
         assert a_new == a_old[:-1] + [ctypes.c_int, bd._lib.P, ctypes.c_size_t, bd._lib.P], new
         p_new, p_old = _header_params(hdr, new), _header_params(hdr, old)
         assert [re.sub(r'\s+', ' ', p) for p in p_new[:len(p_old) - 1]] == [re.sub(r'\s+', ' ', p) for p in p_old[:-1]], new
-    assert bd._lib.lib().bdv_abi_version() == bd._lib.ABI_VERSION == 32
+    assert bd._lib.lib().bdv_abi_version() == bd._lib.ABI_VERSION == 33
 
 
 def test_planner_and_scratch_size_answer_on_the_host():

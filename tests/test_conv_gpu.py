@@ -116,7 +116,7 @@ def test_wgrad(case, dev, conv_arith):
 
 @pytest.mark.parametrize('case', [c for c in CASES if c[4] % 128 == 0 and c[3] % 32 == 0])
 def test_fprop_from_bf16_pieces(case, dev):
-    """bdv_conv_fprop_x3 (the default arithmetic): fp32 products formed from three bf16 pieces per operand value.  Same tolerance as
+    """bdv_conv_fprop_pl (the default arithmetic): fp32 products formed from three bf16 pieces per operand value.  Same tolerance as
     the fp32-MFMA kernel against the CPU reference, and close to the fp32-MFMA result itself; fused statistics and the
     folded eval-mode BatchNorm go through the same epilogues."""
     from bdvcil_amd import kernels as K
@@ -142,7 +142,7 @@ def test_fprop_from_bf16_pieces(case, dev):
 @pytest.mark.parametrize('case', [c for c in CASES if c[3] % 128 == 0])
 @pytest.mark.parametrize('with_add', [False, True])
 def test_dgrad_from_bf16_pieces(case, with_add, dev):
-    """bdv_conv_dgrad_x3 (the default arithmetic) against the CPU reference and the fp32-MFMA kernel, with the residual add, the
+    """bdv_conv_dgrad_pl (the default arithmetic) against the CPU reference and the fp32-MFMA kernel, with the residual add, the
     temporal un-shift and the stride-2 parity classes going through the unchanged epilogue."""
     from bdvcil_amd import kernels as K
     N, H, W, Cin, Cout, R, st, pad, T, fold = case
@@ -165,7 +165,7 @@ def test_dgrad_from_bf16_pieces(case, with_add, dev):
 
 @pytest.mark.parametrize('case', [c for c in CASES if c[3] % 64 == 0 or c[3] == 4])
 def test_wgrad_from_bf16_pieces(case, dev):
-    """bdv_conv_wgrad_partial_x3 (the default arithmetic) + the batched reduction against the CPU reference and the fp32-MFMA kernel."""
+    """bdv_conv_wgrad_partial_pl (the default arithmetic) + the batched reduction against the CPU reference and the fp32-MFMA kernel."""
     from bdvcil_amd import kernels as K
     N, H, W, Cin, Cout, R, st, pad, T, fold = case
     x, w = _mk(case, 2)

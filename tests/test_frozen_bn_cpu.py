@@ -156,7 +156,7 @@ def test_entry_point_in_header_binding_and_library():
     assert res is ctypes.c_int and len(args) == len(params), (len(args), params)
     for p, a in zip(params, args):
         assert ('*' in p) == (a is bd._lib.P), (p, a)
-    assert bd._lib.lib().bdv_abi_version() == bd._lib.ABI_VERSION == 32
+    assert bd._lib.lib().bdv_abi_version() == bd._lib.ABI_VERSION == 33
     assert callable(bd.kernels.bn_eval_backward)
 
 

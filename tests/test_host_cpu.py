@@ -46,6 +46,21 @@ def test_conv_geom_mirror_matches_the_header():
     assert ctypes.sizeof(bd._lib.ConvGeom) == 4 * len(fields)
 
 
+def test_conv_plan_mirror_matches_the_header():
+    """``_lib.ConvPlan`` (ctypes) lists the fields of ``bdv_conv_plan`` in the header's order: five int32, then the kernel name."""
+    hdr = open(os.path.join(ROOT, 'include', 'bdvcil_hip.h')).read()
+    body = re.search(r'typedef struct bdv_conv_plan \{(.*?)\} bdv_conv_plan;', hdr, re.S).group(1)
+    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
+    ints = [n.strip() for decl in re.findall(r'int32_t\s+([^;]+);', body) for n in decl.split(',')]
+    name, size = re.search(r'char\s+(\w+)\[(\d+)\];', body).groups()
+    assert body.index('char') > body.rindex('int32_t')              # the array comes last
+    fields = bd._lib.ConvPlan._fields_
+    assert [n for n, _ in fields] == ints + [name]
+    assert all(t is ctypes.c_int32 for _, t in fields[:-1]) and fields[-1][1] is ctypes.c_char * int(size)
+    assert ctypes.sizeof(bd._lib.ConvPlan) == 4 * len(ints) + int(size)
+    assert bd._lib.ConvPlan.kernel.offset == 4 * len(ints)
+
+
 def test_stale_library_is_refused(monkeypatch):
     """The binding loads only a library built from the sources next to it (bdv_source_hash == sha256 of csrc + header)."""
     L = bd._lib

@@ -100,7 +100,7 @@ def test_header_binding_and_library_agree_on_the_new_symbols():
         for p, a in zip(params, args):       # pointers and arrays against pointers, scalars against scalars
             assert ('*' in p or '[' in p) == (a is bd._lib.P or a is bd._lib._F3), (name, p, a)
     assert 'ragged.hip' in bd._lib.HASHED_SOURCES
-    assert bd._lib.lib().bdv_abi_version() == bd._lib.ABI_VERSION == 32
+    assert bd._lib.lib().bdv_abi_version() == bd._lib.ABI_VERSION == 33
     assert hasattr(bd.kernels, 'resize_linear_ragged_u8') and hasattr(bd.kernels, 'crop_normalize_ragged_u8')
 
 

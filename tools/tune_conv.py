@@ -1,6 +1,6 @@
 """Per-site timing of every kernel choice for fprop / dgrad at the TSM-R50 sites (N = 256 frames), in ONE process (timings
-taken on different boxes differ by several per cent): the round-1 bf16-piece kernels (operands split in the K loop, two
-workgroups per CU) and the 8-wave kernels on pre-split weight planes with each tile configuration forced in turn.
+taken on different boxes differ by several per cent): the two-workgroups-per-CU bf16-piece kernels and the plane kernels with
+each tile configuration forced in turn, all on pre-split weight planes.
 Prints one row per site and direction with the time of every choice and the best one.  FUSED=1 times the calls as the
 training step makes them: fprop with the BatchNorm statistics in its epilogue; dgrad of a block's conv1 (the shifted sites) with
 the identity-branch gradient + ReLU mask added and the BatchNorm-backward statistics taken, the other stride-1 dgrads with the
@@ -16,7 +16,7 @@ from bdvcil_amd._lib import check, lib
 from tools.bench_conv import SHAPES, timeit  # noqa: E402
 
 N = int(os.environ.get('N', 256))
-K.set_conv_arith(os.environ.get('ARITH', 'bf16x3'))      # 'bf16x2': the r1 columns then still are three-piece kernels
+K.set_conv_arith(os.environ.get('ARITH', 'bf16x3'))      # 'bf16x2': the r1p column then still is the three-piece kernel
 FUSED = os.environ.get('FUSED', '0') == '1'
 dev = torch.device('cuda:0')
 CFG = {0: '128x256', 1: '256x128', 2: '256x256', 3: '256x64', 4: '64x128', 5: '128x128'}
@@ -27,7 +27,7 @@ def applicable(c, ncols):
     return ncols % bn == 0
 
 
-print(f'{"site":30s} dir    {"r1 x3":>8s} {"r1 planes":>9s} ' + ' '.join(f'{CFG[c]:>8s}' for c in range(6)) + '   best')
+print(f'{"site":30s} dir    {"r1 planes":>9s} ' + ' '.join(f'{CFG[c]:>8s}' for c in range(6)) + '   best')
 tot = {}
 for (Cin, Cout, k, st, H, cnt, sh) in SHAPES:
     if Cin % 32 != 0:
@@ -49,9 +49,6 @@ for (Cin, Cout, k, st, H, cnt, sh) in SHAPES:
             else:
                 dg = lambda: K.conv_dgrad(dy, w, g, bn_stats=stats)  # noqa: E731
     for name, ncols, fn in (('fprop', Cout, fp), ('dgrad', Cin, dg)):
-        K.USE_PL = False
-        t_old = timeit(fn)
-        K.USE_PL = True
         check(lib().bdv_conv_debug_force_tile(6), 'force')      # two-workgroup kernels with the weights from the planes
         t_r1p = timeit(fn)
         ts = {}
@@ -62,12 +59,12 @@ for (Cin, Cout, k, st, H, cnt, sh) in SHAPES:
             ts[c] = timeit(fn)
         check(lib().bdv_conv_debug_force_tile(-1), 'force')
         t_auto = timeit(fn)
-        best = min([('r1', t_old), ('r1p', t_r1p)] + [(CFG[c], t) for c, t in ts.items()], key=lambda q: q[1])
-        row = f'{str((Cin, Cout, k, st, H)):26s} x{cnt:<2d} {name}  {t_old:8.3f} {t_r1p:9.3f} ' + ' '.join(
+        best = min([('r1p', t_r1p)] + [(CFG[c], t) for c, t in ts.items()], key=lambda q: q[1])
+        row = f'{str((Cin, Cout, k, st, H)):26s} x{cnt:<2d} {name}  {t_r1p:9.3f} ' + ' '.join(
             f'{ts[c]:8.3f}' if c in ts else f'{"-":>8s}' for c in range(6)) + f'   {best[0]:8s} auto {t_auto:.3f}'
         print(row, flush=True)
-        for key, t in [('r1', t_old), ('r1p', t_r1p), ('auto', t_auto), ('best', best[1])]:
+        for key, t in [('r1p', t_r1p), ('auto', t_auto), ('best', best[1])]:
             tot[(name, key)] = tot.get((name, key), 0.0) + t * cnt
 for name in ('fprop', 'dgrad'):
-    print(f'total {name}: r1 x3 {tot[(name, "r1")]:.2f} ms, r1 on planes {tot[(name, "r1p")]:.2f} ms, planner {tot[(name, "auto")]:.2f} ms, '
+    print(f'total {name}: r1 on planes {tot[(name, "r1p")]:.2f} ms, planner {tot[(name, "auto")]:.2f} ms, '
           f'best per site {tot[(name, "best")]:.2f} ms')
