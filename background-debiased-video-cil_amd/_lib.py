@@ -77,6 +77,12 @@ SIGNATURES = {
     'bdv_conv_wgrad_partial': (c_int, [P, P, POINTER(ConvGeom), P, c_size_t, P]),
     'bdv_conv_wgrad_partial_pl': (c_int, [P, P, POINTER(ConvGeom), P, c_size_t, c_int, P, P, P]),
     'bdv_wgrad_reduce_batched': (c_int, [P, P, P, P, c_int, c_float, P]),
+    'bdv_f16x2_amax': (c_int, [P, c_int64, P, P]),
+    'bdv_f16x2_scale': (c_float, [c_float]),
+    'bdv_conv_split_weights_f16x2': (c_int, [P, POINTER(ConvGeom), P, P, P]),
+    'bdv_conv_fprop_f16x2': (c_int, [P, P, P, P, P, POINTER(ConvGeom), P, POINTER(ConvAffine), P, c_size_t, P, P, P]),
+    'bdv_conv_dgrad_f16x2': (c_int, [P, P, P, P, P, P, P, POINTER(ConvGeom), POINTER(BnStatFuse), P, c_size_t, P]),
+    'bdv_conv_wgrad_partial_f16x2': (c_int, [P, P, P, P, POINTER(ConvGeom), P, c_size_t, P, P, P]),
     'bdv_bn_workspace_bytes': (c_size_t, [c_int64, c_int]),
     'bdv_bn_train_stats': (c_int, [P, c_int64, c_int, P, P, c_float, c_float, P, P, P, P, P, P, P, c_size_t, P]),
     'bdv_bn_train_finalize': (c_int, [P, c_int, c_int64, c_int, P, P, c_float, c_float, P, P, P, P, P, P, P]),

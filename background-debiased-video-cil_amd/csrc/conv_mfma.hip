@@ -1691,11 +1691,75 @@ __device__ __forceinline__ int pl_frag_off(int row0, int s, int lane) {
   return pl_off(row0 + r, 2 * s + h);
 }
 
+// ---- "f16x2": two fp16 pieces per operand -------------------------------------------------------------
+// An operand tensor t travels with a device-resident word holding the bits of an upper bound of max|t| (bdv_f16x2_amax; the
+// weights' word lies behind their two planes).  Its scale S_t = 2^(14 - floor(log2 max|t|)) puts the largest entry into
+// [2^14, 2^15), the top binade of fp16 in which rounding cannot reach infinity; x = t * S_t is cut into hi = f16(x) and
+// lo = f16(x - hi) (11 + 11 significand bits and a sign), the K loop forms hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_f16, and
+// the accumulators are multiplied once by 1 / (S_a * S_w) before any epilogue sees them.  All three factors are powers of two.
+// The exponent of S_t is clamped to [-113, 126] (a maximum of 2^127 still lands below 2^15; maxima below 2^-112 keep the largest
+// normal scale and lose bits), the exponent of the product's inverse to the normal range; an all-zero tensor has S_t = 1.
+// The piece type is a template parameter of the plane kernels: everything but the split and the MFMA opcode is the NP = 2 code.
+struct Bf16Pieces {};
+struct F16Pieces {};
+template <typename PT>
+constexpr bool kF16 = std::is_same<PT, F16Pieces>::value;
+// the amax words of the two operands of a launch (null for the bf16 pieces)
+struct PieceScales {
+  const unsigned* a;
+  const unsigned* b;
+};
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+__host__ __device__ __forceinline__ unsigned f16x2_scale_bits(unsigned amax_bits) {
+  if ((amax_bits & 0x7fffffffu) == 0u) return 0x3f800000u;
+  int e = 141 - (int)((amax_bits >> 23) & 0xffu);   // 14 - floor(log2 max); a subnormal maximum counts as 2^-127 and is clamped
+  e = e < -113 ? -113 : e > 126 ? 126 : e;
+  return (unsigned)(e + 127) << 23;
+}
+__host__ __device__ __forceinline__ unsigned f16x2_unscale_bits(unsigned sa_bits, unsigned sb_bits) {
+  int b = 381 - (int)(sa_bits >> 23) - (int)(sb_bits >> 23);   // biased exponent of 1 / (S_a * S_b)
+  b = b < 1 ? 1 : b > 254 ? 254 : b;
+  return (unsigned)b << 23;
+}
+__device__ __forceinline__ unsigned pack_f16x2(float a, float b) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){a, b}, f16x2_t));   // round to nearest even
+}
+__device__ __forceinline__ f32x2_t unpack_f16x2(unsigned u) { return __builtin_convertvector(__builtin_bit_cast(f16x2_t, u), f32x2_t); }
+__device__ __forceinline__ void split2_f16_pairs(const float4 v, float scale, u32x2_t& hi, u32x2_t& lo) {
+  const float x = v.x * scale, y = v.y * scale, z = v.z * scale, w = v.w * scale;
+  const unsigned h0 = pack_f16x2(x, y), h1 = pack_f16x2(z, w);
+  const f32x2_t f0 = unpack_f16x2(h0), f1 = unpack_f16x2(h1);
+  hi = (u32x2_t){h0, h1};
+  lo = (u32x2_t){pack_f16x2(x - f0.x, y - f0.y), pack_f16x2(z - f1.x, w - f1.y)};
+}
+// one 32x32x16 product of two pieces (the fragments are carried as bf16x8_t bits whatever the piece type)
+template <typename PT>
+__device__ __forceinline__ f32x16 mfma_piece(const bf16x8_t a, const bf16x8_t b, const f32x16 c) {
+  if constexpr (kF16<PT>) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+template <typename PT, int TM, int TN>
+__device__ __forceinline__ void f16x2_unscale(f32x16 (&acc)[TM][TN], const PieceScales ps) {
+  if constexpr (kF16<PT>) {
+    const float inv = __builtin_bit_cast(float, f16x2_unscale_bits(f16x2_scale_bits(*ps.a), f16x2_scale_bits(*ps.b)));
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] *= inv;
+  }
+}
+template <typename PT>
+__device__ __forceinline__ float f16x2_scale(const unsigned* amax) {
+  if constexpr (kF16<PT>) return __builtin_bit_cast(float, f16x2_scale_bits(*amax));
+  else return 1.f;
+}
+
 // NP = 3: the six piece products (fp32-level result).  NP = 1: only the leading bf16 piece of each operand, one MFMA product
 // per step -- the reduced-precision arithmetic of BASELINE config 5 (bf16 operands, fp32 accumulate), see bdv_conv_fprop_pl.
 // NP = 2: the two leading pieces of each operand (16 significand bits) and the three products hi*hi + hi*mid + mid*hi: dropped
 // terms <= 2^-16 (mid*mid) + 2 * 2^-17 (the operands' remainders) relative per product -- between TF32 (2^-11) and fp32.
-template <int BM, int BN, int WM, int WN, int NP = 3>
+template <int BM, int BN, int WM, int WN, int NP = 3, typename PT = Bf16Pieces>
 __device__ __forceinline__ void mma_stage_pl(const unsigned char* __restrict__ As, const unsigned char* __restrict__ Bs,
                                              f32x16 (&acc)[BM / WM / 32][BN / WN / 32], const int (&fa)[2], const int (&fb)[2]) {
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
@@ -1720,17 +1784,25 @@ __device__ __forceinline__ void mma_stage_pl(const unsigned char* __restrict__ A
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][i], b[0][j], acc[i][j], 0, 0, 0);
         }
         if constexpr (NP >= 2) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], b[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][i], b[0][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = mfma_piece<PT>(a[0][i], b[1][j], acc[i][j]);
+          acc[i][j] = mfma_piece<PT>(a[1][i], b[0][j], acc[i][j]);
         }
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], b[0][j], acc[i][j], 0, 0, 0);
+        acc[i][j] = mfma_piece<PT>(a[0][i], b[0][j], acc[i][j]);
       }
   }
 }
 
 // fp32 x 4 -> the three planes (NP = 1: the leading one) of a stage image at the thread's precomputed byte offset
-template <int NP = 3>
-__device__ __forceinline__ void pl_split_store_at(unsigned char* __restrict__ q, int plane_bytes, const float4 v) {
+template <int NP = 3, typename PT = Bf16Pieces>
+__device__ __forceinline__ void pl_split_store_at(unsigned char* __restrict__ q, int plane_bytes, const float4 v, float scale = 1.f) {
+  if constexpr (kF16<PT>) {
+    static_assert(NP == 2, "fp16 pieces: two per operand");
+    u32x2_t hi, lo;
+    split2_f16_pairs(v, scale, hi, lo);
+    *reinterpret_cast<u32x2_t*>(q) = hi;
+    *reinterpret_cast<u32x2_t*>(q + plane_bytes) = lo;
+    return;
+  }
   if constexpr (NP == 1) {
     *reinterpret_cast<u32x2_t*>(q) = bf16_hi_pairs(v);
     return;
@@ -1781,6 +1853,78 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
     D[o] = tile[0][tx][ci_l];
     D[plane + o] = tile[1][tx][ci_l];
     D[2 * plane + o] = tile[2][tx][ci_l];
+  }
+}
+
+// ---- fp16 pieces: a tensor's amax word, and the weights' planes ---------------------------------------------------------------
+// amax[0] = max(amax[0], bits of max|t|): |x| of an fp32 number orders like its bit pattern, so an integer atomicMax gives the
+// maximum whatever the order of arrival (bit-reproducible; NaN bits sort above infinity and propagate).  HBM-bound: 16-byte loads,
+// one atomic per workgroup.  The caller zeroes the word.
+__global__ __launch_bounds__(256) void f16x2_amax_kernel(const float* __restrict__ t, long long n, unsigned* __restrict__ amax) {
+  __shared__ unsigned wave_max[4];
+  const long long n4 = n >> 2;
+  unsigned m = 0u;
+  const uint4* const t4 = reinterpret_cast<const uint4*>(t);
+  const long long stride = (long long)gridDim.x * 256;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  for (; i + 3 * stride < n4; i += 4 * stride) {   // four independent 16-byte loads in flight per thread
+    const uint4 v0 = t4[i], v1 = t4[i + stride], v2 = t4[i + 2 * stride], v3 = t4[i + 3 * stride];
+    const unsigned m0 = max(max(v0.x & 0x7fffffffu, v0.y & 0x7fffffffu), max(v0.z & 0x7fffffffu, v0.w & 0x7fffffffu));
+    const unsigned m1 = max(max(v1.x & 0x7fffffffu, v1.y & 0x7fffffffu), max(v1.z & 0x7fffffffu, v1.w & 0x7fffffffu));
+    const unsigned m2 = max(max(v2.x & 0x7fffffffu, v2.y & 0x7fffffffu), max(v2.z & 0x7fffffffu, v2.w & 0x7fffffffu));
+    const unsigned m3 = max(max(v3.x & 0x7fffffffu, v3.y & 0x7fffffffu), max(v3.z & 0x7fffffffu, v3.w & 0x7fffffffu));
+    m = max(m, max(max(m0, m1), max(m2, m3)));
+  }
+  for (; i < n4; i += stride) {
+    const uint4 v = t4[i];
+    m = max(m, max(max(v.x & 0x7fffffffu, v.y & 0x7fffffffu), max(v.z & 0x7fffffffu, v.w & 0x7fffffffu)));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n & 3)) m = max(m, __builtin_bit_cast(unsigned, t[4 * n4 + threadIdx.x]) & 0x7fffffffu);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d, 64));
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
+    if (m != 0u) atomicMax(amax, m);
+  }
+}
+
+// split_weights_kernel for fp16 pieces: hi = f16(w * S_w), lo = f16(w * S_w - hi) into planes 0 and 1 of the same two layouts; the
+// third plane's place starts with the weight's amax word (read here from `amax`, copied to `amax_copy`, the other layout's).
+__global__ __launch_bounds__(256) void split_weights_f16_kernel(const float* __restrict__ w, unsigned short* __restrict__ F,
+                                                                 unsigned short* __restrict__ D, int Cout, int RS, int Cin,
+                                                                 const unsigned* __restrict__ amax, unsigned* __restrict__ amax_copy) {
+  __shared__ unsigned short tile[2][32][34];
+  const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32, tap = blockIdx.z;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const size_t plane = (size_t)Cout * RS * Cin;
+  const unsigned amax_bits = *amax;
+  const float scale = __builtin_bit_cast(float, f16x2_scale_bits(amax_bits));
+  if (amax_copy != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *amax_copy = amax_bits;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int co_l = ty + 8 * p;
+    const float a = w[((size_t)(co0 + co_l) * RS + tap) * Cin + ci0 + tx] * scale;
+    const _Float16 hi = (_Float16)a;
+    const _Float16 lo = (_Float16)(a - (float)hi);
+    const unsigned short h16 = __builtin_bit_cast(unsigned short, hi), l16 = __builtin_bit_cast(unsigned short, lo);
+    if (F != nullptr) {
+      const size_t o = (((size_t)(ci0 >> 5) * RS + tap) * Cout + co0 + co_l) * 32 + tx;
+      F[o] = h16;
+      F[plane + o] = l16;
+    }
+    tile[0][co_l][tx] = h16;
+    tile[1][co_l][tx] = l16;
+  }
+  if (D == nullptr) return;
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int ci_l = ty + 8 * p;  // tx = co within the chunk
+    const size_t o = (((size_t)tap * (Cout >> 5) + (co0 >> 5)) * Cin + ci0 + ci_l) * 32 + tx;
+    D[o] = tile[0][tx][ci_l];
+    D[plane + o] = tile[1][tx][ci_l];
   }
 }
 
@@ -1858,11 +2002,13 @@ constexpr int pl_waves_per_simd(int waves, int np, bool fits128) { return np == 
 
 // ---- fprop ------------------------------------------------------------------------------------
 // ES: bytes per element of x / y / the residual (4 = fp32, 2 = bf16 storage: NP = 1 only, the loader's conversion is then exact)
-template <int BM, int BN, int WM, int WN, int NBUF, int NP = 3, bool PRE = false, int ES = 4>
+template <int BM, int BN, int WM, int WN, int NBUF, int NP = 3, bool PRE = false, int ES = 4, typename PT = Bf16Pieces>
 __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 64 || (BM == 128 && BN == 256))) void conv_fprop_pl_kernel(const void* __restrict__ x,
                                                                                       const unsigned short* __restrict__ wp,
                                                                                       void* __restrict__ y, Geom g, int NT, Work wk,
-                                                                                      float* __restrict__ slab, FpropEpi epi) {
+                                                                                      float* __restrict__ slab, FpropEpi epi,
+                                                                                      PieceScales ps) {
+  static_assert(!kF16<PT> || (NP == 2 && !PRE && ES == 4), "fp16 pieces: two per operand, fp32 tensors, no BatchNorm in the loader");
   constexpr int NTHR = 64 * WM * WN;
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
   // a thread's unit of the activation tile is 16 bytes: 4 fp32 values (8 threads per 32-deep row) or 8 bf16 values (4 threads per
@@ -1963,6 +2109,7 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
   const int st_a = ES == 2 ? pl_off(arow, kg) : pl_off(arow, kg >> 1) + 8 * (kg & 1), st_b = pl_off(brow, bc);
   const int fa[2] = {pl_frag_off(32 * wm, 0, lane), pl_frag_off(32 * wm, 1, lane)};
   const int fb[2] = {pl_frag_off(32 * wn, 0, lane), pl_frag_off(32 * wn, 1, lane)};
+  const float sc_a = f16x2_scale<PT>(ps.a);
   auto store = [&](int stage, auto set) __attribute__((always_inline)) {
     constexpr int SET = decltype(set)::value;
     unsigned char* const As = smem_b + stage * STAGE;
@@ -1978,7 +2125,7 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
         v.w = ok ? fmaxf(fmaf(v.w, psc[SET].w, psh[SET].w), 0.f) : 0.f;
       }
       if constexpr (ES == 2) *reinterpret_cast<float4*>(As + st_a + (NTHR / KG) * p * 64) = v;
-      else pl_split_store_at<NP>(As + st_a + (NTHR / KG) * p * 64, PA, v);
+      else pl_split_store_at<NP, PT>(As + st_a + (NTHR / KG) * p * 64, PA, v, sc_a);
     }
     if (b_active) {
 #pragma unroll
@@ -1992,7 +2139,7 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
 
   if constexpr (NBUF == 2) {
     pl_pipeline2(it.ke - it.kb, load, store, [&](int stage) __attribute__((always_inline)) {
-      mma_stage_pl<BM, BN, WM, WN, NP>(smem_b + stage * STAGE, smem_b + stage * STAGE + NP * PA, acc, fa, fb);
+      mma_stage_pl<BM, BN, WM, WN, NP, PT>(smem_b + stage * STAGE, smem_b + stage * STAGE + NP * PA, acc, fa, fb);
     }, g.stagger != 0 && wave >= WM * WN / 2);
   } else {
     load(PlSet0{});
@@ -2002,10 +2149,11 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
       __syncthreads();
       if (kt == it.kb) BDV_STAMP(1);
       if (kt + 1 < it.ke) load(PlSet0{});
-      mma_stage_pl<BM, BN, WM, WN, NP>(smem_b, smem_b + NP * PA, acc, fa, fb);
+      mma_stage_pl<BM, BN, WM, WN, NP, PT>(smem_b, smem_b + NP * PA, acc, fa, fb);
     }
   }
   BDV_STAMP(2);
+  f16x2_unscale<PT>(acc, ps);   // fp16 pieces: back to the operands' scale before partials, statistics and epilogue
 
   if (it.pslot >= 0) {
     store_partial<TM, TN, NTHR>(slab, it.pslot, acc, tid);
@@ -2018,14 +2166,15 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
 
 // ---- dgrad ------------------------------------------------------------------------------------
 // dp = the D planes of bdv_conv_split_weights: B rows = input channels ci, contraction over (tap, co) with co contiguous.
-template <int BM, int BN, int WM, int WN, int NBUF, int NP = 3, int ES = 4>
+template <int BM, int BN, int WM, int WN, int NBUF, int NP = 3, int ES = 4, typename PT = Bf16Pieces>
 __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM * WN, NP, BN == 64)) void conv_dgrad_pl_kernel(const void* __restrict__ dy,
                                                                                       const unsigned short* __restrict__ dp,
                                                                                       void* __restrict__ dx,
                                                                                       const void* __restrict__ add_src,
                                                                                       const uint32_t* __restrict__ add_mask, Geom g,
                                                                                       int NT, Work wk, float* __restrict__ slab,
-                                                                                      BnStat stat) {
+                                                                                      BnStat stat, PieceScales ps) {
+  static_assert(!kF16<PT> || (NP == 2 && ES == 4), "fp16 pieces: two per operand, fp32 tensors");
   constexpr int NTHR = 64 * WM * WN;
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
   constexpr int KG = ES == 2 ? 4 : 8;   // threads per 32-deep row of the activation tile: 16 bytes each (conv_fprop_pl_kernel)
@@ -2136,6 +2285,7 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
   const int st_a = ES == 2 ? pl_off(arow, kg) : pl_off(arow, kg >> 1) + 8 * (kg & 1), st_b = pl_off(brow, bc);
   const int fa[2] = {pl_frag_off(32 * wm, 0, lane), pl_frag_off(32 * wm, 1, lane)};
   const int fb[2] = {pl_frag_off(32 * wn, 0, lane), pl_frag_off(32 * wn, 1, lane)};
+  const float sc_a = f16x2_scale<PT>(ps.a);
   auto store = [&](int stage, auto set) __attribute__((always_inline)) {
     constexpr int SET = decltype(set)::value;
     unsigned char* const As = smem_b + stage * STAGE;
@@ -2143,7 +2293,7 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
       if constexpr (ES == 2) *reinterpret_cast<float4*>(As + st_a + (NTHR / KG) * p * 64) = ra[SET][p];
-      else pl_split_store_at<NP>(As + st_a + (NTHR / KG) * p * 64, PA, ra[SET][p]);
+      else pl_split_store_at<NP, PT>(As + st_a + (NTHR / KG) * p * 64, PA, ra[SET][p], sc_a);
     }
     if (b_active) {
 #pragma unroll
@@ -2159,7 +2309,7 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
   if (it.ke > it.kb) {
     if constexpr (NBUF == 2) {
       pl_pipeline2(it.ke - it.kb, load, store, [&](int stage) __attribute__((always_inline)) {
-        mma_stage_pl<BM, BN, WM, WN, NP>(smem_b + stage * STAGE, smem_b + stage * STAGE + NP * PA, acc, fa, fb);
+        mma_stage_pl<BM, BN, WM, WN, NP, PT>(smem_b + stage * STAGE, smem_b + stage * STAGE + NP * PA, acc, fa, fb);
       }, g.stagger != 0 && wave >= WM * WN / 2);
     } else {
       load(PlSet0{});
@@ -2169,11 +2319,12 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
         __syncthreads();
         if (kt == it.kb) BDV_STAMP(1);
         if (kt + 1 < it.ke) load(PlSet0{});
-        mma_stage_pl<BM, BN, WM, WN, NP>(smem_b, smem_b + NP * PA, acc, fa, fb);
+        mma_stage_pl<BM, BN, WM, WN, NP, PT>(smem_b, smem_b + NP * PA, acc, fa, fb);
       }
     }
   }
   BDV_STAMP(2);
+  f16x2_unscale<PT>(acc, ps);   // fp16 pieces: back to the operands' scale before partials, scatter and statistics
   if (it.pslot >= 0) {
     store_partial<TM, TN, NTHR>(slab, it.pslot, acc, tid);
     return;
@@ -2200,9 +2351,18 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
 // Eight waves (2 x 4), one workgroup per CU, one LDS stage.
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
-template <int COLS, int NP = 3, int ROWS = 32>
-__device__ __forceinline__ void pl_store_rows(unsigned char* __restrict__ base, int krow, int c4, const float4 v) {
+template <int COLS, int NP = 3, int ROWS = 32, typename PT = Bf16Pieces>
+__device__ __forceinline__ void pl_store_rows(unsigned char* __restrict__ base, int krow, int c4, const float4 v, float scale = 1.f) {
   constexpr int PITCH = 2 * COLS + 64, PLANE = ROWS * PITCH;
+  if constexpr (kF16<PT>) {
+    static_assert(NP == 2, "fp16 pieces: two per operand");
+    u32x2_t hi, lo;
+    split2_f16_pairs(v, scale, hi, lo);
+    unsigned char* q = base + krow * PITCH + 8 * c4;
+    *reinterpret_cast<u32x2_t*>(q) = hi;
+    *reinterpret_cast<u32x2_t*>(q + PLANE) = lo;
+    return;
+  }
   if constexpr (NP == 1) {
     *reinterpret_cast<u32x2_t*>(base + krow * PITCH + 8 * c4) = bf16_hi_pairs(v);
     return;
@@ -2236,11 +2396,12 @@ __device__ __forceinline__ bf16x8_t pl_frag_tr(const unsigned char* __restrict__
 // loads of the ones after are issued among the MFMAs of the current stage, one barrier per 16 pixels -- used for the 128 x 256 and
 // 256 x 128 tiles (0.349 -> 0.315 ms on the 256 -> 128 site, 0.181 -> 0.162 on 128 <-> 512); the 256 x 256 tile has no registers
 // left for a second set.
-template <int BM, int BN, int WM, int WN, bool INCR, int NP = 3, bool MTAP = false, int KW = 32, int ES = 4>
+template <int BM, int BN, int WM, int WN, bool INCR, int NP = 3, bool MTAP = false, int KW = 32, int ES = 4, typename PT = Bf16Pieces>
 __global__ __launch_bounds__(64 * WM * WN, 2) void conv_wgrad_pl_kernel(const void* __restrict__ dy, const void* __restrict__ x,
                                                                          float* __restrict__ slab, Geom g, int MTw, int NTw,
                                                                          int kt_per_split, const float* __restrict__ pre_scale,
-                                                                         const float* __restrict__ pre_shift) {
+                                                                         const float* __restrict__ pre_shift, PieceScales ps) {
+  static_assert(!kF16<PT> || (NP == 2 && ES == 4), "fp16 pieces: two per operand, fp32 tensors");
   constexpr int NTHR = 64 * WM * WN;
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
   // a thread's unit of either operand is 16 bytes of one pixel's channels: 4 fp32 or 8 bf16 values (bf16: stored to LDS as they are)
@@ -2389,6 +2550,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_wgrad_pl_kernel(const vo
   f32x16 acc[TM][TN];
   zero_acc<TM, TN>(acc);
 
+  const float sc_a = f16x2_scale<PT>(ps.a), sc_b = f16x2_scale<PT>(ps.b);   // fp16 pieces: dy's and x's scales
   auto store = [&](int stage, auto set) __attribute__((always_inline)) {
     constexpr int SET = decltype(set)::value;
     unsigned char* const As = smem_b + stage * STAGE;
@@ -2396,7 +2558,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_wgrad_pl_kernel(const vo
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
       if constexpr (ES == 2) *reinterpret_cast<float4*>(As + a_krow[p] * PITCH_A + 16 * ((tid + NTHR * p) % AV)) = ra[SET][p];
-      else pl_store_rows<BM, NP, KW>(As, a_krow[p], (tid + NTHR * p) % AV, ra[SET][p]);
+      else pl_store_rows<BM, NP, KW, PT>(As, a_krow[p], (tid + NTHR * p) % AV, ra[SET][p], sc_a);
     }
 #pragma unroll
     for (int p = 0; p < BP; ++p) {
@@ -2411,7 +2573,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_wgrad_pl_kernel(const vo
         v.w = ok ? fmaxf(fmaf(v.w, sc.w, sh.w), 0.f) : 0.f;
       }
       if constexpr (ES == 2) *reinterpret_cast<float4*>(Bs + b_krow[p] * PITCH_B + 16 * c4) = v;
-      else pl_store_rows<BN, NP, KW>(Bs, b_krow[p], c4, v);
+      else pl_store_rows<BN, NP, KW, PT>(Bs, b_krow[p], c4, v, sc_b);
     }
   };
   auto mma = [&](int stage) __attribute__((always_inline)) {
@@ -2439,10 +2601,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_wgrad_pl_kernel(const vo
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0][j], acc[i][j], 0, 0, 0);
           }
           if constexpr (NP >= 2) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1][j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0][j], acc[i][j], 0, 0, 0);
+            acc[i][j] = mfma_piece<PT>(a[0], b[1][j], acc[i][j]);
+            acc[i][j] = mfma_piece<PT>(a[1], b[0][j], acc[i][j]);
           }
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = mfma_piece<PT>(a[0], b[0][j], acc[i][j]);
         }
       }
     }
@@ -2462,6 +2624,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_wgrad_pl_kernel(const vo
     }
   }
 
+  f16x2_unscale<PT>(acc, ps);   // fp16 pieces: a power of two, so it commutes with the reduction over the slices
   float* out = slab + (size_t)split * g.Cout * g.Ktot;
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
@@ -2691,6 +2854,8 @@ int pl_tile_override() {
   return g_pl_tile_forced;
 }
 
+constexpr int kArithF16x2 = BDV_ARITH_F16X2;   // the `pieces` / `arith` code of the two-fp16-piece arithmetic
+
 // M = GEMM rows, ncols = GEMM columns (Cout for fprop, Cin for dgrad), nk = 32-deep K-steps; ksplit_ok: stride-1 launches only
 // Which kernel family runs a site.  Rules read off tools/tune_conv.py (every choice timed per TSM-R50 site in one process, with
 // the training step's fused epilogues: profiles/r02_tune_conv_fused.txt; plain calls: profiles/r02_tune_conv.txt); differences
@@ -2732,6 +2897,13 @@ int pl_pick(bool dgrad, int ncols, int nk, int taps, int stride, int pieces = 3,
     if (forced >= 0 && forced < kNumPlCfg && ncols % kPlCfg[forced].BN == 0 && (forced != 4 || (dgrad && stride == 1))) return forced;
     const int c = pl_pick(dgrad, ncols, nk, taps, stride, 3, shifted);
     return c >= 0 ? c : ncols % 128 == 0 ? 5 : ncols % 64 == 0 ? 3 : -1;
+  }
+  if (pieces == kArithF16x2) {
+    // Two fp16 pieces: the tiles of the three-piece rules, and the 128x128 four-wave tile where those leave a site to the conv_*_x3
+    // kernels.  What they leave to the other families (64 columns behind a 1x1 filter) keeps three bf16 pieces.
+    if (forced >= 0 && forced < kNumPlCfg && ncols % kPlCfg[forced].BN == 0 && (forced != 4 || (dgrad && stride == 1))) return forced;
+    const int c = pl_pick(dgrad, ncols, nk, taps, stride, 3, shifted);
+    return c >= 0 ? c : ncols % 128 == 0 ? 5 : -1;
   }
   if (forced == kNumPlCfg) return -1;  // "none": the kernels of the other family everywhere
   if (forced >= 0 && ncols % kPlCfg[forced].BN == 0 && (forced != 4 || (dgrad && stride == 1))) return forced;   // (three pieces: the 64x128 tile exists for dgrad only)
@@ -2929,6 +3101,7 @@ struct ConvPlan {
   WgradPlan wg = {};   // BDV_CONV_WGRAD_F32
   WgradPlPlan wpl = {};  // BDV_CONV_WGRAD_PL
   char kernel[128] = "";  // as rocprofv3 prints it, without the anonymous namespace (weight gradients: up to the tile)
+  bool f16 = false;    // arith 4 on a plane kernel: two fp16 pieces (else the call is the three-bf16-piece call)
 };
 
 Geom fprop_geom(const bdv_conv_geom* gg) {  // also the weight gradient's
@@ -2956,9 +3129,32 @@ PlGemm pl_gemm(const bdv_conv_geom* g, int kind) {
   return {st == 1 ? g->N * g->H * g->W : Mc0, g->Cin, g->R * g->S * g->Cout / BK, st == 1};
 }
 
-// arith: 0 = fp32 MFMA, 1 / 2 / 3 = bf16 pieces per operand; pre: the producer's BatchNorm + ReLU in the loader
+// arith: 0 = fp32 MFMA, 1 / 2 / 3 = bf16 pieces per operand, 4 = two fp16 pieces; pre: the producer's BatchNorm + ReLU in the loader
 ConvPlan plan_conv(const bdv_conv_geom* g, int kind, int arith, bool pre) {
   ConvPlan p;
+  if (arith == kArithF16x2) {
+    // The plane kernels only, fp32 tensors, no BatchNorm in the loader (the operand's maximum is not known before the launch):
+    // every other call is the three-bf16-piece call, with its plan and its kernel.
+    if (check_geom(g, "bdv_conv")) return p;
+    const bool plain = !pre && g->act_dtype == BDV_ACT_F32 && g->Cin % BK == 0;
+    const int cfg = !plain || kind == kWgrad ? -1 : kind == kDgrad ? (g->Cin % 64 == 0 ? pl_dgrad_cfg(g, kArithF16x2) : -1) : pl_fprop_cfg(g, kArithF16x2);
+    const int form = plain && kind == kWgrad ? pl_wgrad_form(g) : -1;
+    if (cfg < 0 && (form < 0 || form == 5)) return plan_conv(g, kind, 3, pre);
+    p = plan_conv(g, kind, 2, false);   // side buffers and weight-gradient slices do not depend on the piece type ...
+    if (p.family < 0) return p;
+    if (kind == kWgrad) {
+      snprintf(p.kernel, sizeof(p.kernel), "conv_wgrad_pl_kernel<%d, %d, ..., F16Pieces>", p.wpl.BM, p.wpl.BN);
+    } else {                            // ... the tile of a fprop / dgrad site does
+      const PlGemm m = pl_gemm(g, kind);
+      p.cfg = cfg;
+      p.stat_rows = (kind == kDgrad ? g->stride * g->stride : 1) * plan_pl(cfg, m.M, m.ncols, m.nk, 0, false).MT;
+      p.pre_ok = false;
+      snprintf(p.kernel, sizeof(p.kernel), "conv_%s_pl_kernel<%d, %d, %d, %d, %d, 2, %s4, F16Pieces>", kind == kDgrad ? "dgrad" : "fprop",
+               kPlCfg[cfg].BM, kPlCfg[cfg].BN, pl_cfg_wm(cfg), pl_cfg_wn(cfg), kPlCfg[cfg].nbuf, kind == kDgrad ? "" : "false, ");
+    }
+    p.f16 = true;
+    return p;
+  }
 #define PLAN_REQUIRE(cond, ...)     \
   do {                              \
     if (!(cond)) {                  \
@@ -3077,7 +3273,7 @@ extern "C" size_t bdv_conv_workspace_bytes(const bdv_conv_geom* gg, int kind) {
   }
   size_t need = 0;
   bool any = false;
-  for (int arith = 0; arith <= 3; ++arith)
+  for (int arith = 0; arith <= kArithF16x2; ++arith)
     for (int pre = 0; pre <= (kind == kFprop ? 1 : 0); ++pre) {
       const ConvPlan p = plan_conv(gg, kind, arith, pre != 0);
       if (p.family < 0) continue;
@@ -3261,14 +3457,23 @@ extern "C" int bdv_conv_split_weights(const float* w, const bdv_conv_geom* gg, v
   return BDV_OK;
 }
 
-extern "C" int bdv_conv_fprop_pl(const void* x, const float* w, const void* planes_fprop, void* y, const bdv_conv_geom* gg,
-                                 float* bn_partial, const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes,
-                                 int pieces, const float* pre_scale, const float* pre_shift, void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_fprop_pl")) return e;
-  BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_fprop_pl: pieces = %d (3, 2 or 1)", pieces);
+namespace {
+// the amax word behind the two fp16 planes of a weight (bdv_conv_split_weights_f16x2)
+const unsigned* f16x2_weight_amax(const void* planes, const bdv_conv_geom* gg) {
+  return (const unsigned*)((const unsigned char*)planes + (size_t)2 * gg->Cout * gg->R * gg->S * gg->Cin * sizeof(unsigned short));
+}
+
+// pieces: 1 .. 3 bf16 pieces, or kArithF16x2 with the activation operand's amax word (a call the plan leaves to three bf16 pieces
+// ignores it)
+int conv_fprop_pl_impl(const void* x, const float* w, const void* planes_fprop, void* y, const bdv_conv_geom* gg, float* bn_partial,
+                       const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, int pieces, const float* pre_scale,
+                       const float* pre_shift, const unsigned* amax_x, void* stream) {
   const bool pre = pre_scale != nullptr;
   const ConvPlan cp = plan_conv(gg, kFprop, pieces, pre);
   if (cp.family < 0) return BDV_EINVAL;
+  if (pieces == kArithF16x2 && !cp.f16) pieces = 3;
+  const PieceScales ps = {cp.f16 ? amax_x : nullptr, cp.f16 ? f16x2_weight_amax(planes_fprop, gg) : nullptr};
+  BDV_REQUIRE(!cp.f16 || (amax_x != nullptr && planes_fprop != nullptr), "bdv_conv_fprop_f16x2: null pointer (amax_x, planes_fprop)");
   const bool h16 = gg->act_dtype == BDV_ACT_BF16;
   if (pre) {
     BDV_REQUIRE(pre_shift != nullptr && cp.pre_ok,
@@ -3307,21 +3512,24 @@ extern "C" int bdv_conv_fprop_pl(const void* x, const float* w, const void* plan
             g.W, g.Cin, g.Cout, g.R, g.stride, p.cfg, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split, p.est_us);
 #define BDV_FPROP_PL(BM_, BN_, WM_, WN_, NB_)                                                                                         \
   do {                                                                                                                                \
-    if (h16)                                                                                                                          \
+    if (cp.f16)                                                                                                                       \
+      hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 2, false, 4, F16Pieces>), dim3(blocks), dim3(64 * WM_ * WN_), 0, \
+                         s, x, wp, y, g, p.NT, p.wk, slab, epi, ps);                                                                  \
+    else if (h16)                                                                                                                     \
       hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 1, false, 2>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y, \
-                         g, p.NT, p.wk, slab, epi);                                                                                   \
+                         g, p.NT, p.wk, slab, epi, ps);                                                                               \
     else if (pre)                                                                                                                     \
       hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 3, true>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y,  \
-                         g, p.NT, p.wk, slab, epi);                                                                                   \
+                         g, p.NT, p.wk, slab, epi, ps);                                                                               \
     else if (pieces == 1)                                                                                                             \
       hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 1>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y, g,    \
-                         p.NT, p.wk, slab, epi);                                                                                      \
+                         p.NT, p.wk, slab, epi, ps);                                                                                  \
     else if (pieces == 2)                                                                                                             \
       hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 2>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y, g,    \
-                         p.NT, p.wk, slab, epi);                                                                                      \
+                         p.NT, p.wk, slab, epi, ps);                                                                                  \
     else                                                                                                                              \
       hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 3>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y, g,    \
-                         p.NT, p.wk, slab, epi);                                                                                      \
+                         p.NT, p.wk, slab, epi, ps);                                                                                  \
     BDV_LAUNCH_CHECK("bdv_conv_fprop_pl");                                                                                            \
     if (p.wk.split > 1) {                                                                                                             \
       hipLaunchKernelGGL((conv_fprop_fixup_kernel<BM_, BN_, WM_, WN_>), dim3(p.wk.rem_tiles), dim3(64 * WM_ * WN_), 0, s,             \
@@ -3337,14 +3545,34 @@ extern "C" int bdv_conv_fprop_pl(const void* x, const float* w, const void* plan
 #undef BDV_FPROP_PL
   return BDV_OK;
 }
+}  // namespace
 
-extern "C" int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* planes_dgrad, void* dx, const void* add_src,
-                                 const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat,
-                                 void* workspace, size_t workspace_bytes, int pieces, void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_dgrad_pl")) return e;
-  BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_dgrad_pl: pieces = %d (3, 2 or 1)", pieces);
+extern "C" int bdv_conv_fprop_pl(const void* x, const float* w, const void* planes_fprop, void* y, const bdv_conv_geom* gg,
+                                 float* bn_partial, const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes,
+                                 int pieces, const float* pre_scale, const float* pre_shift, void* stream) {
+  if (int e = check_geom(gg, "bdv_conv_fprop_pl")) return e;
+  BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_fprop_pl: pieces = %d (3, 2 or 1)", pieces);
+  return conv_fprop_pl_impl(x, w, planes_fprop, y, gg, bn_partial, affine, workspace, workspace_bytes, pieces, pre_scale, pre_shift, nullptr,
+                            stream);
+}
+
+extern "C" int bdv_conv_fprop_f16x2(const void* x, const void* amax_x, const float* w, const void* planes_fprop, void* y,
+                                    const bdv_conv_geom* gg, float* bn_partial, const bdv_conv_affine* affine, void* workspace,
+                                    size_t workspace_bytes, const float* pre_scale, const float* pre_shift, void* stream) {
+  if (int e = check_geom(gg, "bdv_conv_fprop_f16x2")) return e;
+  return conv_fprop_pl_impl(x, w, planes_fprop, y, gg, bn_partial, affine, workspace, workspace_bytes, kArithF16x2, pre_scale, pre_shift,
+                            (const unsigned*)amax_x, stream);
+}
+
+namespace {
+int conv_dgrad_pl_impl(const void* dy, const float* w, const void* planes_dgrad, void* dx, const void* add_src,
+                       const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat, void* workspace,
+                       size_t workspace_bytes, int pieces, const unsigned* amax_dy, void* stream) {
   const ConvPlan cp = plan_conv(gg, kDgrad, pieces, false);
   if (cp.family < 0) return BDV_EINVAL;
+  if (pieces == kArithF16x2 && !cp.f16) pieces = 3;
+  const PieceScales ps = {cp.f16 ? amax_dy : nullptr, cp.f16 ? f16x2_weight_amax(planes_dgrad, gg) : nullptr};
+  BDV_REQUIRE(!cp.f16 || (amax_dy != nullptr && planes_dgrad != nullptr), "bdv_conv_dgrad_f16x2: null pointer (amax_dy, planes_dgrad)");
   const bool h16 = gg->act_dtype == BDV_ACT_BF16;
   if (cp.family != BDV_CONV_PL)
     return conv_dgrad_impl((const float*)dy, w, (float*)dx, (const float*)add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, stream,
@@ -3393,18 +3621,21 @@ extern "C" int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* pla
             g.W, g.Cin, g.Cout, g.R, g.stride, p.cfg, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split, p.est_us);
 #define BDV_DGRAD_PL(BM_, BN_, WM_, WN_, NB_)                                                                                          \
   do {                                                                                                                                 \
-    if (h16)                                                                                                                           \
+    if (cp.f16)                                                                                                                        \
+      hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 2, 4, F16Pieces>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, \
+                         add_src, add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                        \
+    else if (h16)                                                                                                                      \
       hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 1, 2>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, add_src,  \
-                         add_mask_src, g, p.NT, p.wk, slab, stat);                                                                     \
+                         add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                                 \
     else if (pieces == 1)                                                                                                              \
       hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 1>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, add_src,     \
-                         add_mask_src, g, p.NT, p.wk, slab, stat);                                                                     \
+                         add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                                 \
     else if (pieces == 2)                                                                                                              \
       hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 2>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, add_src,     \
-                         add_mask_src, g, p.NT, p.wk, slab, stat);                                                                     \
+                         add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                                 \
     else                                                                                                                               \
       hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 3>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, add_src,     \
-                         add_mask_src, g, p.NT, p.wk, slab, stat);                                                                     \
+                         add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                                 \
     BDV_LAUNCH_CHECK("bdv_conv_dgrad_pl");                                                                                             \
     if (p.wk.split > 1) {                                                                                                              \
       hipLaunchKernelGGL((conv_dgrad_fixup_kernel<BM_, BN_, WM_, WN_>), dim3(p.wk.rem_tiles), dim3(64 * WM_ * WN_), 0, s,              \
@@ -3420,6 +3651,23 @@ extern "C" int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* pla
   else BDV_DGRAD_PL(256, 64, 4, 2, 2);
 #undef BDV_DGRAD_PL
   return BDV_OK;
+}
+}  // namespace
+
+extern "C" int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* planes_dgrad, void* dx, const void* add_src,
+                                 const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat,
+                                 void* workspace, size_t workspace_bytes, int pieces, void* stream) {
+  if (int e = check_geom(gg, "bdv_conv_dgrad_pl")) return e;
+  BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_dgrad_pl: pieces = %d (3, 2 or 1)", pieces);
+  return conv_dgrad_pl_impl(dy, w, planes_dgrad, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, pieces, nullptr, stream);
+}
+
+extern "C" int bdv_conv_dgrad_f16x2(const void* dy, const void* amax_dy, const float* w, const void* planes_dgrad, void* dx,
+                                    const void* add_src, const uint32_t* add_mask_src, const bdv_conv_geom* gg,
+                                    const bdv_bn_stat_fuse* bn_stat, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int e = check_geom(gg, "bdv_conv_dgrad_f16x2")) return e;
+  return conv_dgrad_pl_impl(dy, w, planes_dgrad, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, kArithF16x2,
+                            (const unsigned*)amax_dy, stream);
 }
 
 namespace {
@@ -3493,11 +3741,15 @@ extern "C" int bdv_conv_wgrad_partial(const float* dy, const float* x, const bdv
   return wgrad_partial("bdv_conv_wgrad_partial", dy, x, gg, slab, slab_bytes, (hipStream_t)stream, &splits, cp);
 }
 
-extern "C" int bdv_conv_wgrad_partial_pl(const void* dy, const void* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes,
-                                         int pieces, const float* pre_scale, const float* pre_shift, void* stream) {
-  BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_wgrad_partial_pl: pieces = %d (3, 2 or 1)", pieces);
+namespace {
+int conv_wgrad_partial_pl_impl(const void* dy, const void* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes, int pieces,
+                               const float* pre_scale, const float* pre_shift, const unsigned* amax_dy, const unsigned* amax_x,
+                               void* stream) {
   const ConvPlan cp = plan_conv(gg, kWgrad, pieces, pre_scale != nullptr);
   if (cp.family < 0) return BDV_EINVAL;
+  if (pieces == kArithF16x2 && !cp.f16) pieces = 3;
+  const PieceScales ps = {cp.f16 ? amax_dy : nullptr, cp.f16 ? amax_x : nullptr};
+  BDV_REQUIRE(!cp.f16 || (amax_dy != nullptr && amax_x != nullptr), "bdv_conv_wgrad_partial_f16x2: null pointer (amax_dy, amax_x)");
   BDV_REQUIRE(pre_scale == nullptr || pre_shift != nullptr, "bdv_conv_wgrad_partial_pl: pre_scale without pre_shift");
   BDV_REQUIRE(dy && x && slab, "bdv_conv_wgrad_partial_pl: null pointer");
   BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(x) && bdv_aligned16(slab), "bdv_conv_wgrad_partial_pl: pointers must be 16-byte aligned");
@@ -3523,10 +3775,15 @@ extern "C" int bdv_conv_wgrad_partial_pl(const void* dy, const void* x, const bd
   const bool incr = g.Ho * g.Wo > BK && BK / g.Wo + 1 <= g.Ho;
 #define BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, INCR_, NP_, MTAP_, KW_, ES_)                                                                \
   hipLaunchKernelGGL((conv_wgrad_pl_kernel<BM_, BN_, WM_, WN_, INCR_, NP_, MTAP_, KW_, ES_>), grid, dim3(64 * WM_ * WN_), 0, s, dy, x, \
-                     (float*)slab, g, p.MTw, p.NTw, p.kt_per_split, pre_scale, pre_shift)
+                     (float*)slab, g, p.MTw, p.NTw, p.kt_per_split, pre_scale, pre_shift, ps)
+#define BDV_WGRAD_F16(BM_, BN_, WM_, WN_, INCR_, MTAP_, KW_)                                                                        \
+  hipLaunchKernelGGL((conv_wgrad_pl_kernel<BM_, BN_, WM_, WN_, INCR_, 2, MTAP_, KW_, 4, F16Pieces>), grid, dim3(64 * WM_ * WN_), 0, s, \
+                     dy, x, (float*)slab, g, p.MTw, p.NTw, p.kt_per_split, pre_scale, pre_shift, ps)
 #define BDV_WGRAD_PL(BM_, BN_, WM_, WN_, MTAP_, KW_)                                                                             \
   do {                                                                                                                           \
-    if (h16 && incr) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, true, 1, MTAP_, (KW_ == 16 ? 32 : KW_), 2);                               \
+    if (cp.f16 && incr) BDV_WGRAD_F16(BM_, BN_, WM_, WN_, true, MTAP_, KW_);                                                     \
+    else if (cp.f16) BDV_WGRAD_F16(BM_, BN_, WM_, WN_, false, MTAP_, KW_);                                                       \
+    else if (h16 && incr) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, true, 1, MTAP_, (KW_ == 16 ? 32 : KW_), 2);                          \
     else if (h16) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, false, 1, MTAP_, (KW_ == 16 ? 32 : KW_), 2);                                 \
     else if (incr && pieces == 3) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, true, 3, MTAP_, KW_, 4);                                     \
     else if (pieces == 3) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, false, 3, MTAP_, KW_, 4);                                            \
@@ -3548,8 +3805,56 @@ extern "C" int bdv_conv_wgrad_partial_pl(const void* dy, const void* x, const bd
   else if (p.BN == 256) BDV_WGRAD_PL(128, 256, 2, 4, false, 32);
   else BDV_WGRAD_PL(128, 128, 2, 4, false, 32);
 #undef BDV_WGRAD_PL
+#undef BDV_WGRAD_F16
 #undef BDV_WGRAD_PL2
   BDV_LAUNCH_CHECK("bdv_conv_wgrad_partial_pl");
+  return BDV_OK;
+}
+}  // namespace
+
+extern "C" int bdv_conv_wgrad_partial_pl(const void* dy, const void* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes,
+                                         int pieces, const float* pre_scale, const float* pre_shift, void* stream) {
+  BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_wgrad_partial_pl: pieces = %d (3, 2 or 1)", pieces);
+  return conv_wgrad_partial_pl_impl(dy, x, gg, slab, slab_bytes, pieces, pre_scale, pre_shift, nullptr, nullptr, stream);
+}
+
+extern "C" int bdv_conv_wgrad_partial_f16x2(const void* dy, const void* amax_dy, const void* x, const void* amax_x,
+                                            const bdv_conv_geom* gg, void* slab, size_t slab_bytes, const float* pre_scale,
+                                            const float* pre_shift, void* stream) {
+  return conv_wgrad_partial_pl_impl(dy, x, gg, slab, slab_bytes, kArithF16x2, pre_scale, pre_shift, (const unsigned*)amax_dy,
+                                    (const unsigned*)amax_x, stream);
+}
+
+// ---- fp16 pieces: amax word of a tensor, planes of a weight ------------------------------------------------------------------
+extern "C" int bdv_f16x2_amax(const float* t, int64_t n, void* amax, void* stream) {
+  BDV_REQUIRE(t && amax && n > 0, "bdv_f16x2_amax: null pointer or n = %lld", (long long)n);
+  BDV_REQUIRE(bdv_aligned16(t) && ((uintptr_t)amax & 3) == 0, "bdv_f16x2_amax: t must be 16-byte aligned, amax 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  BDV_REQUIRE(hipMemsetAsync(amax, 0, sizeof(unsigned), s) == hipSuccess, "bdv_f16x2_amax: hipMemsetAsync failed");
+  const int64_t blocks = (n / 4 + 1023) / 1024;   // four 16-byte loads per thread and trip, at most eight workgroups per CU
+  hipLaunchKernelGGL(f16x2_amax_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks)), dim3(256), 0, s, t, (long long)n,
+                     (unsigned*)amax);
+  BDV_LAUNCH_CHECK("bdv_f16x2_amax");
+  return BDV_OK;
+}
+
+extern "C" float bdv_f16x2_scale(float amax) {
+  return __builtin_bit_cast(float, f16x2_scale_bits(__builtin_bit_cast(unsigned, amax)));
+}
+
+extern "C" int bdv_conv_split_weights_f16x2(const float* w, const bdv_conv_geom* gg, void* planes_fprop, void* planes_dgrad, void* stream) {
+  if (int e = check_geom(gg, "bdv_conv_split_weights_f16x2")) return e;
+  BDV_REQUIRE(w && (planes_fprop || planes_dgrad), "bdv_conv_split_weights_f16x2: null pointer");
+  BDV_REQUIRE(gg->Cin % 32 == 0 && gg->Cout % 32 == 0, "bdv_conv_split_weights_f16x2: Cin=%d and Cout=%d must be multiples of 32", gg->Cin, gg->Cout);
+  BDV_REQUIRE(bdv_aligned16(w) && bdv_aligned16(planes_fprop) && bdv_aligned16(planes_dgrad), "bdv_conv_split_weights_f16x2: alignment");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned* const amax = (unsigned*)f16x2_weight_amax(planes_fprop ? planes_fprop : planes_dgrad, gg);
+  unsigned* const copy = planes_fprop && planes_dgrad ? (unsigned*)f16x2_weight_amax(planes_dgrad, gg) : nullptr;
+  if (int e = bdv_f16x2_amax(w, (int64_t)gg->Cout * gg->R * gg->S * gg->Cin, amax, stream)) return e;
+  const dim3 grid(gg->Cin / 32, gg->Cout / 32, gg->R * gg->S);
+  hipLaunchKernelGGL(split_weights_f16_kernel, grid, dim3(256), 0, s, w, (unsigned short*)planes_fprop, (unsigned short*)planes_dgrad,
+                     gg->Cout, gg->R * gg->S, gg->Cin, (const unsigned*)amax, copy);
+  BDV_LAUNCH_CHECK("bdv_conv_split_weights_f16x2");
   return BDV_OK;
 }
 

@@ -160,6 +160,8 @@ def wgrad_overlapped(dy: torch.Tensor, inp: torch.Tensor, geom, pre_bn=None) -> 
     main = torch.cuda.current_stream(dy.device)
     idx, side = _side_stream(dy.device)
     dw = torch.empty((geom.Cout, geom.R, geom.S, geom.Cin), dtype=torch.float32, device=dy.device)   # owned by main
+    if not recompute:               # 'f16x2': the operands' amax words are taken here, on the main stream -- the data gradient that
+        K.wgrad_amax(dy, inp, geom)  # follows reads dy's too and must not wait for the side stream's queue
     ready = torch.cuda.Event()
     ready.record(main)
     side.wait_event(ready)

@@ -142,22 +142,26 @@ FPROP_X3 = _x3_default('BDVCIL_FPROP_X3')
 
 
 PIECES = 3      # 3: fp32-level products from three bf16 pieces per operand; 2: two pieces, three products ('bf16x2', 16 significand
-                # bits); 1: single bf16 product (reduced precision, 'bf16x1')
+                # bits); 1: single bf16 product (reduced precision, 'bf16x1'); 4: two fp16 pieces, three products ('f16x2', fp32 level)
+F16X2 = 4       # BDV_ARITH_F16X2
 
 
 def set_conv_arith(mode: str):
     """'bf16x3' (default), 'f32mfma', 'bf16x2' (two bf16 pieces per operand, three MFMA products, 16 significand bits; the plane
-    kernels only, the other sites keep three pieces), or the reduced-precision modes of BASELINE config 5: 'bf16x1' (operands rounded to bf16, one
+    kernels only, the other sites keep three pieces), 'f16x2' (two fp16 pieces of the operand times a per-tensor power of two, three
+    MFMA products, fp32-level result; the same sites as 'bf16x2', the others keep three bf16 pieces; each operand tensor's maximum
+    is taken on the device once, ``act_amax``), or the reduced-precision modes of BASELINE config 5: 'bf16x1' (operands rounded to bf16, one
     MFMA product, fp32 accumulate, fp32 tensors) and 'bf16' (the same arithmetic with activations and their gradients STORED as
     bf16 between the stem's max-pool and the average pool; fp32 statistics, weights and weight gradients) for fprop, dgrad and
     wgrad at once; returns the previous (fprop, dgrad, wgrad) flags.
     Leaving 'bf16x1' needs another ``set_conv_arith`` call (the flags alone do not restore ``PIECES``)."""
     global FPROP_X3, DGRAD_X3, WGRAD_X3, PIECES, ACT_DTYPE
-    if mode not in ('bf16x3', 'f32mfma', 'bf16x2', 'bf16x1', 'bf16'):
-        raise ValueError(f"set_conv_arith: unknown mode {mode!r} ('bf16x3' | 'f32mfma' | 'bf16x2' | 'bf16x1' | 'bf16')")
+    if mode not in ('bf16x3', 'f32mfma', 'bf16x2', 'f16x2', 'bf16x1', 'bf16'):
+        raise ValueError(f"set_conv_arith: unknown mode {mode!r} ('bf16x3' | 'f32mfma' | 'bf16x2' | 'f16x2' | 'bf16x1' | 'bf16')")
     prev = (FPROP_X3, DGRAD_X3, WGRAD_X3)
     FPROP_X3 = DGRAD_X3 = WGRAD_X3 = (mode != 'f32mfma')
-    PIECES = 1 if mode in ('bf16x1', 'bf16') else 2 if mode == 'bf16x2' else 3
+    PIECES = 1 if mode in ('bf16x1', 'bf16') else 2 if mode == 'bf16x2' else F16X2 if mode == 'f16x2' else 3
+    _AMAX.clear()
     # 'bf16': the bf16x1 arithmetic on bf16-STORED activations and gradients (BDV_ACT_BF16) from the stem's max-pool to the average
     # pool; the tensors the model creates from here on carry the type, every kernel follows the dtype of what it is given
     ACT_DTYPE = torch.bfloat16 if mode == 'bf16' else torch.float32
@@ -172,7 +176,8 @@ def set_conv_arith(mode: str):
 import weakref as _weakref
 
 WEIGHT_EPOCH = 0
-_PLANES = {}        # id(base tensor) -> [weakref, (data_ptr, version, epoch), uint8 buffer holding both layouts, view, geometry, checksum]
+_PLANES = {}        # id(base tensor) -> [weakref, (data_ptr, version, epoch, fp16 pieces?), uint8 buffer holding both layouts, view,
+                    # geometry, checksum]
 # A write that torch's version counter does not see -- ``p.data.mul_()``, ``p.data.copy_()``, ``dist.broadcast(p.data)``, any kernel
 # given ``p.data_ptr()`` -- leaves the stamp unchanged and the cached planes STALE: the convolutions would then run on the old
 # weights without any error.  Such writers must call ``bump_weight_epoch()`` ("Weights written behind torch's
@@ -202,12 +207,23 @@ def bump_weight_epoch(params=None):
 _PLANES_PENDING = {}    # device index -> (event of the last refresh_weight_planes() on another stream, streams ordered behind it)
 
 
-def _plane_stamp(w, base):
-    return (w.data_ptr(), base._version, WEIGHT_EPOCH)
+def _plane_stamp(w, base, f16=False):
+    return (w.data_ptr(), base._version, WEIGHT_EPOCH, bool(f16))
 
 
-def weight_planes(w: torch.Tensor, g: ConvGeom):
-    """(planes_fprop, planes_dgrad) of the (Cout, R, S, Cin) weight view ``w``: uint8 views of one cached buffer."""
+def _split_weights(w, g, buf, nbytes, f16):
+    """Cut ``w`` into the planes of both layouts: three bf16 pieces, or (``f16``) two fp16 pieces and the weight's amax word."""
+    if f16:
+        check(lib().bdv_conv_split_weights_f16x2(_p(w), ctypes.byref(g), _p(buf[:nbytes]), _p(buf[nbytes:]), _stream()),
+              'bdv_conv_split_weights_f16x2')
+    else:
+        check(lib().bdv_conv_split_weights(_p(w), ctypes.byref(g), _p(buf[:nbytes]), _p(buf[nbytes:]), _stream()),
+              'bdv_conv_split_weights')
+
+
+def weight_planes(w: torch.Tensor, g: ConvGeom, f16: bool = False):
+    """(planes_fprop, planes_dgrad) of the (Cout, R, S, Cin) weight view ``w``: uint8 views of one cached buffer.  ``f16``: the
+    planes of the 'f16x2' arithmetic (a weight has one kind at a time: the kernels of a site all read the same kind)."""
     if _PLANES_PENDING:
         pend = _PLANES_PENDING.get(w.device.index)
         if pend is not None:                            # (event, stream ids that are ordered behind it already)
@@ -217,7 +233,7 @@ def weight_planes(w: torch.Tensor, g: ConvGeom):
                 pend[1].add(cur.cuda_stream)
     base = w._base if w._base is not None else w
     key = id(base)
-    stamp = _plane_stamp(w, base)
+    stamp = _plane_stamp(w, base, f16)
     ent = _PLANES.get(key)
     if ent is not None and ent[0]() is not base:
         ent = None                                      # the id was recycled by another tensor
@@ -227,8 +243,7 @@ def weight_planes(w: torch.Tensor, g: ConvGeom):
     if ent is None or ent[1] != stamp or ent[2].numel() != 2 * nbytes:
         buf = ent[2] if ent is not None and ent[2].numel() == 2 * nbytes and ent[2].device == w.device else \
             torch.empty(2 * nbytes, dtype=torch.uint8, device=w.device)
-        check(lib().bdv_conv_split_weights(_p(w), ctypes.byref(g), _p(buf[:nbytes]), _p(buf[nbytes:]), _stream()),
-              'bdv_conv_split_weights')
+        _split_weights(w, g, buf, nbytes, f16)
         ref = _weakref.ref(base, lambda _r, k=key: _PLANES.pop(k, None))
         # how to rebuild the view and the geometry without holding the parameter alive (refresh_weight_planes)
         ent = [ref, stamp, buf, (tuple(w.shape), tuple(w.stride()), w.storage_offset()), (g.R, g.S, g.Cin, g.Cout),
@@ -254,7 +269,8 @@ def refresh_weight_planes(stream: Optional[torch.cuda.Stream] = None) -> int:
             continue
         shape, stride, off = ent[3]
         w = base.as_strided(shape, stride, off) if (tuple(base.shape), tuple(base.stride())) != (shape, stride) else base
-        if ent[1] == _plane_stamp(w, base):
+        f16 = bool(ent[1][3]) if ent[1] is not None else PIECES == F16X2      # (bump_weight_epoch(params) clears the stamp)
+        if ent[1] == _plane_stamp(w, base, f16):
             continue
         by_dev.setdefault(base.device, []).append((ent, w, base))
     for device, todo in by_dev.items():
@@ -268,9 +284,9 @@ def refresh_weight_planes(stream: Optional[torch.cuda.Stream] = None) -> int:
                 g = make_geom(1, R, S, Cin, Cout, R, S, 1, 0, 1, 0)
                 buf = ent[2]
                 nbytes = buf.numel() // 2
-                check(lib().bdv_conv_split_weights(_p(w), ctypes.byref(g), _p(buf[:nbytes]), _p(buf[nbytes:]), _stream()),
-                      'bdv_conv_split_weights')
-                ent[1] = _plane_stamp(w, base)
+                f16 = bool(ent[1][3]) if ent[1] is not None else PIECES == F16X2
+                _split_weights(w, g, buf, nbytes, f16)
+                ent[1] = _plane_stamp(w, base, f16)
                 if CHECK_PLANES:
                     ent[5] = _weight_checksum(w)
                 n += 1
@@ -279,6 +295,61 @@ def refresh_weight_planes(stream: Optional[torch.cuda.Stream] = None) -> int:
                 ev.record(st)
                 _PLANES_PENDING[device.index] = (ev, {st.cuda_stream})
     return n
+
+
+# ---- 'f16x2': the amax word of an operand tensor (bdv_f16x2_amax), cached per tensor ------------------------------------------
+# One HBM pass per tensor and value: x's word serves fprop and wgrad, dy's dgrad and wgrad, a block input's conv1 and the downsample.
+# Keyed by the tensor a tensor views (views share their base's version counter) and the range viewed; an entry is valid while the
+# version did not move and dies with the tensor.  Kernels of this package that write INTO a tensor they are given (``out=``, ``dy=``)
+# call ``amax_forget``; plugin code that does the same through raw pointers must too.  R50 training step: about 100 passes.
+_AMAX = {}          # id(base tensor) -> [weakref, {(data_ptr, numel): [version, int32 word, event, stream handle]}]
+
+
+def act_amax(t: torch.Tensor) -> torch.Tensor:
+    """The device-resident amax word (int32[1]: the bits of max|t|) of an fp32 activation / gradient tensor, computed on the current
+    stream the first time it is asked for; no host synchronisation."""
+    base = t._base if t._base is not None else t
+    key = id(base)
+    ent = _AMAX.get(key)
+    if ent is not None and ent[0]() is not base:
+        ent = None
+    if ent is None:
+        ent = _AMAX[key] = [_weakref.ref(base, lambda _r, k=key: _AMAX.pop(k, None)), {}]
+    cur = torch.cuda.current_stream(t.device)
+    sub = (t.data_ptr(), t.numel())
+    rec = ent[1].get(sub)
+    if rec is not None and rec[0] == base._version:
+        if rec[3] != cur.cuda_stream:       # taken on another stream (a weight gradient on the side stream): order behind it
+            cur.wait_event(rec[2])
+        return rec[1]
+    word = torch.empty(1, dtype=torch.int32, device=t.device)
+    check(lib().bdv_f16x2_amax(_p(t), t.numel(), _p(word), _stream()), 'bdv_f16x2_amax')
+    ev = torch.cuda.Event()
+    ev.record(cur)
+    ent[1][sub] = [base._version, word, ev, cur.cuda_stream]
+    return word
+
+
+def amax_forget(t):
+    """``t`` was written by a raw-pointer kernel: its cached amax word (if any) is stale."""
+    if _AMAX and isinstance(t, torch.Tensor):
+        _AMAX.pop(id(t._base if t._base is not None else t), None)
+
+
+def _plan_f16(plan) -> bool:
+    """The plan runs the two-fp16-piece kernels (else, in 'f16x2', the call keeps three bf16 pieces)."""
+    return plan.kernel.endswith(b'F16Pieces>')
+
+
+def wgrad_amax(dy: torch.Tensor, x: torch.Tensor, g: ConvGeom):
+    """'f16x2' only: take the amax words a weight gradient of this geometry will read, on the CURRENT stream (a caller that launches
+    the weight gradient on another stream calls this first, so that other readers of the words do not wait for that stream)."""
+    if PIECES != F16X2 or not WGRAD_X3 or dy.dtype != torch.float32 or x.dtype != torch.float32:
+        return
+    g.act_dtype = 0
+    if _plan_f16(conv_plan(g, 'wgrad')):
+        act_amax(dy)
+        act_amax(x)
 
 
 _KINDS = {'fprop': 0, 'dgrad': 1, 'wgrad': 2}
@@ -357,7 +428,16 @@ def conv_fprop(x: torch.Tensor, w: torch.Tensor, g: ConvGeom, out: Optional[torc
         if res is not None:
             _chk_conv(res, (g.N, g.Ho, g.Wo, g.Cout), g, 'residual')
         aff = ConvAffine(scale.data_ptr(), shift.data_ptr(), res.data_ptr() if res is not None else None, int(bool(relu)))
-    if use_x3:
+    if out is not None:
+        amax_forget(out)
+    if use_x3 and PIECES == F16X2:
+        f16 = _plan_f16(plan)
+        planes_f = weight_planes(w, g, f16)[0] if plan.reads_planes else None
+        check(lib().bdv_conv_fprop_f16x2(_p(x), _p(act_amax(x) if f16 else None), _p(w), _p(planes_f), _p(y), ctypes.byref(g), _p(part),
+                                         ctypes.byref(aff) if aff is not None else None, _p(ws), ws.numel(),
+                                         _p(pre_bn[0] if pre_bn is not None else None), _p(pre_bn[1] if pre_bn is not None else None),
+                                         _stream()), 'bdv_conv_fprop_f16x2')
+    elif use_x3:
         planes_f = weight_planes(w, g)[0] if plan.reads_planes else None
         check(lib().bdv_conv_fprop_pl(_p(x), _p(w), _p(planes_f), _p(y), ctypes.byref(g), _p(part),
                                       ctypes.byref(aff) if aff is not None else None, _p(ws), ws.numel(), PIECES,
@@ -414,7 +494,15 @@ def conv_dgrad(dy: torch.Tensor, w: torch.Tensor, g: ConvGeom, add_src: Optional
                           partial.data_ptr(), relu_affine[0].data_ptr() if relu_affine is not None else None,
                           relu_affine[1].data_ptr() if relu_affine is not None else None)
     ws = _conv_ws(g, 1, dy.device, ws_tag)
-    if use_x3:
+    if out is not None:
+        amax_forget(out)
+    if use_x3 and PIECES == F16X2:
+        f16 = _plan_f16(plan)
+        planes_d = weight_planes(w, g, f16)[1] if plan.reads_planes else None
+        check(lib().bdv_conv_dgrad_f16x2(_p(dy), _p(act_amax(dy) if f16 else None), _p(w), _p(planes_d), _p(dx), _p(add_src),
+                                         _p(add_mask_src), ctypes.byref(g), ctypes.byref(fuse) if fuse is not None else None, _p(ws),
+                                         ws.numel(), _stream()), 'bdv_conv_dgrad_f16x2')
+    elif use_x3:
         planes_d = weight_planes(w, g)[1] if plan.reads_planes else None
         check(lib().bdv_conv_dgrad_pl(_p(dy), _p(w), _p(planes_d), _p(dx), _p(add_src), _p(add_mask_src), ctypes.byref(g),
                                       ctypes.byref(fuse) if fuse is not None else None, _p(ws), ws.numel(), PIECES, _stream()),
@@ -541,6 +629,7 @@ def bn_apply(y, scale, shift, res=None, relu=True, out=None, want_mask=False, re
         _chk(rb, (C,), name='res_shift')
     o = out if out is not None else torch.empty_like(y)
     _chk_act(o, tuple(y.shape), name='out', like=y)
+    amax_forget(out)
     mask = None
     if want_mask:
         if not relu or C % 32 != 0:
@@ -578,6 +667,7 @@ def bn_backward(dout, relu_mask, y, gamma, save_mean, save_invstd, relu, dgamma=
     _chk(dbeta, (C,), name='dbeta')
     d = dy if dy is not None else torch.empty_like(y)
     _chk_act(d, tuple(y.shape), name='dy', like=y)
+    amax_forget(dy)
     srows = 0
     if stat_partial is not None:
         _chk(stat_partial, name='stat_partial')
@@ -733,6 +823,7 @@ def add(a, b, out=None):
     _chk_act(b, tuple(a.shape), name='b', like=a)
     o = out if out is not None else torch.empty_like(a)
     _chk_act(o, tuple(a.shape), name='out', like=a)
+    amax_forget(out)
     check(lib().bdv_add(_p(a), _p(b), _p(o), a.numel(), _act_code(a), _stream()), 'bdv_add')
     return o
 
@@ -1054,7 +1145,13 @@ def conv_wgrad_partial(dy: torch.Tensor, x: torch.Tensor, g: ConvGeom, x3: Optio
         _chk(pre_bn[0], (g.Cin,), name='pre_scale')
         _chk(pre_bn[1], (g.Cin,), name='pre_shift')
     slab = torch.empty((plan.splits, g.Cout, _taps_r(g), g.S, g.Cin), dtype=torch.float32, device=dy.device)
-    if use_x3:
+    if use_x3 and PIECES == F16X2:
+        f16 = _plan_f16(plan)
+        check(lib().bdv_conv_wgrad_partial_f16x2(_p(dy), _p(act_amax(dy) if f16 else None), _p(x), _p(act_amax(x) if f16 else None),
+                                                 ctypes.byref(g), _p(slab), slab.numel() * 4,
+                                                 _p(pre_bn[0] if pre_bn is not None else None), _p(pre_bn[1] if pre_bn is not None else None),
+                                                 _stream()), 'bdv_conv_wgrad_partial_f16x2')
+    elif use_x3:
         check(lib().bdv_conv_wgrad_partial_pl(_p(dy), _p(x), ctypes.byref(g), _p(slab), slab.numel() * 4, PIECES,
                                               _p(pre_bn[0] if pre_bn is not None else None), _p(pre_bn[1] if pre_bn is not None else None),
                                               _stream()), 'bdv_conv_wgrad_partial_pl')

@@ -90,7 +90,8 @@ const char* bdv_source_hash(void);
 size_t bdv_conv_workspace_bytes(const bdv_conv_geom* g, int kind);
 
 /* The plan of one call.  kind: 0 fprop, 1 dgrad, 2 wgrad.  arith: 0 = the fp32-MFMA entry points, 1 / 2 / 3 = the bf16-piece
- * entry points with that many pieces.  pre: the producer's BatchNorm is applied in the loader (pre_scale, below).
+ * entry points with that many pieces, 4 (BDV_ARITH_F16X2) = the two-fp16-piece entry points (bdv_conv_*_f16x2, below).
+ * pre: the producer's BatchNorm is applied in the loader (pre_scale, below).
  * Returns BDV_EINVAL (reason in bdv_last_error) where the library has no kernel for the request: dgrad of the Cin = 4 stem,
  * bf16 storage (g->act_dtype) outside pieces = 1 or on a geometry without a plane kernel, pre on a shifted site, ... */
 #define BDV_CONV_F32 0       /* 4 waves, fp32 MFMA, 128 x 128 / 128 x 64 tiles */
@@ -188,6 +189,37 @@ int bdv_conv_fprop_pl(const void* x, const float* w, const void* planes_fprop, v
 int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* planes_dgrad, void* dx, const void* add_src,
                       const uint32_t* add_mask_src, const bdv_conv_geom* g, const bdv_bn_stat_fuse* bn_stat, void* workspace,
                       size_t workspace_bytes, int pieces, void* stream);
+
+/* "f16x2": fp32-level products from TWO fp16 pieces per operand and three MFMA products (arith code BDV_ARITH_F16X2 of
+ * bdv_conv_plan_query).  Every operand tensor t has a device-resident amax word: the bits of an fp32 upper bound of max|t|
+ * (bdv_f16x2_amax writes the maximum itself; nothing is read back to the host).  The kernels derive the scale
+ *   S_t = 2^(14 - floor(log2 amax)), exponent clamped to [-113, 126]; S_t = 1 for amax = 0     (bdv_f16x2_scale on the host)
+ * so that max|t| * S_t lies in [2^14, 2^15) -- at 2^15 the leading piece could round to infinity -- and form
+ *   x = t * S_t,  hi = f16(x),  lo = f16(x - hi)   (round to nearest even; 11 + 11 significand bits and a sign),
+ *   hi_a * hi_w + hi_a * lo_w + lo_a * hi_w per K-step on v_mfma_f32_32x32x16_f16, smallest first, fp32 accumulate,
+ * and multiply the accumulators once by 1 / (S_a * S_w) (exponent clamped to the normal range) before the statistics rows, the
+ * affine / residual epilogue, the dgrad scatter and the K-split partials: a power of two, so it commutes with the fp32 fix-up adds.
+ * Error of a result: ~1e-7 of the output's scale, finer than an fp32 FMA chain.  Its one weakness: entries more than ~2^14 below
+ * the tensor's maximum fall into fp16's subnormal range after scaling and lose bits relative to their own size (DESIGN.md
+ * section 4).  Inf / NaN operands give Inf / NaN results.
+ * Scope, as pieces = 2: the plane kernels (and the 128 x 128 four-wave tile where the three-piece rules pick the conv_*_x3 kernels),
+ * fp32 tensors.  The stem, 64 GEMM columns behind a 1x1 filter and calls with pre_scale run the pieces = 3 kernels, bit-identical to
+ * the *_pl entry points with pieces = 3 (the plan's kernel name says which: the fp16 kernels end in "F16Pieces>").
+ * bdv_conv_split_weights_f16x2 takes the weight's maximum itself and writes hi / lo as planes 0 and 1 of the two layouts of
+ * bdv_conv_split_weights (buffers of bdv_conv_weight_planes_bytes(g) each); the third plane's place starts with the amax word.
+ * The planes of the two arithmetics cannot share a buffer.  x's amax serves fprop and wgrad, dy's dgrad and wgrad. */
+#define BDV_ARITH_F16X2 4
+int bdv_f16x2_amax(const float* t, int64_t n, void* amax, void* stream);   /* t 16-byte aligned, any n > 0; amax: 4 bytes */
+float bdv_f16x2_scale(float amax);                                          /* host: S_t of a tensor with this maximum */
+int bdv_conv_split_weights_f16x2(const float* w, const bdv_conv_geom* g, void* planes_fprop, void* planes_dgrad, void* stream);
+int bdv_conv_fprop_f16x2(const void* x, const void* amax_x, const float* w, const void* planes_fprop, void* y,
+                         const bdv_conv_geom* g, float* bn_partial, const bdv_conv_affine* affine, void* workspace,
+                         size_t workspace_bytes, const float* pre_scale, const float* pre_shift, void* stream);
+int bdv_conv_dgrad_f16x2(const void* dy, const void* amax_dy, const float* w, const void* planes_dgrad, void* dx,
+                         const void* add_src, const uint32_t* add_mask_src, const bdv_conv_geom* g,
+                         const bdv_bn_stat_fuse* bn_stat, void* workspace, size_t workspace_bytes, void* stream);
+int bdv_conv_wgrad_partial_f16x2(const void* dy, const void* amax_dy, const void* x, const void* amax_x, const bdv_conv_geom* g,
+                                 void* slab, size_t slab_bytes, const float* pre_scale, const float* pre_shift, void* stream);
 
 /* wgrad: dw[Cout,R,S,Cin] = beta * dw + sum_pixels dy (x) shift(x).  Deterministic split-K:
  * partial slabs go to `workspace`, a second kernel reduces them in fixed order. */
