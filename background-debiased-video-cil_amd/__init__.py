@@ -41,6 +41,7 @@ if 'GPU_MAX_HW_QUEUES' not in _os.environ:
                        'step time). Export GPU_MAX_HW_QUEUES=8 or import bdvcil_amd before the first torch.cuda call.',
                        RuntimeWarning, stacklevel=2)
 from .kernels import bump_weight_epoch  # noqa: F401,E402
+from .kernels import CONV_ARITH_MODES, conv_arith, get_conv_arith, set_conv_arith  # noqa: F401,E402
 
 from . import _lib, kernels  # noqa: F401,E402
 from .registry import (BACKBONES, HEADS, LOSSES, OPTIMIZER_BUILDERS, RECOGNIZERS, Registry, build_backbone,  # noqa: F401

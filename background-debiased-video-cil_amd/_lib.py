@@ -108,6 +108,8 @@ SIGNATURES = {
     'bdv_maxpool_bwd': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'bdv_maxpool_t2_fwd': (c_int, [P, P, P, c_int64, c_int64, P]),
     'bdv_maxpool_t2_bwd': (c_int, [P, P, P, c_int64, c_int64, P]),
+    'bdv_maxpool_t2_fwd_act': (c_int, [P, P, P, c_int64, c_int64, c_int, P]),
+    'bdv_maxpool_t2_bwd_act': (c_int, [P, P, P, c_int64, c_int64, c_int, P]),
     'bdv_bn_relu_maxpool_fwd': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'bdv_avgpool_fwd': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     'bdv_avgpool_bwd': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),

@@ -271,68 +271,107 @@ namespace {
 // MaxPool3d((2,1,1), stride (2,1,1)) of UPSTREAM mmaction ResNet3d (pool2, between layer1 and layer2 of I3D): the larger of
 // frames 2t and 2t + 1 of a clip, element by element.  sel: 1 bit per output element, set when the second frame won (ties
 // go to the first frame, as torch's max-pool does); the backward routes the gradient by it and writes zeros elsewhere.
-__global__ __launch_bounds__(256) void maxpool_t2_fwd_kernel(const float4* __restrict__ x, float4* __restrict__ out,
-                                                             uint32_t* __restrict__ sel, int64_t frame4, int64_t n4) {
+// ES: element size of x / out (dout / dx).  A lane moves one 16-byte unit, 4 * U elements (U = ActU<ES>: one float4, or two groups
+// of four bf16 values), so 8 / U neighbouring lanes fill one sel word and a frame has frame_elems / (4 * U) lanes: sel has the
+// same bits for a bf16 tensor as for the same values in fp32.  A bf16 maximum is one of its two bf16 inputs: the store is exact.
+template <int ES>
+__global__ __launch_bounds__(256) void maxpool_t2_fwd_kernel(const void* __restrict__ x, void* __restrict__ out,
+                                                             uint32_t* __restrict__ sel, int64_t frame_u, int64_t n_u) {
+  constexpr int U = ActU<ES>::value, L = 8 / U;
+  static_assert(U == 1 || U == 2, "a sel word is filled by 8 or 4 lanes");
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {   // n4, stride: multiples of 8
-    const int64_t f = i / frame4, r = i - f * frame4;
-    const float4 a = x[(2 * f) * frame4 + r], b = x[(2 * f + 1) * frame4 + r];
-    float4 o;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_u; i += stride) {   // n_u, stride: multiples of L
+    const int64_t f = i / frame_u, r = i - f * frame_u;
+    float4 a[U], b[U], o[U];
+    act_ld16<ES>(x, (2 * f) * frame_u + r, a);
+    act_ld16<ES>(x, (2 * f + 1) * frame_u + r, b);
     unsigned m = 0;
-    o.x = b.x > a.x ? (m |= 1u, b.x) : a.x;
-    o.y = b.y > a.y ? (m |= 2u, b.y) : a.y;
-    o.z = b.z > a.z ? (m |= 4u, b.z) : a.z;
-    o.w = b.w > a.w ? (m |= 8u, b.w) : a.w;
-    out[i] = o;
-    m <<= 4 * (threadIdx.x & 7);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      o[u].x = b[u].x > a[u].x ? (m |= 1u << (4 * u), b[u].x) : a[u].x;
+      o[u].y = b[u].y > a[u].y ? (m |= 2u << (4 * u), b[u].y) : a[u].y;
+      o[u].z = b[u].z > a[u].z ? (m |= 4u << (4 * u), b[u].z) : a[u].z;
+      o[u].w = b[u].w > a[u].w ? (m |= 8u << (4 * u), b[u].w) : a[u].w;
+    }
+    act_st16<ES>(out, i, o);
+    m <<= 4 * U * (threadIdx.x & (L - 1));
     m |= __shfl_xor(m, 1, 64);
     m |= __shfl_xor(m, 2, 64);
-    m |= __shfl_xor(m, 4, 64);
-    if ((threadIdx.x & 7) == 0) sel[i >> 3] = m;
+    if (L > 4) m |= __shfl_xor(m, 4, 64);
+    if ((threadIdx.x & (L - 1)) == 0) sel[i / L] = m;
   }
 }
 
-__global__ __launch_bounds__(256) void maxpool_t2_bwd_kernel(const float4* __restrict__ dout, const uint32_t* __restrict__ sel,
-                                                             float4* __restrict__ dx, int64_t frame4, int64_t n4) {
+template <int ES>
+__global__ __launch_bounds__(256) void maxpool_t2_bwd_kernel(const void* __restrict__ dout, const uint32_t* __restrict__ sel,
+                                                             void* __restrict__ dx, int64_t frame_u, int64_t n_u) {
+  constexpr int U = ActU<ES>::value, L = 8 / U;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const int64_t f = i / frame4, r = i - f * frame4;
-    const unsigned nib = (sel[i >> 3] >> (4 * (int)(i & 7))) & 0xFu;
-    const float4 g = dout[i];
-    float4 a, b;
-    a.x = (nib & 1u) ? 0.f : g.x; b.x = (nib & 1u) ? g.x : 0.f;
-    a.y = (nib & 2u) ? 0.f : g.y; b.y = (nib & 2u) ? g.y : 0.f;
-    a.z = (nib & 4u) ? 0.f : g.z; b.z = (nib & 4u) ? g.z : 0.f;
-    a.w = (nib & 8u) ? 0.f : g.w; b.w = (nib & 8u) ? g.w : 0.f;
-    dx[(2 * f) * frame4 + r] = a;
-    dx[(2 * f + 1) * frame4 + r] = b;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_u; i += stride) {
+    const int64_t f = i / frame_u, r = i - f * frame_u;
+    const unsigned bits = sel[i / L] >> (4 * U * (int)(i & (L - 1)));
+    float4 g[U], a[U], b[U];
+    act_ld16<ES>(dout, i, g);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const unsigned nib = (bits >> (4 * u)) & 0xFu;
+      a[u].x = (nib & 1u) ? 0.f : g[u].x; b[u].x = (nib & 1u) ? g[u].x : 0.f;
+      a[u].y = (nib & 2u) ? 0.f : g[u].y; b[u].y = (nib & 2u) ? g[u].y : 0.f;
+      a[u].z = (nib & 4u) ? 0.f : g[u].z; b[u].z = (nib & 4u) ? g[u].z : 0.f;
+      a[u].w = (nib & 8u) ? 0.f : g[u].w; b[u].w = (nib & 8u) ? g[u].w : 0.f;
+    }
+    act_st16<ES>(dx, (2 * f) * frame_u + r, a);
+    act_st16<ES>(dx, (2 * f + 1) * frame_u + r, b);
   }
+}
+
+// units of a launch: frame_elems % 32 == 0 keeps a frame and the whole tensor whole numbers of sel words
+template <int ES>
+inline void pool_t2_units(int64_t frames_out, int64_t frame_elems, int64_t* frame_u, int64_t* n_u, int* blocks) {
+  *frame_u = frame_elems / (4 * ActU<ES>::value);
+  *n_u = frames_out * *frame_u;
+  const int64_t b = (*n_u + 255) / 256;
+  *blocks = (int)(b > (1 << 20) ? (1 << 20) : b);
 }
 }  // namespace
 
-extern "C" int bdv_maxpool_t2_fwd(const float* x, float* out, uint32_t* sel, int64_t frames_out, int64_t frame_elems, void* stream) {
+extern "C" int bdv_maxpool_t2_fwd_act(const void* x, void* out, uint32_t* sel, int64_t frames_out, int64_t frame_elems, int act_dtype,
+                                      void* stream) {
+  BDV_REQUIRE_ACT(act_dtype, "bdv_maxpool_t2_fwd");
   BDV_REQUIRE(x && out && sel && frames_out > 0 && frame_elems > 0 && frame_elems % 32 == 0, "bdv_maxpool_t2_fwd: bad argument");
-  BDV_REQUIRE(bdv_aligned16(x) && bdv_aligned16(out), "bdv_maxpool_t2_fwd: alignment");
-  const int64_t n4 = frames_out * frame_elems / 4;
-  int64_t blocks = (n4 + 255) / 256;
-  if (blocks > (1 << 20)) blocks = 1 << 20;
-  hipLaunchKernelGGL(maxpool_t2_fwd_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (const float4*)x, (float4*)out, sel,
-                     frame_elems / 4, n4);
+  BDV_REQUIRE(bdv_aligned16(x) && bdv_aligned16(out) && (((uintptr_t)sel) & 3) == 0, "bdv_maxpool_t2_fwd: alignment");
+  BDV_ACT_SWITCH(act_dtype, ES, {
+    int64_t frame_u, n_u;
+    int blocks;
+    pool_t2_units<ES>(frames_out, frame_elems, &frame_u, &n_u, &blocks);
+    hipLaunchKernelGGL((maxpool_t2_fwd_kernel<ES>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, out, sel, frame_u, n_u);
+  });
   BDV_LAUNCH_CHECK("bdv_maxpool_t2_fwd");
   return BDV_OK;
 }
 
-extern "C" int bdv_maxpool_t2_bwd(const float* dout, const uint32_t* sel, float* dx, int64_t frames_out, int64_t frame_elems,
-                                  void* stream) {
+extern "C" int bdv_maxpool_t2_bwd_act(const void* dout, const uint32_t* sel, void* dx, int64_t frames_out, int64_t frame_elems,
+                                      int act_dtype, void* stream) {
+  BDV_REQUIRE_ACT(act_dtype, "bdv_maxpool_t2_bwd");
   BDV_REQUIRE(dout && dx && sel && frames_out > 0 && frame_elems > 0 && frame_elems % 32 == 0, "bdv_maxpool_t2_bwd: bad argument");
-  BDV_REQUIRE(bdv_aligned16(dout) && bdv_aligned16(dx), "bdv_maxpool_t2_bwd: alignment");
-  const int64_t n4 = frames_out * frame_elems / 4;
-  int64_t blocks = (n4 + 255) / 256;
-  if (blocks > (1 << 20)) blocks = 1 << 20;
-  hipLaunchKernelGGL(maxpool_t2_bwd_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (const float4*)dout, sel, (float4*)dx,
-                     frame_elems / 4, n4);
+  BDV_REQUIRE(bdv_aligned16(dout) && bdv_aligned16(dx) && (((uintptr_t)sel) & 3) == 0, "bdv_maxpool_t2_bwd: alignment");
+  BDV_ACT_SWITCH(act_dtype, ES, {
+    int64_t frame_u, n_u;
+    int blocks;
+    pool_t2_units<ES>(frames_out, frame_elems, &frame_u, &n_u, &blocks);
+    hipLaunchKernelGGL((maxpool_t2_bwd_kernel<ES>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, dout, sel, dx, frame_u, n_u);
+  });
   BDV_LAUNCH_CHECK("bdv_maxpool_t2_bwd");
   return BDV_OK;
+}
+
+extern "C" int bdv_maxpool_t2_fwd(const float* x, float* out, uint32_t* sel, int64_t frames_out, int64_t frame_elems, void* stream) {
+  return bdv_maxpool_t2_fwd_act(x, out, sel, frames_out, frame_elems, BDV_ACT_F32, stream);
+}
+
+extern "C" int bdv_maxpool_t2_bwd(const float* dout, const uint32_t* sel, float* dx, int64_t frames_out, int64_t frame_elems,
+                                  void* stream) {
+  return bdv_maxpool_t2_bwd_act(dout, sel, dx, frames_out, frame_elems, BDV_ACT_F32, stream);
 }
 
 

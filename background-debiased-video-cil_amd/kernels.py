@@ -168,6 +168,49 @@ def set_conv_arith(mode: str):
     return prev
 
 
+CONV_ARITH_MODES = ('bf16x3', 'f32mfma', 'bf16x2', 'f16x2', 'bf16x1', 'bf16')
+
+
+def check_conv_arith(mode: str) -> str:
+    """``mode`` if it is one of ``CONV_ARITH_MODES``, else ``ValueError``; touches nothing."""
+    if mode not in CONV_ARITH_MODES:
+        raise ValueError(f"conv_arith: unknown mode {mode!r} ({' | '.join(repr(m) for m in CONV_ARITH_MODES)})")
+    return mode
+
+
+def get_conv_arith() -> str:
+    """The name ``set_conv_arith`` would need to produce the arithmetic in force, or 'custom' when no name does (a per-direction
+    override: the BDVCIL_*_X3 environment switches, or a direct write of the flags)."""
+    flags = (bool(FPROP_X3), bool(DGRAD_X3), bool(WGRAD_X3))
+    if ACT_DTYPE == torch.bfloat16:
+        return 'bf16' if flags == (True, True, True) and PIECES == 1 else 'custom'
+    if flags == (False, False, False):
+        return 'f32mfma' if PIECES == 3 else 'custom'
+    if flags != (True, True, True):
+        return 'custom'
+    return {3: 'bf16x3', 2: 'bf16x2', F16X2: 'f16x2', 1: 'bf16x1'}.get(PIECES, 'custom')
+
+
+import contextlib as _contextlib
+
+
+@_contextlib.contextmanager
+def conv_arith(mode: str):
+    """``with conv_arith(mode):`` -- ``set_conv_arith(mode)`` for the body, and on the way out (normally or through an exception)
+    everything that call writes is put back: the three direction flags, ``PIECES`` and ``ACT_DTYPE``, whatever they were (a 'custom'
+    state included), and the cached operand maxima of 'f16x2' are dropped again.  Blocks nest.  An unknown mode raises ``ValueError``
+    before anything changes.  Process-wide like ``set_conv_arith``: not for two threads that want different arithmetics."""
+    global FPROP_X3, DGRAD_X3, WGRAD_X3, PIECES, ACT_DTYPE
+    check_conv_arith(mode)
+    saved = (FPROP_X3, DGRAD_X3, WGRAD_X3, PIECES, ACT_DTYPE)
+    set_conv_arith(mode)
+    try:
+        yield mode
+    finally:
+        FPROP_X3, DGRAD_X3, WGRAD_X3, PIECES, ACT_DTYPE = saved
+        _AMAX.clear()
+
+
 # ---- weights as bf16 planes (bdv_conv_split_weights), cached per weight tensor -----------------------------------------
 # A conv weight is cut into its hi / mid / lo planes once per value: the entry of a weight is refreshed when torch's version
 # counter of the tensor moved (any in-place torch op, load_state_dict, torch optimizers), when its storage moved, or when
@@ -870,23 +913,24 @@ def bn_relu_maxpool_fwd(y, scale, shift, out_dtype=torch.float32):
 
 
 def maxpool_t2_fwd(x):
-    """MaxPool3d((2,1,1),(2,1,1)) on frames (2n, H, W, C) -> ((n, H, W, C), sel bit mask)."""
-    _chk(x, name='x')
+    """MaxPool3d((2,1,1),(2,1,1)) on frames (2n, H, W, C) -> ((n, H, W, C), sel bit mask).  The output has x's storage type."""
+    _chk_act(x, name='x')
     N2, H, W, C = x.shape
     if N2 % 2 or (H * W * C) % 32:
         raise ValueError(f'maxpool_t2_fwd: {tuple(x.shape)}: needs an even frame count and H*W*C % 32 == 0')
-    out = torch.empty((N2 // 2, H, W, C), dtype=torch.float32, device=x.device)
+    out = torch.empty((N2 // 2, H, W, C), dtype=x.dtype, device=x.device)
     sel = torch.empty(out.numel() // 32, dtype=torch.int32, device=x.device)
-    check(lib().bdv_maxpool_t2_fwd(_p(x), _p(out), _p(sel), N2 // 2, H * W * C, _stream()), 'bdv_maxpool_t2_fwd')
+    check(lib().bdv_maxpool_t2_fwd_act(_p(x), _p(out), _p(sel), N2 // 2, H * W * C, _act_code(x), _stream()), 'bdv_maxpool_t2_fwd_act')
     return out, sel
 
 
 def maxpool_t2_bwd(dout, sel):
-    _chk(dout, name='dout')
+    """-> dx (2n, H, W, C) in dout's storage type: the gradient at the frame ``sel`` names, zero at the other one."""
+    _chk_act(dout, name='dout')
     n, H, W, C = dout.shape
     _chk(sel, (dout.numel() // 32,), dtype=torch.int32, name='sel')
-    dx = torch.empty((2 * n, H, W, C), dtype=torch.float32, device=dout.device)
-    check(lib().bdv_maxpool_t2_bwd(_p(dout), _p(sel), _p(dx), n, H * W * C, _stream()), 'bdv_maxpool_t2_bwd')
+    dx = torch.empty((2 * n, H, W, C), dtype=dout.dtype, device=dout.device)
+    check(lib().bdv_maxpool_t2_bwd_act(_p(dout), _p(sel), _p(dx), n, H * W * C, _act_code(dout), _stream()), 'bdv_maxpool_t2_bwd_act')
     return dx
 
 

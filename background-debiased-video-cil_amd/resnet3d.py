@@ -3,7 +3,8 @@ configs/_base_/models/i3d_r50.py:1-27) on the same HIP kernels as the TSM path -
 BASELINE.json config 4.  Parity unpinned: mmaction2 is not vendored and the reference holds no fixture for this model; the CPU
 restatement used by the parity tests lives in the checker directory (i3d_*.py).
 
-How the 3-D network maps onto the 2-D kernels (activations stay fp32 NHWC frames, ``[B*T][H][W][C]``):
+How the 3-D network maps onto the 2-D kernels (activations stay NHWC frames, ``[B*T][H][W][C]``; fp32, or under the 'bf16'
+arithmetic bf16 from pool1's output to the average pool's input, as in the 2-D model):
 
 * ``1 x k x k`` and ``1 x 1 x 1`` convolutions (conv2, conv3, downsample) are per-frame convolutions: N = B*T.
 * the inflated ``3 x 1 x 1`` conv1 of a bottleneck runs as a ``3 x 1`` convolution on the ``[B][T][H*W][C]`` view of the same
@@ -148,7 +149,7 @@ class _Stem3dFn(torch.autograd.Function):
         # pool1: temporal kernel 1, stride 2 -> the even frames; spatial 3x3 / 2
         Tp = (To - 1) // 2 + 1
         even = a.view(B, To, g.Ho, g.Wo, Cout)[:, ::2].contiguous().view(B * Tp, g.Ho, g.Wo, Cout)
-        p, pidx = K.maxpool_fwd(even)
+        p, pidx = K.maxpool_fwd(even, out_dtype=K.ACT_DTYPE)        # the first tensor in the activation storage type, as in the 2-D stem
         if mask is not None:                                        # tests: the stem's ReLU sign bits / pool1's arg-max codes
             Fn._tap_mask(y.shape, mask)
         Fn._tap_pool(pidx)
@@ -173,7 +174,7 @@ class _Stem3dFn(torch.autograd.Function):
             gamma, y, mask, pidx, mean, invstd, *taps = ctx.saved_tensors     # (eval-mode 'affine': the scale in gamma's place)
             Cout = y.shape[-1]
         dp = dp if dp.is_contiguous() else dp.contiguous()
-        d_even = K.maxpool_bwd(dp, pidx, (B * Tp, g.Ho, g.Wo, Cout))
+        d_even = K.maxpool_bwd(dp, pidx, (B * Tp, g.Ho, g.Wo, Cout))      # dp carries the storage type; fp32 from here on
         da = torch.zeros((B, To, g.Ho, g.Wo, Cout), dtype=torch.float32, device=dp.device)   # odd frames: unused by pool1
         da[:, ::2] = d_even.view(B, Tp, g.Ho, g.Wo, Cout)
         da = da.view(B * To, g.Ho, g.Wo, Cout)

@@ -14,6 +14,7 @@ All tensor arithmetic goes through the HIP-backed modules of this package (``cil
 from __future__ import annotations
 
 import copy
+import functools
 import os
 import os.path as osp
 import pathlib
@@ -24,6 +25,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import kernels as K
 from .cil_step import base_training_step, icarl_training_step, icarl_video_mix_training_step
 from .ddp import GradAllReducer, broadcast_parameters
 from .hooks import OutputHook
@@ -336,6 +338,38 @@ def task_accuracies(preds: torch.Tensor, labels: torch.Tensor, sizes: Sequence[i
     return meter
 
 
+def check_loop_conv_arith(config) -> Optional[str]:
+    """The ``conv_arith`` key of a loop config, validated without touching the GPU: None (absent: the process's arithmetic stays), or
+    one of ``kernels.CONV_ARITH_MODES``.  'bf16' stores activations as bf16, and the backward through an eval-mode BatchNorm is
+    not implemented for that storage: a backbone with ``norm_eval=True`` or ``partial_bn=True`` trains through one, so the
+    combination is refused here and not at the first backward of task 0.  ``frozen_stages`` alone sends no gradient through the
+    frozen part and is fine."""
+    mode = config.get('conv_arith')
+    if mode is None:
+        return None
+    K.check_conv_arith(mode)
+    backbone = (config.get('model') or {}).get('backbone') or {}
+    if mode == 'bf16':
+        bad = [k for k in ('norm_eval', 'partial_bn') if backbone.get(k)]
+        if bad:
+            raise ValueError(f"conv_arith='bf16' cannot be combined with {' / '.join(k + '=True' for k in bad)} of the backbone: the "
+                             f"backward through eval-mode BatchNorm is not implemented for bf16 activation storage; use "
+                             f"conv_arith='bf16x1' (the same arithmetic on fp32 tensors) or drop {' / '.join(bad)}")
+    return mode
+
+
+def _in_arith(fn):
+    """A public entry point of the loop runs under the loop's ``conv_arith`` (nothing to do without one); the process's own
+    arithmetic is back when it returns or raises.  Entry points call each other: the blocks nest."""
+    @functools.wraps(fn)
+    def run(self, *a, **kw):
+        if self.conv_arith is None:
+            return fn(self, *a, **kw)
+        with K.conv_arith(self.conv_arith):
+            return fn(self, *a, **kw)
+    return run
+
+
 class CILTaskLoop:
     """``CILTrainer`` (libs/cil/cil.py:622-1140) on the HIP path.
 
@@ -352,11 +386,17 @@ class CILTaskLoop:
     batches, and so the files of the run, do not depend on ``prefetch``; an unseeded loader draws from the process-global generators
     on the worker thread and is not reproducible under prefetch.  An exception the loader raises surfaces at its batch, on the
     calling thread; the worker is shut down before it propagates.  ``close()`` releases the thread.
+
+    Config key ``conv_arith``: a mode of ``kernels.set_conv_arith`` for everything the loop computes -- the current model, the teacher,
+    feature extraction, class means, testing.  Every public entry point enters ``kernels.conv_arith(mode)`` and leaves the process's
+    arithmetic as it found it; None / absent changes nothing.  Parameters and BatchNorm buffers are fp32 in every mode, so the files of
+    a work_dir do not depend on it.  Unknown modes, and 'bf16' with ``norm_eval`` / ``partial_bn``, raise ``ValueError`` here.
     """
 
     def __init__(self, config, clip_loader: Callable[[List[dict], str], Dict], device='cuda', seed: int = 0, log: Callable = print,
                  prefetch: Optional[int] = None):
         self.config = config = config if isinstance(config, AttrDict) else AttrDict(config)
+        self.conv_arith = check_loop_conv_arith(config)         # before any file or GPU work
         self.device = torch.device(device)
         self.clip_loader = clip_loader
         self.prefetch = int(config.get('prefetch_batches', 0) if prefetch is None else prefetch)
@@ -417,7 +457,7 @@ class CILTaskLoop:
         if self.starting_task == 0:
             self.reload_train_dataset(use_internal_exemplar=False)
         else:
-            self._resume()
+            self._resume()              # may extract features to rebuild exemplar files: under the loop's arithmetic
         for i in range(self.num_tasks):
             self.val_datasets.append(RawframeRecords(str(self.files.task_splits_ann_files['val'][i]), config.data_root,
                                                      test_mode=True, phase='val'))
@@ -506,6 +546,7 @@ class CILTaskLoop:
             torch.save(obj, tmp)
             os.replace(tmp, path)
 
+    @_in_arith
     def _resume(self):
         """libs/cil/cil.py:659-696: rebuild exemplars (from disk, or by re-extracting them), roll back one task to
         load its weights into both models, then grow both classifiers to the starting task."""
@@ -564,6 +605,7 @@ class CILTaskLoop:
                                   kd_exemplar_only=cfg.get('kd_exemplar_only', False),
                                   previous_task_num_classes=self.num_classes(t - 1))
 
+    @_in_arith
     def fit(self, records: RawframeRecords, max_epochs: int, validate: bool = False) -> List[float]:
         """One ``pl.Trainer.fit`` (libs/cil/cil.py:745-760, :776-800): a fresh optimizer + scheduler from the config
         of the current ``optimizer_mode``, gradient clipping by global norm 1.0 after task 0, gradient accumulation
@@ -650,6 +692,7 @@ class CILTaskLoop:
             self._save_state(self.current_model.state_dict(), self.files.ckpt_file(self._current_task))
         return acc
 
+    @_in_arith
     def train_task(self) -> List[float]:
         self.training_phase = 'inc_step'
         validate = bool(self.config.get('save_best', False)) and self._current_task == 0
@@ -674,6 +717,7 @@ class CILTaskLoop:
                 cbf.bg_files = []
         return cbf
 
+    @_in_arith
     def train_cbf(self) -> List[float]:
         self.training_phase = 'cbf_step'
         validate = bool(self.config.get('save_best', False))
@@ -698,6 +742,7 @@ class CILTaskLoop:
         out = RawframeRecords(None, None, test_mode=True, phase=phase)
         return out.extend(datasets)
 
+    @_in_arith
     @torch.no_grad()
     def predict(self, records: RawframeRecords, batch_size: int, extract_repr: bool = True, extract_meta: bool = False) -> List[Dict]:
         """``CILTrainer.predict`` (libs/cil/cil.py:1091-1140) without the per-rank writer files: every rank runs the
@@ -784,6 +829,7 @@ class CILTaskLoop:
         return cnn, nme
 
     # -- the loop (libs/cil/cil.py:806-861) ------------------------------------------------------------------------------
+    @_in_arith
     def train(self):
         cfg = self.config
         while self._current_task < self.num_tasks:
@@ -815,6 +861,7 @@ class CILTaskLoop:
                 self.reload_train_dataset(use_internal_exemplar=True)
         return self.history
 
+    @_in_arith
     def cil_testing(self, test_nme: bool = False):
         """libs/cil/cil.py:985-1030: re-test every task's checkpoint, write ``cnn_result.txt`` / ``nme_result.txt``."""
         tmp = self._current_task

@@ -356,6 +356,14 @@ int bdv_maxpool_bwd(const void* dout, const uint8_t* idx, float* dx, int N, int 
  * per clip keeps pairs inside a clip).  sel: 1 bit per output element (second frame won); the backward fills dx completely. */
 int bdv_maxpool_t2_fwd(const float* x, float* out, uint32_t* sel, int64_t frames_out, int64_t frame_elems, void* stream);
 int bdv_maxpool_t2_bwd(const float* dout, const uint32_t* sel, float* dx, int64_t frames_out, int64_t frame_elems, void* stream);
+/* The same pool2 on tensors of either storage type (act_dtype: BDV_ACT_F32 | BDV_ACT_BF16 = element type of x and out, resp.
+ * dout and dx): I3D under bf16 storage, where layer1's output and layer2's input gradient are bf16 (UPSTREAM ResNet3d.forward,
+ * `if i == 0 and self.with_pool2: x = self.pool2(x)`).  sel is the same word for word as for the same values in fp32; ties go to
+ * the first frame; BDV_ACT_F32 is the two entry points above. */
+int bdv_maxpool_t2_fwd_act(const void* x, void* out, uint32_t* sel, int64_t frames_out, int64_t frame_elems, int act_dtype,
+                           void* stream);
+int bdv_maxpool_t2_bwd_act(const void* dout, const uint32_t* sel, void* dx, int64_t frames_out, int64_t frame_elems, int act_dtype,
+                           void* stream);
 /* Stem tail of a training forward in one pass (UPSTREAM ConvModule norm+act, then ResNet.maxpool): a = relu(y * scale +
  * shift), out = maxpool(a), idx as bdv_maxpool_fwd, relu_mask = 1 bit per element of a (a > 0) as bdv_bn_apply writes it.
  * The activation a itself is not materialised. */

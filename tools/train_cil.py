@@ -1,12 +1,16 @@
 """Run a CIL config file end to end: train every task of the config, or re-test the checkpoints of a finished run.
 
     VIDEO_CIL_ROOT=/data/ucf101 python tools/train_cil.py CONFIG [--test] [--test-nme] [--prefetch N] [--seed S] [--device D]
+        [--conv-arith {bf16x3,f32mfma,bf16x2,f16x2,bf16x1,bf16}]
 
 CONFIG is a config file of the reference (configs/ucf101/..., self-contained Python that reads VIDEO_CIL_ROOT).  The clip loader is
 built from the config's ``data.train`` and its four pipelines (``bdvcil_amd.clip_loader_spec``; a stage the loaders cannot honour is an
 error, not a guess), and ``CILTaskLoop`` leaves the reference's files in the config's ``work_dir``; training ends with the re-test of
 every task's checkpoint (``cnn_result.txt``; with ``--test-nme`` also ``nme_result.txt``), and ``--test`` does only that.  ``--seed`` seeds the loader's own generators,
 the shuffle and the process-global generators the training step draws from, which makes a run reproducible at any ``--prefetch``.
+``--conv-arith`` sets the config's ``conv_arith`` key (the conv arithmetic of everything the loop computes; it wins over the config
+file, and without either the default arithmetic runs); the files of the work_dir are fp32 in every mode, so a run trained under one
+mode re-tests under any other.
 Several GPUs: start one process per GPU with torchrun; the process group is picked up from the environment."""
 import argparse
 import os
@@ -15,7 +19,10 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main(argv=None):
+CONV_ARITH_MODES = ('bf16x3', 'f32mfma', 'bf16x2', 'f16x2', 'bf16x1', 'bf16')      # bdvcil_amd.CONV_ARITH_MODES (checked in main)
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('config')
     ap.add_argument('--test', action='store_true', help='re-test the checkpoints of the work_dir instead of training')
@@ -24,9 +31,16 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=None)
     ap.add_argument('--device', default=None)
     ap.add_argument('--threads', type=int, default=8, help='host threads of the JPEG entropy stage')
-    args = ap.parse_args(argv)
+    ap.add_argument('--conv-arith', choices=CONV_ARITH_MODES, default=None,
+                    help="conv arithmetic of the run (the config's conv_arith key; default: the config's, else bf16x3)")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     import bdvcil_amd as bd           # before the first torch.cuda call (GPU_MAX_HW_QUEUES)
+    assert tuple(bd.CONV_ARITH_MODES) == CONV_ARITH_MODES
     import torch
     import torch.distributed as dist
     local = int(os.environ.get('LOCAL_RANK', 0))
@@ -41,6 +55,8 @@ def main(argv=None):
         np.random.seed(args.seed)
         torch.manual_seed(args.seed)
     cfg = bd.load_config(args.config)
+    if args.conv_arith is not None:
+        cfg['conv_arith'] = args.conv_arith
     rank = dist.get_rank() if dist.is_initialized() else 0
     # each rank loads its own share of an epoch: its loader draws from its own stream
     loader = bd.build_clip_loader(cfg, device=device, seed=None if args.seed is None else args.seed + rank, threads=args.threads)
