@@ -19,6 +19,8 @@ Import as ``bdvcil_amd`` (see ``bdvcil_amd.py`` at the repo root).  Layout:
 * ``resnet3d``     I3D-ResNet50 (ResNet3d / I3DHead / Recognizer3D) on the same kernels (temporal convs as k x 1 convs)
 * ``task_loop``    the CIL task loop (CILTrainer + CILDataModule bookkeeping, same files on disk)
 * ``config_run``   a reference config file -> the clip loader that computes its pipelines (``tools/train_cil.py`` runs one)
+* ``gradcam``      Grad-CAM of a 2D recognizer: map, colormap overlay and the map's share inside person boxes (csrc/gradcam.hip)
+* ``bias``         background reliance of a trained model: actor attention and scene-only accuracy (``tools/bias_report.py``)
 """
 import os as _os
 
@@ -66,5 +68,7 @@ from .ddp import GradAllReducer, broadcast_parameters  # noqa: F401
 from .representation import Herding, ReprPredictor, class_means_from_repr, nme_classify  # noqa: F401
 from .task_loop import AttrDict, CILTaskLoop, CILWorkDir, RawframeRecords, SyntheticClipLoader, TaskSplits  # noqa: F401
 from .config_run import build_clip_loader, clip_loader_spec, load_config  # noqa: F401
+from .gradcam import GradCAM  # noqa: F401
+from . import bias, gradcam  # noqa: F401,E402
 
 __version__ = '0.1.0'

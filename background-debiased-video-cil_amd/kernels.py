@@ -1172,6 +1172,98 @@ def actor_cut_mix_u8(actor, scene, plan, nclips: int, out, mean, std):
           'bdv_actor_cut_mix_u8')
     return counts
 
+
+def gradcam_map(act, wgt):
+    """``bdv_gradcam_map``: act (N, h, w, C) fp32 NHWC, wgt (N, C) fp32 -> (N, h, w) = relu(sum_c wgt[n, c] * act[n, y, x, c])."""
+    _chk(act, name='act')
+    if act.dim() != 4:
+        raise ValueError(f'gradcam_map: act must be (N, h, w, C), got {tuple(act.shape)}')
+    N, h, w, C = (int(d) for d in act.shape)
+    if N == 0 or h * w == 0 or C == 0 or C % 4:
+        raise ValueError(f'gradcam_map: act {tuple(act.shape)}: every dimension must be positive and C a multiple of 4')
+    _chk(wgt, (N, C), name='wgt')
+    out = torch.empty((N, h, w), dtype=torch.float32, device=act.device)
+    check(lib().bdv_gradcam_map(_p(act), _p(wgt), _p(out), N, h * w, C, _stream()), 'bdv_gradcam_map')
+    return out
+
+
+def _gradcam_dims(m, B, T, H, W, who):
+    _chk(m, name='map')
+    B, T, H, W = int(B), int(T), int(H), int(W)
+    if m.dim() != 3 or B <= 0 or T <= 0 or m.shape[0] != B * T or m.shape[1] == 0 or m.shape[2] == 0:
+        raise ValueError(f'{who}: map must be (B*T, h, w) = ({B * T}, h, w), got {tuple(m.shape)}')
+    if H <= 0 or W <= 0:
+        raise ValueError(f'{who}: output size {(H, W)} must be positive')
+    return B, T, int(m.shape[1]), int(m.shape[2]), H, W
+
+
+def gradcam_minmax(m, B: int, T: int, H: int, W: int):
+    """``bdv_gradcam_minmax``: m (B*T, h, w) fp32, non-negative -> (2, B): per clip the minimum (row 0) and maximum (row 1) of the map
+    upsampled per frame to (H, W) (bilinear, align_corners=False)."""
+    B, T, h, w, H, W = _gradcam_dims(m, B, T, H, W, 'gradcam_minmax')
+    out = torch.empty((2, B), dtype=torch.float32, device=m.device)
+    check(lib().bdv_gradcam_minmax(_p(m), B, T, h, w, H, W, _p(out), _stream()), 'bdv_gradcam_minmax')
+    return out
+
+
+def gradcam_render(m, minmax, B: int, T: int, H: int, W: int, want_map: bool = True, frames4=None, lut=None, alpha: float = 0.5,
+                   mean=None, std=None, box_offsets=None, boxes=None):
+    """``bdv_gradcam_render``: m (B*T, h, w), minmax (2, B) from ``gradcam_minmax`` -> ``(v, overlay, sums)``, each None unless asked for:
+    v (B, T, H, W) fp32 when ``want_map``; overlay (B, T, H, W, 3) uint8 when ``frames4`` (B*T, H, W, 4) -- the normalised frames --
+    is given, with ``lut`` (256, 3) fp32 on the device, ``alpha``, and the Normalize ``mean`` / ``std``; sums (B, 2) fp32 =
+    (sum v, sum v inside the boxes) when ``box_offsets`` (B*T + 1,) and ``boxes`` (n, 4) -- host arrays, x0 y0 x1 y1 in output
+    pixels -- are given.  The tables are validated on the host (here and in the library) before the launch."""
+    B, T, h, w, H, W = _gradcam_dims(m, B, T, H, W, 'gradcam_render')
+    _chk(minmax, (2, B), name='minmax')
+    dev = m.device
+    v = torch.empty((B, T, H, W), dtype=torch.float32, device=dev) if want_map else None
+    overlay, f3 = None, ctypes.c_float * 3
+    mean3, std3 = f3(0.0, 0.0, 0.0), f3(1.0, 1.0, 1.0)
+    if frames4 is not None:
+        _chk(frames4, (B * T, H, W, 4), name='frames4')
+        if lut is None or mean is None or std is None:
+            raise ValueError('gradcam_render: the overlay needs lut, mean and std')
+        _chk(lut, (256, 3), name='lut')
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f'gradcam_render: alpha {alpha} outside [0, 1]')
+        mean3 = f3(*torch.tensor(list(mean), dtype=torch.float32).tolist())
+        std3 = f3(*torch.tensor(list(std), dtype=torch.float32).tolist())
+        overlay = torch.empty((B, T, H, W, 3), dtype=torch.uint8, device=dev)
+    sums = off_h = box_h = off_d = box_d = ws = None
+    nbox, ws_bytes = 0, 0
+    if (box_offsets is None) != (boxes is None):
+        raise ValueError('gradcam_render: box_offsets and boxes come together')
+    if box_offsets is not None:
+        off64 = torch.as_tensor(box_offsets).to('cpu').reshape(-1)
+        if off64.is_floating_point() or off64.dtype == torch.bool:
+            raise TypeError(f'gradcam_render: box_offsets must be integers, got {off64.dtype}')
+        off64 = off64.to(torch.int64)
+        box_h = torch.as_tensor(boxes).to('cpu', torch.float32).contiguous()
+        if box_h.numel() == 0:
+            box_h = box_h.reshape(0, 4)
+        if box_h.dim() != 2 or box_h.shape[1] != 4:
+            raise ValueError(f'gradcam_render: boxes must be (n, 4), got {tuple(box_h.shape)}')
+        nbox = int(box_h.shape[0])
+        if off64.numel() != B * T + 1:
+            raise ValueError(f'gradcam_render: {off64.numel()} box offsets for {B * T} frames ({B * T + 1} expected)')
+        if int(off64[0]) != 0 or bool((off64[1:] < off64[:-1]).any()):
+            raise ValueError('gradcam_render: box offsets must start at 0 and must not decrease')
+        if int(off64[-1]) != nbox:
+            raise ValueError(f'gradcam_render: the box offsets end at {int(off64[-1])}, the table has {nbox} rows')
+        if bool(torch.isnan(box_h).any()):
+            raise ValueError('gradcam_render: a box holds a NaN')
+        off_h = off64.to(torch.int32).contiguous()
+        off_d, box_d = off_h.to(dev), (box_h.to(dev) if nbox else None)
+        sums = torch.empty((B, 2), dtype=torch.float32, device=dev)
+        ws_bytes = int(lib().bdv_gradcam_workspace_bytes(B, T, H))
+        ws = workspace(ws_bytes, dev, 'gradcam')
+    if v is None and overlay is None and sums is None:
+        raise ValueError('gradcam_render: nothing requested (want_map, frames4 or boxes)')
+    check(lib().bdv_gradcam_render(_p(m), _p(minmax), B, T, h, w, H, W, _p(v), _p(frames4), _p(lut), float(alpha), mean3, std3, _p(overlay),
+                                   _p(off_d), off_h.data_ptr() if off_h is not None else None, _p(box_d),
+                                   box_h.data_ptr() if nbox else None, nbox, _p(sums), _p(ws), ws_bytes, _stream()), 'bdv_gradcam_render')
+    return v, overlay, sums
+
 WGRAD_X3 = _x3_default('BDVCIL_WGRAD_X3')
 
 

@@ -640,6 +640,41 @@ int bdv_jpeg_entropy_encode(const short* coefs, int width, int height, int quali
 int bdv_jpeg_entropy_encode_batch(const short* coefs, int n, int width, int height, int quality, unsigned char* out, size_t stride,
                                   size_t* sizes, int threads);
 
+/* ---- Grad-CAM ----------------------------------------------------------
+ * UPSTREAM mmaction2 GradCAM (mmaction/utils/gradcam_utils.py, _calculate_localization_map and __call__, for a 2D recognizer);
+ * the reference repository has no counterpart and mmaction2 is not vendored: restated from memory, PARITY UNPINNED.  All tensors
+ * fp32; no float atomics, every result is bit-identical from run to run.
+ *
+ * bdv_gradcam_map (device): act (N, HW, C) -- the tapped activation in NHWC storage -- and wgt (N, C), the spatial mean of the
+ * gradient (bdv_avgpool_fwd on it) -> map (N, HW) = max(0, sum_c wgt[n, c] * act[n, p, c]).  C % 4 == 0, act and wgt 16-byte
+ * aligned.  One wave per pixel: fmaf in channel order inside a lane (channels 4l .. 4l+3, 4(l+64) .., ...), then a fixed butterfly
+ * over the 64 lanes.  -0 and NaN sums are written as +0. */
+int bdv_gradcam_map(const float* act, const float* wgt, float* map, int N, int HW, int C, void* stream);
+/* bdv_gradcam_minmax (device): map (B*T, h, w), non-negative -> minmax (2, B): row 0 the minimum, row 1 the maximum over all T*H*W
+ * values of clip b's map after each frame is upsampled to (H, W) as torch.nn.functional.interpolate(mode='bilinear',
+ * align_corners=False) does (UPSTREAM normalises after the interpolation, per sample and not per frame; the temporal interpolation
+ * is the identity).  Indices and fractions as bdv_bg_resize_crop_u8: source index (dst + 0.5) * (in / out) - 0.5 clamped at 0, second
+ * tap clamped to the edge (the coordinate in fp64, its fraction rounded to fp32), columns before rows, no fused multiply-add; two taps a, b with fraction l give a + l * (b - a),
+ * which is exactly a on a constant map.  The upsampled map is not stored.  B <= 65535. */
+int bdv_gradcam_minmax(const float* map, int B, int T, int h, int w, int H, int W, float* minmax, void* stream);
+/* bdv_gradcam_render (device): recomputes the upsampled value u of every output pixel (the same bits as bdv_gradcam_minmax saw) and
+ * writes whichever outputs are given:
+ *   v_out (B, T, H, W) = (u - min_b) / (max_b - min_b + 1e-20f) (UPSTREAM's delta; an all-zero or constant clip gives zeros);
+ *   overlay (B, T, H, W, 3) uint8 = rint(255 * clamp(alpha * lut[idx] + (1 - alpha) * img01, 0, 1)), idx = min(255, floor(256 * v))
+ *     (matplotlib's colormap lookup), lut (256, 3) in [0, 1], img01 = (x * std + mean) / 255 with x = frames_nhwc4 (B*T, H, W, 4), the
+ *     model's normalised input (16-byte aligned); 0 <= alpha <= 1;
+ *   sums (B, 2) = (sum of v, sum of v over the pixels whose centre (x + 0.5, y + 0.5) lies in the union of that frame's boxes:
+ *     x0 <= x + 0.5 < x1 and y0 <= y + 0.5 < y1), accumulated in fp64 in a fixed order (per output row, then one block per clip) and
+ *     rounded once.  Boxes: box_off (B*T + 1) int32 offsets per frame and boxes (nbox, 4) fp32 rows x0 y0 x1 y1 in output-pixel
+ *     coordinates (any finite values: a box may leave the frame or be empty), on the device AND on the host, where the offsets
+ *     (start at 0, do not decrease, end at nbox) and the rows (no NaN) are checked before the launch.  workspace: at least
+ *     bdv_gradcam_workspace_bytes(B, T, H) bytes, 8-byte aligned; needed for sums only. */
+size_t bdv_gradcam_workspace_bytes(int B, int T, int H);
+int bdv_gradcam_render(const float* map, const float* minmax, int B, int T, int h, int w, int H, int W, float* v_out,
+                       const float* frames_nhwc4, const float* lut, float alpha, const float mean[3], const float std[3],
+                       uint8_t* overlay, const int32_t* box_off, const int32_t* box_off_host, const float* boxes,
+                       const float* boxes_host, int nbox, float* sums, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimizer: multi-tensor global-norm clip + SGD(momentum, wd) ---------------------------
  * torch.optim.SGD built at libs/cil/cil.py:467 with the groups of libs/models/cil_heads/tsm.py:273-303
  * and PL gradient_clip_val (cil.py:743).  Tables are device arrays, one entry per tensor. */
