@@ -71,6 +71,7 @@ SIGNATURES = {
     'bdv_conv_weight_planes_bytes': (c_size_t, [POINTER(ConvGeom)]),
     'bdv_conv_split_weights': (c_int, [P, POINTER(ConvGeom), P, P, P]),
     'bdv_conv_debug_force_tile': (c_int, [c_int]),
+    'bdv_conv_debug_row_run': (c_int, [c_int]),
     'bdv_conv_fprop_pl': (c_int, [P, P, P, P, POINTER(ConvGeom), P, POINTER(ConvAffine), P, c_size_t, c_int, P, P, P]),
     'bdv_conv_dgrad_pl': (c_int, [P, P, P, P, P, P, POINTER(ConvGeom), POINTER(BnStatFuse), P, c_size_t, c_int, P]),
     'bdv_conv_wgrad': (c_int, [P, P, P, c_float, POINTER(ConvGeom), P, c_size_t, P]),
@@ -174,7 +175,7 @@ class HipExtensionError(RuntimeError):
 
 
 HASHED_SOURCES = ('conv_mfma.hip', 'bn.hip', 'pool_frontend.hip', 'head_loss.hip', 'repr.hip', 'augment.hip', 'optim.hip', 'jpeg.hip',
-                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'ragged.hip', 'gradcam.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
+                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'ragged.hip', 'gradcam.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'conv_row_run.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
 
 
 def source_hash():

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
+#include "conv_row_run.h"
 
 // ---- in-kernel time stamps (diagnostic builds only: make stamps -> libbdvcil_hip_stamps.so, tools/stamp_tiles.py) --------------
 // With -DBDV_STAMPS lane 0 of every workgroup of the plane kernels writes s_memtime at five points of its life (start, first
@@ -57,6 +58,7 @@ struct Geom {
   int Ktot;  // fprop: R*S*Cin ; dgrad: R*S*Cout ; wgrad: row length of dw = R*S*Cin
   float rcp_HoWo, rcp_Wo;  // fast division helpers (dividends < 2^22)
   int stagger;             // two-stage plane kernels: SIMD partners run a K-step in opposite order (pl_pipeline2)
+  int row_run;             // 3x3 stride-1 sites of the 256x64 tile: one activation image per filter row (pl_pipeline_rr)
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -2000,6 +2002,203 @@ __device__ __forceinline__ void pl_pipeline2(int n, LoadF&& load, StoreF&& store
 // the other's K loop.
 constexpr int pl_waves_per_simd(int waves, int np, bool fits128) { return np == 1 && waves == 8 && fits128 ? 4 : waves == 4 ? 2 : waves / 4; }
 
+// ---- row run: the activation operand of a 3x3 stride-1 site staged once per filter row (conv_row_run.h) ----------------------
+// The K loop runs (chunk, r, s) and the three taps s of a filter row address the same run of BM + 2 flat pixels, shifted by one
+// pixel each: the per-tap loader loads and splits every activation value three times.  Here a GROUP = the (up to) three K-steps of
+// one (chunk, r): its run is loaded and split once into an LDS image of rowrun::lds_row rows per plane, and tap s reads its A
+// fragments from the rows of the output pixels' centres + (s - 1) (dgrad: 1 - s).  Column borders read the image's all-zero
+// separator rows (zeroed once per tile, never written by data); validity in h, frame ends, the temporal shift and rows past M are
+// properties of the run entry and stay in the loader.  K order, the six products per step and their order are those of the per-tap
+// path, and the pieces of a value do not depend on when it is split: every output bit is the same.
+// Where it is compiled in: the 256x64 tile with fp32 tensors, two or three pieces (bf16 or fp16) and no BatchNorm in the loader
+// (all its sites are 3x3; 32 accumulator registers leave room for the image's offsets).  NP = 1 runs two workgroups per CU on
+// 128 registers, where the path's offsets spill (168 / 232 bytes of scratch per lane, fprop / dgrad): it keeps the per-tap loader.
+// LDS: two A images of kRrRows rows and two weight stages per plane,
+//   2 * NP * (kRrRows * 64 + 64 * 64) = 6 * 26624 = 159744 bytes <= 160 KB for NP = 3 with kRrRows = 256 + 96,
+// the last row being a dump for the 62 x 8 threads that own none of the BM + 2 = 4 x 64 + 2 entries in the fifth pass (they load
+// nothing and store there: no divergent branch in a step).  So a tile takes the path iff
+//   rowrun::rows_bound(256, W) = 259 + 256 / W <= 351, i.e. W >= 3;
+// below, the same instantiation runs the per-tap loader (a uniform branch on the geometry).  The 256x128 and wider tiles keep the
+// per-tap loader: two A images and two weight stages of the 256x128 tile need 6 * (22528 + 8192) = 184320 bytes.
+constexpr int kRrRows = 256 + 96;
+constexpr int kRrDataRows = kRrRows - 1;   // the last row takes the stores of the threads that own no entry in the last pass
+template <int BM, int BN, int NP, int ES, bool PRE>
+constexpr bool kRowRunTile = BM == 256 && BN == 64 && NP >= 2 && ES == 4 && !PRE;
+template <int BM, int BN, int NP>
+constexpr int kRowRunSmem = 2 * NP * (kRrRows * 64 + BN * 64);
+static_assert(kRowRunSmem<256, 64, 3> <= 160 * 1024, "row-run images + weight stages of the 256x64 tile do not fit the LDS");
+static_assert(rowrun::fits(256, 3, kRrDataRows) && !rowrun::fits(256, 2, kRrDataRows), "row-run fallback bound: W >= 3 takes the path");
+
+// mma_stage_pl with the A fragments of the lane at per-tile byte offsets fa[i][16-deep step] into an image of PAR bytes per plane
+template <int BM, int BN, int WM, int WN, int NP, typename PT, int PAR>
+__device__ __forceinline__ void mma_stage_rr(const unsigned char* __restrict__ As, const unsigned char* __restrict__ Bs,
+                                             f32x16 (&acc)[BM / WM / 32][BN / WN / 32], const int (&fa)[BM / WM / 32][2],
+                                             const int (&fb)[2]) {
+  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
+  constexpr int PB = BN * 64;
+#pragma unroll
+  for (int s = 0; s < BK / 16; ++s) {
+    bf16x8_t a[NP][TM], b[NP][TN];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i) a[p][i] = *reinterpret_cast<const bf16x8_t*>(As + fa[i][s] + p * PAR);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) b[p][j] = *reinterpret_cast<const bf16x8_t*>(Bs + fb[s] + (p * PB + 32 * WN * j * 64));
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {  // the products and their order of mma_stage_pl
+        if constexpr (NP == 3) {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][i], b[1][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], b[2][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][i], b[0][j], acc[i][j], 0, 0, 0);
+        }
+        if constexpr (NP >= 2) {
+          acc[i][j] = mfma_piece<PT>(a[0][i], b[1][j], acc[i][j]);
+          acc[i][j] = mfma_piece<PT>(a[1][i], b[0][j], acc[i][j]);
+        }
+        acc[i][j] = mfma_piece<PT>(a[0][i], b[0][j], acc[i][j]);
+      }
+  }
+}
+
+// The row-run pipeline: n K-steps, the first at tap s0 of its group.  Weights as in pl_pipeline2 (two stages, two register sets,
+// the loads three steps ahead).  Activations: two images, group G in image G & 1 (counted from the slice's first group), ONE
+// register set whose passes are spread over the group's steps -- step s stores the passes of part s of group G + 1 into the other
+// image (last read before the barrier that ended group G - 1) and reloads them for group G + 2, so every load has three steps to
+// arrive and a step carries a third of the split.  Nothing in a step is conditional: loads past the slice's end are masked out of
+// range by the loaders, the stores that follow them fill an image or a stage nobody reads.  A slice may start and stop at any tap:
+// the prologue does the parts of the steps in front of s0.  One barrier per step; `late` as in pl_pipeline2.
+using RrPart0 = std::integral_constant<int, 0>;
+using RrPart1 = std::integral_constant<int, 1>;
+using RrPart2 = std::integral_constant<int, 2>;
+template <typename LoadA, typename NextA, typename StoreA, typename LoadB, typename StoreB, typename MmaF>
+__device__ __forceinline__ void pl_pipeline_rr(int n, int s0, LoadA&& loadA, NextA&& nextA, StoreA&& storeA, LoadB&& loadB,
+                                               StoreB&& storeB, MmaF&& mma, bool late) {
+  loadA(RrPart0{});
+  loadA(RrPart1{});
+  loadA(RrPart2{});
+  nextA();
+  loadB(PlSet0{});
+  storeA(0, RrPart0{});
+  storeA(0, RrPart1{});
+  storeA(0, RrPart2{});
+  loadA(RrPart0{});
+  loadA(RrPart1{});
+  loadA(RrPart2{});
+  nextA();
+  storeB(0, PlSet0{});
+  loadB(PlSet1{});
+  loadB(PlSet0{});
+  if (s0 >= 1) {
+    storeA(1, RrPart0{});
+    loadA(RrPart0{});
+  }
+  if (s0 >= 2) {
+    storeA(1, RrPart1{});
+    loadA(RrPart1{});
+  }
+  __syncthreads();
+  BDV_STAMP(1);
+  // One step: `SET` = parity of the step (weight stage and register set), `part` = tap of the step, `img` = image of its group.
+  auto step = [&](auto set, auto part, auto is_late, int img) __attribute__((always_inline)) {
+    constexpr int SET = decltype(set)::value, S = decltype(part)::value;
+    using Other = std::integral_constant<int, SET ^ 1>;
+    if constexpr (decltype(is_late)::value) {
+      storeB(SET ^ 1, Other{});
+      loadB(Other{});
+      storeA(img ^ 1, part);
+      loadA(part);
+      mma(img, part, SET);
+    } else {
+      mma(img, part, SET);
+      storeB(SET ^ 1, Other{});
+      loadB(Other{});
+      storeA(img ^ 1, part);
+      loadA(part);
+    }
+    if constexpr (S == 2) nextA();
+    __syncthreads();
+  };
+  int i = 0, abuf = 0, s = s0;
+  // any step by its phase: the slices of K-split remainder tiles start and stop anywhere, and the last steps of every slice
+  auto any_step = [&]() __attribute__((always_inline)) {
+    auto by_order = [&](auto set, auto part) __attribute__((always_inline)) {
+      if (late) step(set, part, std::true_type{}, abuf);
+      else step(set, part, std::false_type{}, abuf);
+    };
+    switch ((i & 1) * 3 + s) {
+      case 0: by_order(PlSet0{}, RrPart0{}); break;
+      case 1: by_order(PlSet0{}, RrPart1{}); break;
+      case 2: by_order(PlSet0{}, RrPart2{}); break;
+      case 3: by_order(PlSet1{}, RrPart0{}); break;
+      case 4: by_order(PlSet1{}, RrPart1{}); break;
+      default: by_order(PlSet1{}, RrPart2{}); break;
+    }
+    i += 1;
+    s += 1;
+    if (s == 3) {
+      s = 0;
+      abuf ^= 1;
+    }
+  };
+  // steady state: two groups = six steps per round, every register set, stage and part a constant of its place in the round (no
+  // condition, no copy between rounds: a step's MFMAs, stores and loads are one basic block, as in pl_pipeline2)
+  auto rounds = [&](auto is_late) __attribute__((always_inline)) {
+    for (; i + 6 <= n; i += 6) {
+      step(PlSet0{}, RrPart0{}, is_late, abuf);
+      step(PlSet1{}, RrPart1{}, is_late, abuf);
+      step(PlSet0{}, RrPart2{}, is_late, abuf);
+      step(PlSet1{}, RrPart0{}, is_late, abuf ^ 1);
+      step(PlSet0{}, RrPart1{}, is_late, abuf ^ 1);
+      step(PlSet1{}, RrPart2{}, is_late, abuf ^ 1);
+    }
+  };
+  // (a slice that starts inside a group runs on any_step alone: short, and no path from that loop into the rounds, whose loads
+  // in flight the compiler then counts exactly -- a merge with the switch's states makes every round begin with vmcnt(0))
+  if (s0 == 0) {
+    if (late) rounds(std::true_type{});
+    else rounds(std::false_type{});
+  }
+  while (i < n) any_step();
+}
+
+// per-thread LDS offsets of the row-run image for the tile that starts at flat pixel m0 (W = image width, rcp_W its reciprocal):
+// st[p] = byte offset of the thread's 8-byte unit of run entry arow + 64 p in plane 0; fa[d][i][s] = the lane's fragment offsets of
+// MFMA tile i at row offset d - 1; the separators of both images and all planes are zeroed (the caller's first barrier orders it).
+template <int BM, int WM, int NP, int NTHR, int AP>
+__device__ __forceinline__ void rr_setup(unsigned char* __restrict__ smem_b, int m0, int W, float rcp_W, int tid, int wm,
+                                         int (&st)[AP], int (&fa)[3][BM / WM / 32][2]) {
+  constexpr int PAR = kRrRows * 64;
+  const int c0 = rowrun::col0(m0, W);
+  const int lane = tid & 63, arow = tid >> 3, kg = tid & 7;
+#pragma unroll
+  for (int p = 0; p < AP; ++p) {
+    const int j = arow + (NTHR / 8) * p;
+    int q, rm;
+    fast_divmod(c0 + j, W, rcp_W, q, rm);   // j + q = rowrun::lds_row(j, c0, W)
+    st[p] = pl_off(j < BM + 2 ? j + q : kRrDataRows, kg >> 1) + 8 * (kg & 1);   // past the run: the dump row
+  }
+#pragma unroll
+  for (int i = 0; i < BM / WM / 32; ++i) {
+    const int j = 32 * WM * i + 32 * wm + (lane & 31) + 1;   // the centre entry of the lane's output pixel
+    int q, rm;
+    fast_divmod(c0 + j, W, rcp_W, q, rm);
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) fa[d][i][s] = pl_off(j + q + d - 1, 2 * s + (lane >> 5));
+  }
+  const int nsep = rowrun::num_sep(BM, c0, W);
+  for (int idx = tid; idx < nsep * 2 * NP * 4; idx += NTHR) {
+    const int k = idx / (2 * NP * 4), rest = idx - k * (2 * NP * 4);
+    *reinterpret_cast<float4*>(smem_b + (rest >> 2) * PAR + rowrun::sep_row(k + 1, c0, W) * 64 + 16 * (rest & 3)) =
+        make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
 // ---- fprop ------------------------------------------------------------------------------------
 // ES: bytes per element of x / y / the residual (4 = fp32, 2 = bf16 storage: NP = 1 only, the loader's conversion is then exact)
 template <int BM, int BN, int WM, int WN, int NBUF, int NP = 3, bool PRE = false, int ES = 4, typename PT = Bf16Pieces>
@@ -2017,7 +2216,9 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
   constexpr int AP = BM * KG / NTHR;    // 16-byte loads of the activation tile per thread and K-step
   constexpr int BPP = (BN * 4 + NTHR - 1) / NTHR;   // 16-byte loads per weight plane per thread and K-step
   constexpr int PA = BM * 64, PB = BN * 64, STAGE = NP * (PA + PB);   // NP planes per operand and stage
-  constexpr int SMEM = NBUF * STAGE >= WM * 32 * BN * 4 ? NBUF * STAGE : WM * 32 * BN * 4;   // K-loop stages, then the epilogue's staging
+  constexpr int SMEM0 = NBUF * STAGE >= WM * 32 * BN * 4 ? NBUF * STAGE : WM * 32 * BN * 4;   // K-loop stages, then the epilogue's staging
+  constexpr bool RR = kRowRunTile<BM, BN, NP, ES, PRE> && NBUF == 2;   // the row-run activation path is compiled in
+  constexpr int SMEM = RR && kRowRunSmem<BM, BN, NP> > SMEM0 ? kRowRunSmem<BM, BN, NP> : SMEM0;
   static_assert(AP >= 1 && SMEM <= 160 * 1024, "tile / epilogue staging do not fit");
   __shared__ __attribute__((aligned(16))) unsigned char smem_b[SMEM];
   float* const smem = reinterpret_cast<float*>(smem_b);
@@ -2137,7 +2338,86 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
   f32x16 acc[TM][TN];
   zero_acc<TM, TN>(acc);
 
-  if constexpr (NBUF == 2) {
+  bool rr_done = false;
+  if constexpr (RR) {
+    // 3-wide filter rows, stride 1, one column of padding (so Wo = W and a tap is a shift by one flat pixel), image fits the LDS
+    if (g.row_run != 0 && g.S == 3 && g.stride == 1 && g.pad_w == 1 && g.Rt == 1 && rowrun::fits(BM, g.W, kRrDataRows)) {
+      constexpr int PAR = kRrRows * 64;            // bytes per plane of an A image
+      constexpr int APR = (BM + 2 + 63) / 64;      // passes of 64 run entries: the last one holds the two extra entries
+      static_assert(NTHR == 512 && KG == 8 && APR == 5, "row run: 64 run entries per pass, parts {0,1} {2,3} {4}");
+      unsigned char* const Bst = smem_b + 2 * NP * PAR;   // the two weight stages behind the two A images
+      int st_r[APR], fa3[3][TM][2];
+      rr_setup<BM, WM, NP, NTHR, APR>(smem_b, mt * BM, g.W, g.rcp_Wo, tid, wm, st_r, fa3);
+      // run entry j = arow + 64 p is the output pixel mt * BM - 1 + j; its input pixel through filter row r, centre tap
+      int e_base[APR], e_t[APR], e_h[APR];
+#pragma unroll
+      for (int p = 0; p < APR; ++p) {
+        const int j = arow + 64 * p, m = mt * BM - 1 + j;
+        const bool ok = j < BM + 2 && m >= 0 && m < g.M;
+        int n, rem, ho, wo;
+        fast_divmod(ok ? m : 0, HoWo, g.rcp_HoWo, n, rem);
+        fast_divmod(rem, g.Wo, g.rcp_Wo, ho, wo);
+        e_t[p] = n % g.T;
+        e_h[p] = ok ? ho - g.pad : -(1 << 20);   // entries outside the tensor's pixels fail every bounds test
+        e_base[p] = ((n * g.H + ho - g.pad) * g.W + wo) * g.Cin * ES + 16 * kg;
+      }
+      const int nchunk = g.Cin / BK;
+      float4 re[APR];
+      int chunk_a = it.kb / RS, r_a = (it.kb - chunk_a * RS) / 3;   // the group the next loadA loads
+      auto loadA = [&](auto part) __attribute__((always_inline)) {
+        constexpr int P0 = 2 * decltype(part)::value, P1 = P0 == 4 ? APR : P0 + 2;
+        const int cls = shift_class(chunk_a * BK + 4 * kg, g.fold);
+        const int koff = (r_a * g.W * g.Cin + chunk_a * BK) * ES + cls * frame_bytes;
+        const bool live = chunk_a < nchunk;   // groups past the last one: nothing is fetched
+#pragma unroll
+        for (int p = P0; p < P1; ++p) {
+          const bool v = live && (unsigned)(e_h[p] + r_a) < (unsigned)g.H && (unsigned)(e_t[p] + cls) < (unsigned)g.T;
+          re[p] = buf_load16(xr, (e_base[p] + koff) | (v ? 0 : kOOB), 0);
+        }
+      };
+      auto nextA = [&]() __attribute__((always_inline)) {
+        r_a += 1;
+        const int w_ = (r_a == g.R) ? 1 : 0;
+        r_a = w_ ? 0 : r_a;
+        chunk_a += w_;
+      };
+      auto storeA = [&](int img, auto part) __attribute__((always_inline)) {
+        constexpr int P0 = 2 * decltype(part)::value, P1 = P0 == 4 ? APR : P0 + 2;
+        unsigned char* const As = smem_b + img * (NP * PAR);
+#pragma unroll
+        for (int p = P0; p < P1; ++p) {
+          pl_split_store_at<NP, PT>(As + st_r[p], PAR, re[p], sc_a);
+        }
+      };
+      auto loadB = [&](auto set) __attribute__((always_inline)) {
+        constexpr int SET = decltype(set)::value;
+        const int off = kt_w < it.ke ? 0 : kOOB;   // steps past the slice: nothing is fetched
+        const int koff_b = kt_w * g.Cout * 64;
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl)
+#pragma unroll
+          for (int q = 0; q < BPP; ++q)
+            rb[SET][pl * BPP + q] = __builtin_amdgcn_raw_buffer_load_b128(wr, (b_base[q] + pl * plane_bytes) | off, off ? 0 : koff_b, 0);
+        kt_w += 1;
+      };
+      auto storeB = [&](int stage, auto set) __attribute__((always_inline)) {
+        constexpr int SET = decltype(set)::value;
+        if (b_active) {
+#pragma unroll
+          for (int pl = 0; pl < NP; ++pl)
+#pragma unroll
+            for (int q = 0; q < BPP; ++q)
+              *reinterpret_cast<u32x4*>(Bst + stage * (NP * PB) + st_b + (pl * PB + (NTHR / 4) * q * 64)) = rb[SET][pl * BPP + q];
+        }
+      };
+      pl_pipeline_rr(it.ke - it.kb, s, loadA, nextA, storeA, loadB, storeB, [&](int img, auto part, int stage) __attribute__((always_inline)) {
+        mma_stage_rr<BM, BN, WM, WN, NP, PT, PAR>(smem_b + img * (NP * PAR), Bst + stage * (NP * PB), acc, fa3[decltype(part)::value], fb);
+      }, g.stagger != 0 && wave >= WM * WN / 2);
+      rr_done = true;
+    }
+  }
+  if (rr_done) {
+  } else if constexpr (NBUF == 2) {
     pl_pipeline2(it.ke - it.kb, load, store, [&](int stage) __attribute__((always_inline)) {
       mma_stage_pl<BM, BN, WM, WN, NP, PT>(smem_b + stage * STAGE, smem_b + stage * STAGE + NP * PA, acc, fa, fb);
     }, g.stagger != 0 && wave >= WM * WN / 2);
@@ -2181,7 +2461,9 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
   constexpr int AP = BM * KG / NTHR;
   constexpr int BPP = (BN * 4 + NTHR - 1) / NTHR;
   constexpr int PA = BM * 64, PB = BN * 64, STAGE = NP * (PA + PB);   // NP planes per operand and stage
-  constexpr int SMEM = NBUF * STAGE >= WM * 32 * BN * 4 ? NBUF * STAGE : WM * 32 * BN * 4;   // K-loop stages, then the epilogue's staging
+  constexpr int SMEM0 = NBUF * STAGE >= WM * 32 * BN * 4 ? NBUF * STAGE : WM * 32 * BN * 4;   // K-loop stages, then the epilogue's staging
+  constexpr bool RR = kRowRunTile<BM, BN, NP, ES, false> && NBUF == 2;   // the row-run activation path is compiled in
+  constexpr int SMEM = RR && kRowRunSmem<BM, BN, NP> > SMEM0 ? kRowRunSmem<BM, BN, NP> : SMEM0;
   static_assert(AP >= 1 && SMEM <= 160 * 1024, "tile / epilogue staging do not fit");
   __shared__ __attribute__((aligned(16))) unsigned char smem_b[SMEM];
   float* const smem = reinterpret_cast<float*>(smem_b);
@@ -2306,7 +2588,93 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
   f32x16 acc[TM][TN];
   zero_acc<TM, TN>(acc);
 
-  if (it.ke > it.kb) {
+  bool rr_done = false;
+  if constexpr (RR) {
+    // stride 1 (one class, Mc = M, Wc = W), 3-wide filter rows with one column of padding (ns = 3, bw = 1, Wo = W): tap `is` reads
+    // the dy pixel one flat pixel to the RIGHT of the centre for is = 0, to the left for is = 2
+    if (g.row_run != 0 && st == 1 && g.S == 3 && g.pad_w == 1 && it.ke > it.kb && rowrun::fits(BM, g.W, kRrDataRows)) {
+      constexpr int PAR = kRrRows * 64;
+      constexpr int APR = (BM + 2 + 63) / 64;
+      static_assert(NTHR == 512 && KG == 8 && APR == 5, "row run: 64 run entries per pass, parts {0,1} {2,3} {4}");
+      unsigned char* const Bst = smem_b + 2 * NP * PAR;
+      int st_r[APR], fa3[3][TM][2];
+      rr_setup<BM, WM, NP, NTHR, APR>(smem_b, mt * BM, g.W, g.rcp_Wo, tid, wm, st_r, fa3);
+      // run entry j = arow + 64 p is the input pixel mt * BM - 1 + j; its dy pixel through filter row 0, centre tap
+      int e_base[APR], e_h[APR];
+#pragma unroll
+      for (int p = 0; p < APR; ++p) {
+        const int j = arow + 64 * p, m = mt * BM - 1 + j;
+        const bool ok = j < BM + 2 && m >= 0 && m < Mc;
+        const int mm = ok ? m : 0;
+        const int n = mm / HcWc;
+        const int rem = mm - n * HcWc;
+        const int hc = rem / Wc, wc = rem - hc * Wc;
+        e_h[p] = ok ? hc + bh : -(1 << 20);
+        e_base[p] = ((n * g.Ho + hc + bh) * g.Wo + wc) * g.Cout * ES + 16 * kg;
+      }
+      float4 re[APR];
+      int chunk_a = it.kb / ntap, r_a = (it.kb - chunk_a * ntap) / 3;   // the group the next loadA loads
+      int kt_b = it.kb;
+      auto loadA = [&](auto part) __attribute__((always_inline)) {
+        constexpr int P0 = 2 * decltype(part)::value, P1 = P0 == 4 ? APR : P0 + 2;
+        const int koff = (chunk_a * BK - r_a * g.Wo * g.Cout) * ES;
+        const bool live = chunk_a < nchunk;
+#pragma unroll
+        for (int p = P0; p < P1; ++p) {
+          const bool v = live && (unsigned)(e_h[p] - r_a) < (unsigned)g.Ho;
+          re[p] = buf_load16(yr, (e_base[p] + koff) | (v ? 0 : kOOB), 0);
+        }
+      };
+      auto nextA = [&]() __attribute__((always_inline)) {
+        r_a += 1;
+        const int w_ = (r_a == nr) ? 1 : 0;
+        r_a = w_ ? 0 : r_a;
+        chunk_a += w_;
+      };
+      auto storeA = [&](int img, auto part) __attribute__((always_inline)) {
+        constexpr int P0 = 2 * decltype(part)::value, P1 = P0 == 4 ? APR : P0 + 2;
+        unsigned char* const As = smem_b + img * (NP * PAR);
+#pragma unroll
+        for (int p = P0; p < P1; ++p) {
+          pl_split_store_at<NP, PT>(As + st_r[p], PAR, re[p], sc_a);
+        }
+      };
+      auto loadB = [&](auto set) __attribute__((always_inline)) {
+        constexpr int SET = decltype(set)::value;
+        const int off = kt_b < it.ke ? 0 : kOOB;
+        const int tap = (r0 + ir * st) * g.S + (s0 + is * st);
+        const int koff_b = (tap * nchunk + chunk) * g.Cin * 64;
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl)
+#pragma unroll
+          for (int q = 0; q < BPP; ++q)
+            rb[SET][pl * BPP + q] = __builtin_amdgcn_raw_buffer_load_b128(wr, (b_base[q] + pl * plane_bytes) | off, off ? 0 : koff_b, 0);
+        kt_b += 1;
+        is += 1;
+        const int w1 = (is == ns) ? 1 : 0;
+        is = w1 ? 0 : is;
+        ir += w1;
+        const int w2 = (ir == nr) ? 1 : 0;
+        ir = w2 ? 0 : ir;
+        chunk += w2;
+      };
+      auto storeB = [&](int stage, auto set) __attribute__((always_inline)) {
+        constexpr int SET = decltype(set)::value;
+        if (b_active) {
+#pragma unroll
+          for (int pl = 0; pl < NP; ++pl)
+#pragma unroll
+            for (int q = 0; q < BPP; ++q)
+              *reinterpret_cast<u32x4*>(Bst + stage * (NP * PB) + st_b + (pl * PB + (NTHR / 4) * q * 64)) = rb[SET][pl * BPP + q];
+        }
+      };
+      pl_pipeline_rr(it.ke - it.kb, is, loadA, nextA, storeA, loadB, storeB, [&](int img, auto part, int stage) __attribute__((always_inline)) {
+        mma_stage_rr<BM, BN, WM, WN, NP, PT, PAR>(smem_b + img * (NP * PAR), Bst + stage * (NP * PB), acc, fa3[2 - decltype(part)::value], fb);
+      }, g.stagger != 0 && wave >= WM * WN / 2);
+      rr_done = true;
+    }
+  }
+  if (it.ke > it.kb && !rr_done) {
     if constexpr (NBUF == 2) {
       pl_pipeline2(it.ke - it.kb, load, store, [&](int stage) __attribute__((always_inline)) {
         mma_stage_pl<BM, BN, WM, WN, NP, PT>(smem_b + stage * STAGE, smem_b + stage * STAGE + NP * PA, acc, fa, fb);
@@ -2674,6 +3042,7 @@ int check_geom(const bdv_conv_geom* g, const char* who) {
 }
 
 // BDVCIL_STAGGER=0 turns the wave stagger of pl_pipeline2 off (A/B runs); read per call, so that tools can flip it between rounds
+int g_pl_row_run = 1;   // bdv_conv_debug_row_run
 static bool pl_stagger_enabled() {
   const char* e = getenv("BDVCIL_STAGGER");
   return e == nullptr || atoi(e) != 0;
@@ -2682,6 +3051,7 @@ static bool pl_stagger_enabled() {
 Geom make_geom(const bdv_conv_geom* g) {
   Geom d;
   d.stagger = pl_stagger_enabled() ? 1 : 0;
+  d.row_run = g_pl_row_run;
   d.N = g->N; d.H = g->H; d.W = g->W; d.Cin = g->Cin; d.Ho = g->Ho; d.Wo = g->Wo; d.Cout = g->Cout;
   d.R = g->R; d.S = g->S; d.stride = g->stride; d.pad = g->pad; d.pad_w = g->pad_w < 0 ? g->pad : g->pad_w;
   d.T = (g->fold > 0 || g->Rt > 1) ? g->T : 1;
@@ -3442,6 +3812,12 @@ extern "C" int bdv_debug_set_stamps(void* buf, int cap_workgroups) {
 extern "C" int bdv_conv_debug_force_tile(int cfg) {
   BDV_REQUIRE(cfg >= -1 && cfg <= kNumPlCfg, "bdv_conv_debug_force_tile: cfg %d (-1 automatic, 0 = 128x256, 1 = 256x128, 2 = 256x256, 3 = 256x64, 4 = 64x128 (dgrad), 5 = 128x128 (four waves), 6 = none)", cfg);
   g_pl_tile_forced = cfg;
+  return BDV_OK;
+}
+
+extern "C" int bdv_conv_debug_row_run(int on) {
+  BDV_REQUIRE(on == 0 || on == 1, "bdv_conv_debug_row_run: on = %d (1 = one activation image per filter row, 0 = the per-tap loader)", on);
+  g_pl_row_run = on;
   return BDV_OK;
 }
 

@@ -175,6 +175,11 @@ int bdv_conv_split_weights(const float* w, const bdv_conv_geom* g, void* planes_
  * (0 = 128x256, 1 = 256x128, 2 = 256x256, 3 = 256x64, 4 = 64x128 (dgrad, stride 1), 5 = 128x128 with four waves and two
  * workgroups per CU, where the tile divides the column count; 6 = none of them; -1 = the planner's rules). */
 int bdv_conv_debug_force_tile(int cfg);
+/* Test / A-B hook, process-wide and not thread-safe: on = 1 (the default) lets the 3x3 stride-1 sites of the 256x64 tile (fp32
+ * tensors, two or three pieces) stage each activation run once per filter row and read the three taps from that one LDS image;
+ * on = 0 routes the same kernel instantiation through the per-tap loader.  Both give the same output bits
+ * (tests/test_conv_row_run_gpu.py). */
+int bdv_conv_debug_row_run(int on);
 /* pre_scale / pre_shift (optional, [Cin] each): x is then the RAW output of the producing conv and the producer's train-mode
  * BatchNorm + ReLU, a = max(x * pre_scale[ci] + pre_shift[ci], 0), is applied in the loader (the same fused multiply-add as
  * bdv_bn_apply, bit-identical activations; halo / ragged lanes stay zero): the apply pass between the two convs, the activation
