@@ -3165,22 +3165,39 @@ FdPlan plan_dgrad(const Geom& g, size_t ws_bytes, bool x3 = false) {
 }
 
 // ---- planner of the "P" kernels (8 waves, ONE workgroup per CU: a round is 256 blocks) ----------------------------------
-// Tile configurations: 0 = 128 x 256 (two LDS stages), 1 = 256 x 128 (two stages), 2 = 256 x 256 (one stage, opt-in),
-// 3 = 256 x 64 (two stages; the 64-channel layers).
-struct PlCfg {
-  int BM, BN, nbuf;
-  double iter_us;  // one 32-deep K-step of a block, measured per-CU rate (tools/ubench/gemm_x3p.hip: ~200 / ~230 TFLOP/s chip-wide)
+// The tiles of conv_fprop_pl_kernel / conv_dgrad_pl_kernel, by tile configuration (`cfg`).  This table is the one place a tile is
+// written down: the planner, the kernel names, the launches and bdv_conv_debug_force_tile's message all read it, and a kernel is
+// instantiated for exactly the (tile, direction) pairs it allows.
+struct PlTile {
+  int BM, BN, WM, WN, NBUF;   // tile, waves along M and N (64 * WM * WN threads), LDS stages
+  double iter_us;   // one 32-deep K-step of a block, measured per-CU rate (tools/ubench/gemm_x3p.hip: ~200 / ~230 TFLOP/s chip-wide)
+  int round;        // workgroups resident on the chip at once
+  bool fprop;       // false: data gradient only, ...
+  bool stride1;     // ... true: of stride-1 sites only
 };
-constexpr int kNumPlCfg = 6;
-// 4 = 64 x 128, four waves, FOUR workgroups per CU: for dgrads whose epilogue streams as many bytes as their K loop takes MFMA time
-// (a block's conv1), so that one tile's epilogue runs beside other tiles' K loops; dgrad only
-// 5 = 128 x 128, four waves, TWO workgroups per CU, one LDS stage (48 KB): the tile of the round-1 conv_*_x3 kernels on the plane
-// kernels' conflict-free LDS image (64-byte rows, 16-byte chunk XOR, immediate-offset fragment reads) and their weight planes
-constexpr PlCfg kPlCfg[kNumPlCfg] = {{128, 256, 2, 2.7}, {256, 128, 2, 2.7}, {256, 256, 1, 4.7}, {256, 64, 2, 1.9}, {64, 128, 1, 0.7},
-                                     {128, 128, 1, 1.6}};
-constexpr int pl_cfg_wm(int cfg) { return cfg == 0 || cfg == 2 || cfg == 4 || cfg == 5 ? 2 : 4; }
-constexpr int pl_cfg_wn(int cfg) { return cfg == 4 || cfg == 5 ? 2 : 8 / pl_cfg_wm(cfg); }
-constexpr int pl_cfg_round(int cfg) { return cfg == 5 ? 512 : 256; }   // workgroups resident on the chip at once
+constexpr PlTile kPlTiles[] = {
+    {128, 256, 2, 4, 2, 2.7, 256, true, false},
+    {256, 128, 4, 2, 2, 2.7, 256, true, false},
+    {256, 256, 2, 4, 1, 4.7, 256, true, false},   // one stage, opt-in
+    {256, 64, 4, 2, 2, 1.9, 256, true, false},    // the 64-channel layers
+    // four waves, FOUR workgroups per CU: for dgrads whose epilogue streams as many bytes as their K loop takes MFMA time (a block's
+    // conv1), so that one tile's epilogue runs beside other tiles' K loops; thousands of tiles, no remainder worth a K split
+    {64, 128, 2, 2, 1, 0.7, 256, false, true},
+    // four waves, TWO workgroups per CU, one LDS stage (48 KB): the tile of the round-1 conv_*_x3 kernels on the plane kernels'
+    // conflict-free LDS image (64-byte rows, 16-byte chunk XOR, immediate-offset fragment reads) and their weight planes
+    {128, 128, 2, 2, 1, 1.6, 512, true, false},
+};
+constexpr int kNumPlTiles = sizeof(kPlTiles) / sizeof(kPlTiles[0]);
+
+// f(std::integral_constant<int, i>{}) for the runtime index i in [0, N): the launches turn a table row into template arguments with it
+template <class F, int... I>
+void static_index(int i, F&& f, std::integer_sequence<int, I...>) {
+  ((i == I ? (void)f(std::integral_constant<int, I>{}) : (void)0), ...);
+}
+template <int N, class F>
+void static_index(int i, F&& f) {
+  static_index(i, f, std::make_integer_sequence<int, N>{});
+}
 
 struct PlPlan {
   int cfg;  // -1: shape not covered by the P kernels
@@ -3247,8 +3264,16 @@ constexpr int kArithF16x2 = BDV_ARITH_F16X2;   // the `pieces` / `arith` code of
 //     against 589.9 / 590.9 / 588.1 without (profiles/r02_ab_streams.txt) -- kept as a tested tile, not chosen by default.
 // Returns the tile configuration, or -1 for the kernels that take fp32 weights.  BDVCIL_PL_TILE / bdv_conv_debug_force_tile
 // override the rules wherever the forced tile divides the column count.
+// may the debug override force tile `t` on this call: the tile exists, has the direction and divides the column count
+bool pl_tile_forcible(int t, bool dgrad, int ncols, int stride) {
+  if (t < 0 || t >= kNumPlTiles) return false;
+  const PlTile& k = kPlTiles[t];
+  return ncols % k.BN == 0 && (k.fprop || dgrad) && (!k.stride1 || stride == 1);
+}
+
 int pl_pick(bool dgrad, int ncols, int nk, int taps, int stride, int pieces = 3, bool shifted = false) {
   const int forced = pl_tile_override();
+  if (pl_tile_forcible(forced, dgrad, ncols, stride)) return forced;
   if (pieces == 1) {  // the single-product arithmetic only exists in the plane kernels
     // A sixth of the MFMA work per K-step: the loop waits for its loads, not for the matrix pipe.  For the data gradient (whose
     // epilogue streams the residual, the mask and the statistics operands on top) many small workgroups hide that better than one
@@ -3256,7 +3281,6 @@ int pl_pick(bool dgrad, int ncols, int nk, int taps, int stride, int pieces = 3,
     // bf16 storage: dgrad 18.9 -> 15.6 ms, 1100 -> 1158 clips/s; fp32 tensors: level (gpurun_out/np1_*.log).  The same tile for
     // fprop (8.8 against 8.0 ms) and 128x128 weight-gradient tiles (7.4 against 7.7 ms) were measured and left out.
     const bool small_ok = dgrad && stride == 1;
-    if (forced >= 0 && forced < kNumPlCfg && ncols % kPlCfg[forced].BN == 0 && (forced != 4 || small_ok)) return forced;
     static const bool np1_small = getenv("BDVCIL_NP1_SMALL_TILES") == nullptr || atoi(getenv("BDVCIL_NP1_SMALL_TILES")) != 0;
     if (np1_small && small_ok && ncols % 128 == 0) return 4;
     return ncols % 256 == 0 ? 0 : ncols % 128 == 0 ? 1 : ncols % 64 == 0 ? 3 : -1;
@@ -3264,19 +3288,16 @@ int pl_pick(bool dgrad, int ncols, int nk, int taps, int stride, int pieces = 3,
   if (pieces == 2) {
     // Two pieces per operand, three products: only the plane kernels have the form, so the sites the three-piece rules leave to the
     // conv_*_x3 kernels take the 128x128 four-wave tile (two workgroups per CU, like them) here.
-    if (forced >= 0 && forced < kNumPlCfg && ncols % kPlCfg[forced].BN == 0 && (forced != 4 || (dgrad && stride == 1))) return forced;
     const int c = pl_pick(dgrad, ncols, nk, taps, stride, 3, shifted);
     return c >= 0 ? c : ncols % 128 == 0 ? 5 : ncols % 64 == 0 ? 3 : -1;
   }
   if (pieces == kArithF16x2) {
     // Two fp16 pieces: the tiles of the three-piece rules, and the 128x128 four-wave tile where those leave a site to the conv_*_x3
     // kernels.  What they leave to the other families (64 columns behind a 1x1 filter) keeps three bf16 pieces.
-    if (forced >= 0 && forced < kNumPlCfg && ncols % kPlCfg[forced].BN == 0 && (forced != 4 || (dgrad && stride == 1))) return forced;
     const int c = pl_pick(dgrad, ncols, nk, taps, stride, 3, shifted);
     return c >= 0 ? c : ncols % 128 == 0 ? 5 : -1;
   }
-  if (forced == kNumPlCfg) return -1;  // "none": the kernels of the other family everywhere
-  if (forced >= 0 && ncols % kPlCfg[forced].BN == 0 && (forced != 4 || (dgrad && stride == 1))) return forced;   // (three pieces: the 64x128 tile exists for dgrad only)
+  if (forced == kNumPlTiles) return -1;  // "none": the kernels of the other family everywhere (three pieces only: the others have none)
   if (ncols % 64 != 0) return -1;
   if (ncols % 128 != 0) return taps > 1 ? 3 : -1;
   if (!dgrad) {
@@ -3284,8 +3305,6 @@ int pl_pick(bool dgrad, int ncols, int nk, int taps, int stride, int pieces = 3,
     if (nk >= 16 || nk <= 2) return 0;
     return -1;
   }
-  // (round 2 also had modes 2 / 3 -- the conv1 dgrads of layers 1-2 / layer 1 only: level within the run-to-run spread,
-  // profiles/r02_ab_streams.txt; removed)
   static const bool small_tiles = getenv("BDVCIL_DGRAD_64X128") != nullptr && atoi(getenv("BDVCIL_DGRAD_64X128")) == 1;
   if (ncols % 256 != 0) return taps > 1 && stride == 1 ? 1 : (small_tiles && taps == 1 && stride == 1 && nk >= 16 ? 4 : -1);
   if (stride == 2 && taps > 1) return 0;
@@ -3303,13 +3322,13 @@ PlPlan plan_pl(int cfg, int M, int ncols, int nk, size_t ws_bytes, bool ksplit_o
   p.cfg = cfg;
   p.est_us = 0.0;
   if (cfg < 0) return p;
-  const PlCfg& k = kPlCfg[cfg];
+  const PlTile& k = kPlTiles[cfg];
   p.MT = (M + k.BM - 1) / k.BM;
   p.NT = ncols / k.BN;
   p.nk = nk;
   p.seg_bytes = (size_t)k.BM * k.BN * sizeof(float);
   if (ksplit_ok && cfg != 4) {   // (the 64 x 128 tile runs four workgroups per CU: thousands of tiles, no remainder worth splitting)
-    p.wk = plan_work_pl(p.MT * p.NT, nk, k.iter_us, p.seg_bytes, ws_bytes, &p.est_us, pl_cfg_round(cfg));
+    p.wk = plan_work_pl(p.MT * p.NT, nk, k.iter_us, p.seg_bytes, ws_bytes, &p.est_us, k.round);
   } else {
     p.wk.dp_tiles = p.MT * p.NT;
     p.wk.rem_tiles = 0;
@@ -3386,9 +3405,9 @@ WgradPlan plan_wgrad(const bdv_conv_geom* g) {
   return p;
 }
 
-// Tile forms of conv_wgrad_pl_kernel: 0 = 128/256 x 128/256 (8 waves); the 64-channel layers: 1 = 64 x 192 (a filter row of
-// three taps x 64 input channels), 2 = 64 x 64 (1x1), 3 = 256 x 64 (1x1), 4 = 64 x 256 (1x1), 5 = the stem (Cin = 4 on NHWC4:
-// 64 x 256 = 64 taps of 4 channels, R*S <= 64, the columns past the last tap stay empty); -1 = not covered.
+// Tile forms of conv_wgrad_pl_kernel (their tiles: kWgradTiles below): 0 = multiples of 128 channels on both sides (8 waves); the
+// 64-channel layers: 1 = a filter row of three taps x 64 input channels, 2 = 64 -> 64 1x1, 3 = 64 -> 256 1x1, 4 = 256 -> 64 1x1,
+// 5 = the stem (Cin = 4 on NHWC4: 64 taps of 4 channels, R*S <= 64, the columns past the last tap stay empty); -1 = not covered.
 // BDVCIL_WGRAD_2STAGE=0: the one-stage weight-gradient loop for every tile (read per call: A/B runs flip it)
 bool wgrad_two_stage() {
   const char* e = getenv("BDVCIL_WGRAD_2STAGE");
@@ -3410,17 +3429,31 @@ int pl_wgrad_form(const bdv_conv_geom* g) {
   return -1;
 }
 
-// wgrad of the P family: one workgroup per CU, tiles of 128 / 256 output channels x 128 / 256 input channels of a tap
+// The tiles of conv_wgrad_pl_kernel: output channels x input channels of a tap (MTAP: x the taps of a filter row / of the stem).
+// Rows 0..3 are form 0 (8 waves, one workgroup per CU), by whether 256 divides Cout and Cin; rows 4..8 are forms 1..5.
+struct WgradTile {
+  int BM, BN, WM, WN;
+  bool MTAP;
+  bool two_stage;   // has the two-stage loop (16 pixels per stage, KW = 16) beside the one-stage one (KW = 32)
+};
+constexpr WgradTile kWgradTiles[] = {
+    {128, 128, 2, 4, false, false}, {128, 256, 2, 4, false, true}, {256, 128, 2, 4, false, true},
+    {256, 256, 2, 4, false, false},   // two register sets would spill here (128 accumulators)
+    {64, 192, 2, 2, true, false},   {64, 64, 2, 2, false, false},  {256, 64, 4, 1, false, false},
+    {64, 256, 1, 4, false, false},  {64, 256, 1, 4, true, false},
+};
+constexpr int kNumWgradTiles = sizeof(kWgradTiles) / sizeof(kWgradTiles[0]);
+
 struct WgradPlPlan {
-  int form, BM, BN, MTw, NTw, splits, kt_per_split;
+  int form, tile, BM, BN, MTw, NTw, splits, kt_per_split;   // tile: row of kWgradTiles
 };
 
 WgradPlPlan plan_wgrad_pl(const bdv_conv_geom* g) {
   WgradPlPlan p;
   p.form = pl_wgrad_form(g);
-  static const int kBM[6] = {0, 64, 64, 256, 64, 64}, kBN[6] = {0, 192, 64, 64, 256, 256};
-  p.BM = p.form == 0 ? (g->Cout % 256 == 0 ? 256 : 128) : kBM[p.form];
-  p.BN = p.form == 0 ? (g->Cin % 256 == 0 ? 256 : 128) : kBN[p.form];
+  p.tile = p.form == 0 ? (g->Cout % 256 == 0 ? 2 : 0) + (g->Cin % 256 == 0 ? 1 : 0) : 3 + p.form;
+  p.BM = kWgradTiles[p.tile].BM;
+  p.BN = kWgradTiles[p.tile].BN;
   p.MTw = g->Cout / p.BM;
   p.NTw = ((g->Rt > 1 ? g->Rt : 1) * g->R * g->S * g->Cin + p.BN - 1) / p.BN;
   const int64_t M = (int64_t)g->N * g->Ho * g->Wo;
@@ -3462,7 +3495,7 @@ enum { kFprop = 0, kDgrad = 1, kWgrad = 2 };
 
 struct ConvPlan {
   int family = -1;     // BDV_CONV_* of include/bdvcil_hip.h; -1: refused, the reason is in bdv_last_error()
-  int cfg = -1;        // BDV_CONV_PL: tile configuration (kPlCfg)
+  int cfg = -1;        // BDV_CONV_PL: tile configuration (kPlTiles)
   bool wide = false;   // the 4-wave fp32-MFMA / bf16-piece / stem kernels: 128 x 128 tile (else 128 x 64)
   bool reads_planes = false;
   bool pre_ok = false; // the producer's BatchNorm can be applied in the loader (pre = true on a shifted site still gives its tile)
@@ -3519,8 +3552,9 @@ ConvPlan plan_conv(const bdv_conv_geom* g, int kind, int arith, bool pre) {
       p.cfg = cfg;
       p.stat_rows = (kind == kDgrad ? g->stride * g->stride : 1) * plan_pl(cfg, m.M, m.ncols, m.nk, 0, false).MT;
       p.pre_ok = false;
+      const PlTile& k = kPlTiles[cfg];
       snprintf(p.kernel, sizeof(p.kernel), "conv_%s_pl_kernel<%d, %d, %d, %d, %d, 2, %s4, F16Pieces>", kind == kDgrad ? "dgrad" : "fprop",
-               kPlCfg[cfg].BM, kPlCfg[cfg].BN, pl_cfg_wm(cfg), pl_cfg_wn(cfg), kPlCfg[cfg].nbuf, kind == kDgrad ? "" : "false, ");
+               k.BM, k.BN, k.WM, k.WN, k.NBUF, kind == kDgrad ? "" : "false, ");
     }
     p.f16 = true;
     return p;
@@ -3575,8 +3609,9 @@ ConvPlan plan_conv(const bdv_conv_geom* g, int kind, int arith, bool pre) {
     p.cfg = cfg;
     p.reads_planes = true;
     p.stat_rows = classes * plan_pl(cfg, m.M, m.ncols, m.nk, 0, false).MT;
-    snprintf(p.kernel, sizeof(p.kernel), "conv_%s_pl_kernel<%d, %d, %d, %d, %d, %d%s>", dir, kPlCfg[cfg].BM, kPlCfg[cfg].BN, pl_cfg_wm(cfg),
-             pl_cfg_wn(cfg), kPlCfg[cfg].nbuf, arith, pre ? ", true" : "");
+    const PlTile& k = kPlTiles[cfg];
+    snprintf(p.kernel, sizeof(p.kernel), "conv_%s_pl_kernel<%d, %d, %d, %d, %d, %d%s>", dir, k.BM, k.BN, k.WM, k.WN, k.NBUF, arith,
+             pre ? ", true" : "");
     return p;
   }
   p.wide = ncols % 128 == 0;
@@ -3655,144 +3690,6 @@ extern "C" size_t bdv_conv_workspace_bytes(const bdv_conv_geom* gg, int kind) {
   return need > 16 ? need : 16;
 }
 
-namespace {
-int conv_fprop_impl(const float* x, const float* w, float* y, const bdv_conv_geom* gg, float* bn_partial,
-                    const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, void* stream, int arith,
-                    const void* planes_f = nullptr) {
-  const ConvPlan cp = plan_conv(gg, kFprop, arith, false);
-  if (cp.family < 0) return BDV_EINVAL;
-  BDV_REQUIRE(!cp.reads_planes || planes_f != nullptr, "bdv_conv_fprop: this site runs on the weight planes (bdv_conv_plan_query: reads_planes), planes_fprop is NULL");
-  BDV_REQUIRE(x && w && y, "bdv_conv_fprop: null pointer");
-  FpropEpi epi = {bn_partial, 0, nullptr, nullptr, nullptr, 0};
-  if (affine != nullptr) {
-    BDV_REQUIRE(bn_partial == nullptr, "bdv_conv_fprop: batch statistics and the folded eval-mode BatchNorm exclude each other");
-    BDV_REQUIRE(affine->scale && affine->shift, "bdv_conv_fprop: null pointer in bdv_conv_affine");
-    BDV_REQUIRE(bdv_aligned16(affine->scale) && bdv_aligned16(affine->shift) && bdv_aligned16(affine->residual),
-                "bdv_conv_fprop: bdv_conv_affine pointers must be 16-byte aligned");
-    epi.scale = affine->scale;
-    epi.shift = affine->shift;
-    epi.res = affine->residual;
-    epi.relu = affine->relu;
-  }
-  BDV_REQUIRE(bdv_aligned16(x) && bdv_aligned16(w) && bdv_aligned16(y) && bdv_aligned16(workspace),
-              "bdv_conv_fprop: pointers must be 16-byte aligned");
-  Geom g = make_geom(gg);
-  g.M = g.N * g.Ho * g.Wo;
-  g.Ktot = g.Rt * g.R * g.S * g.Cin;
-  hipStream_t s = (hipStream_t)stream;
-  const FdPlan p = plan_fprop(g, workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, cp.family == BDV_CONV_X3);
-  BDV_REQUIRE(p.MT == cp.stat_rows && p.wide == cp.wide, "bdv_conv_fprop: row tiles %d != planned %d", p.MT, cp.stat_rows);
-  const int blocks = p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split;
-  epi.MT = p.MT;
-  float* slab = (float*)workspace;
-  if (debug_plan())
-    fprintf(stderr, "[bdv plan] fprop %dx%d Cin %d Cout %d k%d s%d: tiles %d nk %d -> dp %d rem %d split %d\n", g.H, g.W,
-            g.Cin, g.Cout, g.R, g.stride, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split);
-  if (cp.family == BDV_CONV_C4_X3) {
-    if (p.wide)
-      hipLaunchKernelGGL((conv_fprop_c4_x3_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, epi);
-    else
-      hipLaunchKernelGGL((conv_fprop_c4_x3_kernel<128, 64, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, epi);
-  } else if (cp.family == BDV_CONV_C4) {
-    if (p.wide)
-      hipLaunchKernelGGL((conv_fprop_c4_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, epi);
-    else
-      hipLaunchKernelGGL((conv_fprop_c4_kernel<128, 64, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, epi);
-  } else if (cp.family == BDV_CONV_X3) {
-    hipLaunchKernelGGL((conv_fprop_x3_kernel<128, 128, 2, 2, true>), dim3(blocks), dim3(256), 0, s, x, (const float*)planes_f, y, g, p.NT, p.wk, slab, epi);
-  } else if (p.wide) {
-    hipLaunchKernelGGL((conv_fprop_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, p.wk, slab, epi);
-  } else {
-    hipLaunchKernelGGL((conv_fprop_kernel<128, 64, 2, 2>), dim3(blocks), dim3(256), 0, s, x, w, y, g, p.NT, p.wk, slab, epi);
-  }
-  BDV_LAUNCH_CHECK("bdv_conv_fprop");
-  if (p.wk.split > 1) {
-    const dim3 fg(p.wk.rem_tiles);
-    if (p.wide)
-      hipLaunchKernelGGL((conv_fprop_fixup_kernel<128, 128, 2, 2>), fg, dim3(256), 0, s, (const float*)slab, y, g, p.NT, p.wk, epi);
-    else
-      hipLaunchKernelGGL((conv_fprop_fixup_kernel<128, 64, 2, 2>), fg, dim3(256), 0, s, (const float*)slab, y, g, p.NT, p.wk, epi);
-    BDV_LAUNCH_CHECK("bdv_conv_fprop(fixup)");
-  }
-  return BDV_OK;
-}
-}  // namespace
-
-extern "C" int bdv_conv_fprop(const float* x, const float* w, float* y, const bdv_conv_geom* gg, float* bn_partial,
-                              const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, void* stream) {
-  return conv_fprop_impl(x, w, y, gg, bn_partial, affine, workspace, workspace_bytes, stream, 0);
-}
-
-namespace {
-int conv_dgrad_impl(const float* dy, const float* w, float* dx, const float* add_src,
-                    const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat, void* workspace,
-                    size_t workspace_bytes, void* stream, int arith, const void* planes_d = nullptr) {
-  const ConvPlan cp = plan_conv(gg, kDgrad, arith, false);
-  if (cp.family < 0) return BDV_EINVAL;
-  BDV_REQUIRE(!cp.reads_planes || planes_d != nullptr, "bdv_conv_dgrad: this site runs on the weight planes (bdv_conv_plan_query: reads_planes), planes_dgrad is NULL");
-  BnStat stat = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-  if (bn_stat != nullptr) {
-    BDV_REQUIRE(gg->stride == 1 || (gg->R >= gg->stride && gg->S >= gg->stride),
-                "bdv_conv_dgrad: fused BatchNorm statistics with stride 2 need a filter that reaches every input pixel (R, S >= 2)");
-    BDV_REQUIRE(bn_stat->y && bn_stat->mean && bn_stat->invstd && bn_stat->partial, "bdv_conv_dgrad: null pointer in bdv_bn_stat_fuse");
-    BDV_REQUIRE(bdv_aligned16(bn_stat->y) && bdv_aligned16(bn_stat->mean) && bdv_aligned16(bn_stat->invstd) &&
-                    bdv_aligned16(bn_stat->partial), "bdv_conv_dgrad: bdv_bn_stat_fuse pointers must be 16-byte aligned");
-    BDV_REQUIRE(bn_stat->relu_mask == nullptr || gg->Cin % 32 == 0, "bdv_conv_dgrad: a ReLU mask needs Cin %% 32 == 0");
-    stat.y = bn_stat->y;
-    stat.mask = bn_stat->relu_mask;
-    stat.mean = bn_stat->mean;
-    stat.invstd = bn_stat->invstd;
-    stat.partial = bn_stat->partial;
-    stat.rscale = bn_stat->relu_mask == nullptr ? bn_stat->relu_scale : nullptr;
-    stat.rshift = bn_stat->relu_shift;
-    stat.MT = cp.stat_rows;
-    BDV_REQUIRE(stat.rscale == nullptr || cp.family != BDV_CONV_F32 || !cp.wide,
-                "bdv_conv_dgrad: a ReLU sign derived from y (relu_scale) is not compiled into the 128-wide fp32-MFMA kernel");
-    if (gg->stride != 1)  // parity classes of odd-sized inputs have fewer row tiles than the largest: their rows stay zero
-      (void)hipMemsetAsync(bn_stat->partial, 0, (size_t)2 * stat.MT * gg->Cin * sizeof(float), (hipStream_t)stream);
-  }
-  BDV_REQUIRE(dy && w && dx, "bdv_conv_dgrad: null pointer");
-  BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(w) && bdv_aligned16(dx) && bdv_aligned16(workspace),
-              "bdv_conv_dgrad: pointers must be 16-byte aligned");
-  BDV_REQUIRE(add_src != nullptr || add_mask_src == nullptr, "bdv_conv_dgrad: add_mask_src without add_src");
-  Geom g = make_geom(gg);
-  g.M = g.N * g.H * g.W;
-  g.Ktot = g.R * g.S * g.Cout;
-  hipStream_t s = (hipStream_t)stream;
-  const int st = g.stride;
-  const bool x3 = cp.family == BDV_CONV_X3;
-  const FdPlan p = plan_dgrad(g, workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, x3);
-  BDV_REQUIRE(st * st * p.MT == cp.stat_rows && p.wide == cp.wide, "bdv_conv_dgrad: row tiles %d != planned %d", st * st * p.MT, cp.stat_rows);
-  const dim3 grid(p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split, st * st);
-  float* slab = (float*)workspace;
-  if (debug_plan())
-    fprintf(stderr, "[bdv plan] dgrad %dx%d Cin %d Cout %d k%d s%d: tiles %d nk %d -> dp %d rem %d split %d\n", g.H, g.W,
-            g.Cin, g.Cout, g.R, g.stride, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split);
-  if (x3)
-    hipLaunchKernelGGL((conv_dgrad_x3_kernel<128, 128, 2, 2, true>), grid, dim3(256), 0, s, dy, (const float*)planes_d, dx, add_src, add_mask_src, g, p.NT, p.wk, slab, stat);
-  else if (p.wide)
-    hipLaunchKernelGGL((conv_dgrad_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, dy, w, dx, add_src, add_mask_src, g, p.NT, p.wk, slab, stat);
-  else
-    hipLaunchKernelGGL((conv_dgrad_kernel<128, 64, 2, 2>), grid, dim3(256), 0, s, dy, w, dx, add_src, add_mask_src, g, p.NT, p.wk, slab, stat);
-  BDV_LAUNCH_CHECK("bdv_conv_dgrad");
-  if (p.wk.split > 1) {
-    const dim3 fg(p.wk.rem_tiles);
-    if (p.wide)
-      hipLaunchKernelGGL((conv_dgrad_fixup_kernel<128, 128, 2, 2>), fg, dim3(256), 0, s, (const float*)slab, dx, add_src, add_mask_src, g, p.NT, p.wk, stat);
-    else
-      hipLaunchKernelGGL((conv_dgrad_fixup_kernel<128, 64, 2, 2>), fg, dim3(256), 0, s, (const float*)slab, dx, add_src, add_mask_src, g, p.NT, p.wk, stat);
-    BDV_LAUNCH_CHECK("bdv_conv_dgrad(fixup)");
-  }
-  return BDV_OK;
-}
-}  // namespace
-
-extern "C" int bdv_conv_dgrad(const float* dy, const float* w, float* dx, const float* add_src,
-                              const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-  return conv_dgrad_impl(dy, w, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, stream, 0);
-}
-
 // ---- weights as bf16 planes + the P kernels --------------------------------------------------------------------------
 extern "C" size_t bdv_conv_weight_planes_bytes(const bdv_conv_geom* gg) {
   if (check_geom(gg, "bdv_conv_weight_planes_bytes")) return 0;
@@ -3810,7 +3707,15 @@ extern "C" int bdv_debug_set_stamps(void* buf, int cap_workgroups) {
 #endif
 
 extern "C" int bdv_conv_debug_force_tile(int cfg) {
-  BDV_REQUIRE(cfg >= -1 && cfg <= kNumPlCfg, "bdv_conv_debug_force_tile: cfg %d (-1 automatic, 0 = 128x256, 1 = 256x128, 2 = 256x256, 3 = 256x64, 4 = 64x128 (dgrad), 5 = 128x128 (four waves), 6 = none)", cfg);
+  if (cfg < -1 || cfg > kNumPlTiles) {
+    char tiles[256] = "";
+    for (int t = 0, n = 0; t < kNumPlTiles && n < (int)sizeof(tiles); ++t) {
+      const PlTile& k = kPlTiles[t];
+      n += snprintf(tiles + n, sizeof(tiles) - n, "%d = %dx%d%s, ", t, k.BM, k.BN, !k.fprop ? " (dgrad)" : k.WM * k.WN == 4 ? " (four waves)" : "");
+    }
+    bdv_set_error("bdv_conv_debug_force_tile: cfg %d (-1 automatic, %s%d = none)", cfg, tiles, kNumPlTiles);
+    return BDV_EINVAL;
+  }
   g_pl_tile_forced = cfg;
   return BDV_OK;
 }
@@ -3833,372 +3738,426 @@ extern "C" int bdv_conv_split_weights(const float* w, const bdv_conv_geom* gg, v
   return BDV_OK;
 }
 
+// ---- the launches: one function per direction ---------------------------------------------------------------------------------
+// Every conv entry point is a thin wrapper over conv_fprop_launch / conv_dgrad_launch / conv_wgrad_partial_launch.  Each of them
+// plans once (plan_conv), makes every check of its arguments before its first HIP call, and launches what the plan says; `who` is
+// the entry point that was called, for the messages.
 namespace {
+
+// The arithmetic variants of the plane kernels: bf16 pieces per operand (NP), bytes of a stored activation (ES; 2 = bf16 storage),
+// the two-fp16-piece type, and (fprop only) the producer's BatchNorm in the loader.  A kernel is instantiated per (tile, variant).
+struct PlArith {
+  int NP, ES;
+  bool f16, pre;
+};
+constexpr PlArith kPlAriths[] = {{1, 4, false, false}, {2, 4, false, false}, {3, 4, false, false},
+                                 {3, 4, false, true}, {1, 2, false, false}, {2, 4, true, false}};
+constexpr int kNumPlAriths = sizeof(kPlAriths) / sizeof(kPlAriths[0]);
+template <int A>
+using PlPieces = std::conditional_t<kPlAriths[A].f16, F16Pieces, Bf16Pieces>;
+// row of kPlAriths of a call of the plane kernels; `pieces` 1..3 (a kArithF16x2 call the plan left to bf16 pieces: 3)
+int pl_arith(const ConvPlan& cp, const bdv_conv_geom* gg, int pieces, bool pre) {
+  return cp.f16 ? 5 : gg->act_dtype == BDV_ACT_BF16 ? 4 : pre ? 3 : pieces == 1 ? 0 : pieces == 2 ? 1 : 2;
+}
+
 // the amax word behind the two fp16 planes of a weight (bdv_conv_split_weights_f16x2)
 const unsigned* f16x2_weight_amax(const void* planes, const bdv_conv_geom* gg) {
   return (const unsigned*)((const unsigned char*)planes + (size_t)2 * gg->Cout * gg->R * gg->S * gg->Cin * sizeof(unsigned short));
 }
 
-// pieces: 1 .. 3 bf16 pieces, or kArithF16x2 with the activation operand's amax word (a call the plan leaves to three bf16 pieces
-// ignores it)
-int conv_fprop_pl_impl(const void* x, const float* w, const void* planes_fprop, void* y, const bdv_conv_geom* gg, float* bn_partial,
-                       const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, int pieces, const float* pre_scale,
-                       const float* pre_shift, const unsigned* amax_x, void* stream) {
+// bytes of the caller's workspace a K split may use
+size_t ksplit_workspace(const void* workspace, size_t bytes) {
+  return workspace == nullptr ? 0 : bytes < kMaxSplitWorkspace ? bytes : kMaxSplitWorkspace;
+}
+
+int launch_check(const char* who, const char* stage = "") {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) bdv_set_error("%s%s: launch failed: %s", who, stage, hipGetErrorString(e));
+  return (int)e;
+}
+
+// the forward epilogue a caller asked for: batch statistics, or the folded eval-mode BatchNorm of bdv_conv_affine
+int make_fprop_epi(const char* who, float* bn_partial, const bdv_conv_affine* affine, const float* pre_scale, const float* pre_shift,
+                   FpropEpi* epi) {
+  *epi = {bn_partial, 0, nullptr, nullptr, nullptr, 0, pre_scale, pre_shift};
+  if (affine == nullptr) return BDV_OK;
+  BDV_REQUIRE(bn_partial == nullptr, "%s: batch statistics and the folded eval-mode BatchNorm exclude each other", who);
+  BDV_REQUIRE(affine->scale && affine->shift, "%s: null pointer in bdv_conv_affine", who);
+  BDV_REQUIRE(bdv_aligned16(affine->scale) && bdv_aligned16(affine->shift) && bdv_aligned16(affine->residual),
+              "%s: bdv_conv_affine pointers must be 16-byte aligned", who);
+  epi->scale = affine->scale;
+  epi->shift = affine->shift;
+  epi->res = affine->residual;
+  epi->relu = affine->relu;
+  return BDV_OK;
+}
+
+// the BatchNorm-backward statistics a data gradient takes in its epilogue (bdv_bn_stat_fuse; NULL: none)
+int make_bn_stat(const char* who, const bdv_bn_stat_fuse* bn_stat, const bdv_conv_geom* gg, const ConvPlan& cp, BnStat* stat) {
+  *stat = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+  if (bn_stat == nullptr) return BDV_OK;
+  BDV_REQUIRE(gg->stride == 1 || (gg->R >= gg->stride && gg->S >= gg->stride),
+              "%s: fused BatchNorm statistics with stride 2 need a filter that reaches every input pixel (R, S >= 2)", who);
+  BDV_REQUIRE(bn_stat->y && bn_stat->mean && bn_stat->invstd && bn_stat->partial, "%s: null pointer in bdv_bn_stat_fuse", who);
+  BDV_REQUIRE(bdv_aligned16(bn_stat->y) && bdv_aligned16(bn_stat->mean) && bdv_aligned16(bn_stat->invstd) && bdv_aligned16(bn_stat->partial),
+              "%s: bdv_bn_stat_fuse pointers must be 16-byte aligned", who);
+  BDV_REQUIRE(bn_stat->relu_mask == nullptr || gg->Cin % 32 == 0, "%s: a ReLU mask needs Cin %% 32 == 0", who);
+  stat->y = bn_stat->y;
+  stat->mask = bn_stat->relu_mask;
+  stat->mean = bn_stat->mean;
+  stat->invstd = bn_stat->invstd;
+  stat->partial = bn_stat->partial;
+  stat->rscale = bn_stat->relu_mask == nullptr ? bn_stat->relu_scale : nullptr;
+  stat->rshift = bn_stat->relu_shift;
+  stat->MT = cp.stat_rows;   // one row per row tile of the planned kernel (stride 2: per parity class and row tile)
+  BDV_REQUIRE(stat->rscale == nullptr || cp.family != BDV_CONV_F32 || !cp.wide,
+              "%s: a ReLU sign derived from y (relu_scale) is not compiled into the 128-wide fp32-MFMA kernel", who);
+  return BDV_OK;
+}
+
+// arith: 0 = the fp32-MFMA kernels, 1 .. 3 bf16 pieces, or kArithF16x2 with the activation operand's amax word (a call the plan
+// leaves to three bf16 pieces ignores it)
+int conv_fprop_launch(const char* who, const void* x, const float* w, const void* planes, void* y, const bdv_conv_geom* gg,
+                      float* bn_partial, const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, int arith,
+                      const float* pre_scale, const float* pre_shift, const unsigned* amax_x, void* stream) {
   const bool pre = pre_scale != nullptr;
-  const ConvPlan cp = plan_conv(gg, kFprop, pieces, pre);
+  const ConvPlan cp = plan_conv(gg, kFprop, arith, pre);
   if (cp.family < 0) return BDV_EINVAL;
-  if (pieces == kArithF16x2 && !cp.f16) pieces = 3;
-  const PieceScales ps = {cp.f16 ? amax_x : nullptr, cp.f16 ? f16x2_weight_amax(planes_fprop, gg) : nullptr};
-  BDV_REQUIRE(!cp.f16 || (amax_x != nullptr && planes_fprop != nullptr), "bdv_conv_fprop_f16x2: null pointer (amax_x, planes_fprop)");
-  const bool h16 = gg->act_dtype == BDV_ACT_BF16;
+  const bool pl = cp.family == BDV_CONV_PL;   // else: the two-workgroups-per-CU kernels (weights from the planes too), the stem, 64 columns behind 1x1
+  BDV_REQUIRE(!cp.f16 || (amax_x != nullptr && planes != nullptr), "%s: null pointer (amax_x, planes_fprop)", who);
   if (pre) {
     BDV_REQUIRE(pre_shift != nullptr && cp.pre_ok,
-                "bdv_conv_fprop_pl: a producer BatchNorm in the loader needs the plane kernels (pieces 3, no temporal shift, Cin %% 32 == 0)");
-    BDV_REQUIRE(bdv_aligned16(pre_scale) && bdv_aligned16(pre_shift), "bdv_conv_fprop_pl: pre_scale / pre_shift must be 16-byte aligned");
+                "%s: a producer BatchNorm in the loader needs the plane kernels (pieces 3, no temporal shift, Cin %% 32 == 0)", who);
+    BDV_REQUIRE(bdv_aligned16(pre_scale) && bdv_aligned16(pre_shift), "%s: pre_scale / pre_shift must be 16-byte aligned", who);
   }
-  if (cp.family != BDV_CONV_PL)  // sites of the two-workgroups-per-CU kernels (weights from the planes too), the stem, 64 columns behind 1x1
-    return conv_fprop_impl((const float*)x, w, (float*)y, gg, bn_partial, affine, workspace, workspace_bytes, stream, pieces, planes_fprop);
-  BDV_REQUIRE(x && y && planes_fprop, "bdv_conv_fprop_pl: null pointer");
-  FpropEpi epi = {bn_partial, 0, nullptr, nullptr, nullptr, 0, pre_scale, pre_shift};
-  if (affine != nullptr) {
-    BDV_REQUIRE(bn_partial == nullptr, "bdv_conv_fprop_pl: batch statistics and the folded eval-mode BatchNorm exclude each other");
-    BDV_REQUIRE(affine->scale && affine->shift, "bdv_conv_fprop_pl: null pointer in bdv_conv_affine");
-    BDV_REQUIRE(bdv_aligned16(affine->scale) && bdv_aligned16(affine->shift) && bdv_aligned16(affine->residual),
-                "bdv_conv_fprop_pl: bdv_conv_affine pointers must be 16-byte aligned");
-    epi.scale = affine->scale;
-    epi.shift = affine->shift;
-    epi.res = affine->residual;
-    epi.relu = affine->relu;
+  BDV_REQUIRE(pl || !cp.reads_planes || planes != nullptr,
+              "%s: this site runs on the weight planes (bdv_conv_plan_query: reads_planes), planes_fprop is NULL", who);
+  BDV_REQUIRE(x && y && (pl ? planes != nullptr : w != nullptr), "%s: null pointer", who);
+  FpropEpi epi;
+  if (int e = make_fprop_epi(who, bn_partial, affine, pre_scale, pre_shift, &epi)) return e;
+  BDV_REQUIRE(bdv_aligned16(x) && bdv_aligned16(pl ? planes : (const void*)w) && bdv_aligned16(y) && bdv_aligned16(workspace),
+              "%s: pointers must be 16-byte aligned", who);
+  const Geom g = fprop_geom(gg);
+  const size_t ws_bytes = ksplit_workspace(workspace, workspace_bytes);
+  const hipStream_t s = (hipStream_t)stream;
+  float* const slab = (float*)workspace;
+  if (!pl) {
+    const float* const xf = (const float*)x;
+    float* const yf = (float*)y;
+    const FdPlan p = plan_fprop(g, ws_bytes, cp.family == BDV_CONV_X3);
+    BDV_REQUIRE(p.MT == cp.stat_rows && p.wide == cp.wide, "%s: row tiles %d != planned %d", who, p.MT, cp.stat_rows);
+    const int blocks = p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split;
+    epi.MT = p.MT;
+    if (debug_plan())
+      fprintf(stderr, "[bdv plan] fprop %dx%d Cin %d Cout %d k%d s%d: tiles %d nk %d -> dp %d rem %d split %d\n", g.H, g.W,
+              g.Cin, g.Cout, g.R, g.stride, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split);
+    if (cp.family == BDV_CONV_C4_X3) {
+      if (p.wide)
+        hipLaunchKernelGGL((conv_fprop_c4_x3_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, xf, w, yf, g, p.NT, epi);
+      else
+        hipLaunchKernelGGL((conv_fprop_c4_x3_kernel<128, 64, 2, 2>), dim3(blocks), dim3(256), 0, s, xf, w, yf, g, p.NT, epi);
+    } else if (cp.family == BDV_CONV_C4) {
+      if (p.wide)
+        hipLaunchKernelGGL((conv_fprop_c4_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, xf, w, yf, g, p.NT, epi);
+      else
+        hipLaunchKernelGGL((conv_fprop_c4_kernel<128, 64, 2, 2>), dim3(blocks), dim3(256), 0, s, xf, w, yf, g, p.NT, epi);
+    } else if (cp.family == BDV_CONV_X3) {
+      hipLaunchKernelGGL((conv_fprop_x3_kernel<128, 128, 2, 2, true>), dim3(blocks), dim3(256), 0, s, xf, (const float*)planes, yf, g, p.NT, p.wk, slab, epi);
+    } else if (p.wide) {
+      hipLaunchKernelGGL((conv_fprop_kernel<128, 128, 2, 2>), dim3(blocks), dim3(256), 0, s, xf, w, yf, g, p.NT, p.wk, slab, epi);
+    } else {
+      hipLaunchKernelGGL((conv_fprop_kernel<128, 64, 2, 2>), dim3(blocks), dim3(256), 0, s, xf, w, yf, g, p.NT, p.wk, slab, epi);
+    }
+    if (int e = launch_check(who)) return e;
+    if (p.wk.split > 1) {
+      const dim3 fg(p.wk.rem_tiles);
+      if (p.wide)
+        hipLaunchKernelGGL((conv_fprop_fixup_kernel<128, 128, 2, 2>), fg, dim3(256), 0, s, (const float*)slab, yf, g, p.NT, p.wk, epi);
+      else
+        hipLaunchKernelGGL((conv_fprop_fixup_kernel<128, 64, 2, 2>), fg, dim3(256), 0, s, (const float*)slab, yf, g, p.NT, p.wk, epi);
+      return launch_check(who, "(fixup)");
+    }
+    return BDV_OK;
   }
-  BDV_REQUIRE(bdv_aligned16(x) && bdv_aligned16(planes_fprop) && bdv_aligned16(y) && bdv_aligned16(workspace),
-              "bdv_conv_fprop_pl: pointers must be 16-byte aligned");
-  Geom g = make_geom(gg);
-  g.M = g.N * g.Ho * g.Wo;
-  g.Ktot = g.Rt * g.R * g.S * g.Cin;
-  BDV_REQUIRE((int64_t)3 * g.Cout * g.Ktot * 2 < (1ll << 31), "bdv_conv_fprop_pl: weight planes exceed 2^31 bytes");
-  hipStream_t s = (hipStream_t)stream;
-  const PlPlan p = plan_pl(cp.cfg, g.M, g.Cout, g.Ktot / BK, workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, !h16);  // (no K split with bf16 storage: the fix-up kernels are fp32)
-  BDV_REQUIRE(p.MT == cp.stat_rows, "bdv_conv_fprop_pl: row tiles %d != planned %d", p.MT, cp.stat_rows);  // bn_partial has one row per row tile of THIS kernel
+  BDV_REQUIRE((int64_t)3 * g.Cout * g.Ktot * 2 < (1ll << 31), "%s: weight planes exceed 2^31 bytes", who);
+  const bool h16 = gg->act_dtype == BDV_ACT_BF16;
+  const PlPlan p = plan_pl(cp.cfg, g.M, g.Cout, g.Ktot / BK, ws_bytes, !h16);  // (no K split with bf16 storage: the fix-up kernels are fp32)
+  BDV_REQUIRE(p.MT == cp.stat_rows, "%s: row tiles %d != planned %d", who, p.MT, cp.stat_rows);  // bn_partial has one row per row tile of THIS kernel
   const int blocks = p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split;
   epi.MT = p.MT;
-  float* slab = (float*)workspace;
-  const unsigned short* wp = (const unsigned short*)planes_fprop;
+  const PieceScales ps = {cp.f16 ? amax_x : nullptr, cp.f16 ? f16x2_weight_amax(planes, gg) : nullptr};
+  const unsigned short* const wp = (const unsigned short*)planes;
+  const int variant = pl_arith(cp, gg, arith, pre);
   if (debug_plan())
     fprintf(stderr, "[bdv plan] fprop_pl %dx%d Cin %d Cout %d k%d s%d: cfg %d tiles %d nk %d -> dp %d rem %d split %d (est %.0f us)\n", g.H,
             g.W, g.Cin, g.Cout, g.R, g.stride, p.cfg, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split, p.est_us);
-#define BDV_FPROP_PL(BM_, BN_, WM_, WN_, NB_)                                                                                         \
-  do {                                                                                                                                \
-    if (cp.f16)                                                                                                                       \
-      hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 2, false, 4, F16Pieces>), dim3(blocks), dim3(64 * WM_ * WN_), 0, \
-                         s, x, wp, y, g, p.NT, p.wk, slab, epi, ps);                                                                  \
-    else if (h16)                                                                                                                     \
-      hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 1, false, 2>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y, \
-                         g, p.NT, p.wk, slab, epi, ps);                                                                               \
-    else if (pre)                                                                                                                     \
-      hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 3, true>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y,  \
-                         g, p.NT, p.wk, slab, epi, ps);                                                                               \
-    else if (pieces == 1)                                                                                                             \
-      hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 1>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y, g,    \
-                         p.NT, p.wk, slab, epi, ps);                                                                                  \
-    else if (pieces == 2)                                                                                                             \
-      hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 2>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y, g,    \
-                         p.NT, p.wk, slab, epi, ps);                                                                                  \
-    else                                                                                                                              \
-      hipLaunchKernelGGL((conv_fprop_pl_kernel<BM_, BN_, WM_, WN_, NB_, 3>), dim3(blocks), dim3(64 * WM_ * WN_), 0, s, x, wp, y, g,    \
-                         p.NT, p.wk, slab, epi, ps);                                                                                  \
-    BDV_LAUNCH_CHECK("bdv_conv_fprop_pl");                                                                                            \
-    if (p.wk.split > 1) {                                                                                                             \
-      hipLaunchKernelGGL((conv_fprop_fixup_kernel<BM_, BN_, WM_, WN_>), dim3(p.wk.rem_tiles), dim3(64 * WM_ * WN_), 0, s,             \
-                         (const float*)slab, (float*)y, g, p.NT, p.wk, epi);                                                                  \
-      BDV_LAUNCH_CHECK("bdv_conv_fprop_pl(fixup)");                                                                                   \
-    }                                                                                                                                 \
-  } while (0)
-  if (p.cfg == 0) BDV_FPROP_PL(128, 256, 2, 4, 2);
-  else if (p.cfg == 1) BDV_FPROP_PL(256, 128, 4, 2, 2);
-  else if (p.cfg == 2) BDV_FPROP_PL(256, 256, 2, 4, 1);
-  else if (p.cfg == 5) BDV_FPROP_PL(128, 128, 2, 2, 1);
-  else BDV_FPROP_PL(256, 64, 4, 2, 2);
-#undef BDV_FPROP_PL
+  bool launched = false;   // stays false where the tables compile no kernel for (tile, variant): an error, never a silent return
+  static_index<kNumPlTiles>(p.cfg, [&](auto tile) {
+    constexpr PlTile k = kPlTiles[decltype(tile)::value];
+    if constexpr (k.fprop)
+      static_index<kNumPlAriths>(variant, [&](auto ar) {
+        constexpr int A = decltype(ar)::value;
+        constexpr PlArith a = kPlAriths[A];
+        launched = true;
+        hipLaunchKernelGGL((conv_fprop_pl_kernel<k.BM, k.BN, k.WM, k.WN, k.NBUF, a.NP, a.pre, a.ES, PlPieces<A>>), dim3(blocks),
+                           dim3(64 * k.WM * k.WN), 0, s, x, wp, y, g, p.NT, p.wk, slab, epi, ps);
+      });
+  });
+  BDV_REQUIRE(launched, "%s: no kernel is compiled for tile %d, variant %d", who, p.cfg, variant);
+  if (int e = launch_check(who)) return e;
+  if (p.wk.split > 1) {
+    static_index<kNumPlTiles>(p.cfg, [&](auto tile) {
+      constexpr PlTile k = kPlTiles[decltype(tile)::value];
+      if constexpr (k.fprop)
+        hipLaunchKernelGGL((conv_fprop_fixup_kernel<k.BM, k.BN, k.WM, k.WN>), dim3(p.wk.rem_tiles), dim3(64 * k.WM * k.WN), 0, s,
+                           (const float*)slab, (float*)y, g, p.NT, p.wk, epi);
+    });
+    return launch_check(who, "(fixup)");
+  }
   return BDV_OK;
 }
 }  // namespace
 
+extern "C" int bdv_conv_fprop(const float* x, const float* w, float* y, const bdv_conv_geom* gg, float* bn_partial,
+                              const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes, void* stream) {
+  return conv_fprop_launch("bdv_conv_fprop", x, w, nullptr, y, gg, bn_partial, affine, workspace, workspace_bytes, 0, nullptr, nullptr,
+                           nullptr, stream);
+}
+
 extern "C" int bdv_conv_fprop_pl(const void* x, const float* w, const void* planes_fprop, void* y, const bdv_conv_geom* gg,
                                  float* bn_partial, const bdv_conv_affine* affine, void* workspace, size_t workspace_bytes,
                                  int pieces, const float* pre_scale, const float* pre_shift, void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_fprop_pl")) return e;
   BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_fprop_pl: pieces = %d (3, 2 or 1)", pieces);
-  return conv_fprop_pl_impl(x, w, planes_fprop, y, gg, bn_partial, affine, workspace, workspace_bytes, pieces, pre_scale, pre_shift, nullptr,
-                            stream);
+  return conv_fprop_launch("bdv_conv_fprop_pl", x, w, planes_fprop, y, gg, bn_partial, affine, workspace, workspace_bytes, pieces,
+                           pre_scale, pre_shift, nullptr, stream);
 }
 
 extern "C" int bdv_conv_fprop_f16x2(const void* x, const void* amax_x, const float* w, const void* planes_fprop, void* y,
                                     const bdv_conv_geom* gg, float* bn_partial, const bdv_conv_affine* affine, void* workspace,
                                     size_t workspace_bytes, const float* pre_scale, const float* pre_shift, void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_fprop_f16x2")) return e;
-  return conv_fprop_pl_impl(x, w, planes_fprop, y, gg, bn_partial, affine, workspace, workspace_bytes, kArithF16x2, pre_scale, pre_shift,
-                            (const unsigned*)amax_x, stream);
+  return conv_fprop_launch("bdv_conv_fprop_f16x2", x, w, planes_fprop, y, gg, bn_partial, affine, workspace, workspace_bytes,
+                           kArithF16x2, pre_scale, pre_shift, (const unsigned*)amax_x, stream);
 }
 
 namespace {
-int conv_dgrad_pl_impl(const void* dy, const float* w, const void* planes_dgrad, void* dx, const void* add_src,
-                       const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat, void* workspace,
-                       size_t workspace_bytes, int pieces, const unsigned* amax_dy, void* stream) {
-  const ConvPlan cp = plan_conv(gg, kDgrad, pieces, false);
+int conv_dgrad_launch(const char* who, const void* dy, const float* w, const void* planes, void* dx, const void* add_src,
+                      const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat, void* workspace,
+                      size_t workspace_bytes, int arith, const unsigned* amax_dy, void* stream) {
+  const ConvPlan cp = plan_conv(gg, kDgrad, arith, false);
   if (cp.family < 0) return BDV_EINVAL;
-  if (pieces == kArithF16x2 && !cp.f16) pieces = 3;
-  const PieceScales ps = {cp.f16 ? amax_dy : nullptr, cp.f16 ? f16x2_weight_amax(planes_dgrad, gg) : nullptr};
-  BDV_REQUIRE(!cp.f16 || (amax_dy != nullptr && planes_dgrad != nullptr), "bdv_conv_dgrad_f16x2: null pointer (amax_dy, planes_dgrad)");
-  const bool h16 = gg->act_dtype == BDV_ACT_BF16;
-  if (cp.family != BDV_CONV_PL)
-    return conv_dgrad_impl((const float*)dy, w, (float*)dx, (const float*)add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, stream,
-                           pieces, planes_dgrad);
-  BnStat stat = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-  if (bn_stat != nullptr) {
-    BDV_REQUIRE(gg->stride == 1 || (gg->R >= gg->stride && gg->S >= gg->stride),
-                "bdv_conv_dgrad_pl: fused BatchNorm statistics with stride 2 need a filter that reaches every input pixel (R, S >= 2)");
-    BDV_REQUIRE(bn_stat->y && bn_stat->mean && bn_stat->invstd && bn_stat->partial, "bdv_conv_dgrad_pl: null pointer in bdv_bn_stat_fuse");
-    BDV_REQUIRE(bdv_aligned16(bn_stat->y) && bdv_aligned16(bn_stat->mean) && bdv_aligned16(bn_stat->invstd) &&
-                    bdv_aligned16(bn_stat->partial), "bdv_conv_dgrad_pl: bdv_bn_stat_fuse pointers must be 16-byte aligned");
-    BDV_REQUIRE(bn_stat->relu_mask == nullptr || gg->Cin % 32 == 0, "bdv_conv_dgrad_pl: a ReLU mask needs Cin %% 32 == 0");
-    stat.y = bn_stat->y;
-    stat.mask = bn_stat->relu_mask;
-    stat.mean = bn_stat->mean;
-    stat.invstd = bn_stat->invstd;
-    stat.partial = bn_stat->partial;
-    stat.rscale = bn_stat->relu_mask == nullptr ? bn_stat->relu_scale : nullptr;
-    stat.rshift = bn_stat->relu_shift;
-  }
-  BDV_REQUIRE(dy && dx && planes_dgrad, "bdv_conv_dgrad_pl: null pointer");
-  BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(planes_dgrad) && bdv_aligned16(dx) && bdv_aligned16(workspace),
-              "bdv_conv_dgrad_pl: pointers must be 16-byte aligned");
-  BDV_REQUIRE(add_src != nullptr || add_mask_src == nullptr, "bdv_conv_dgrad_pl: add_mask_src without add_src");
-  Geom g = make_geom(gg);
-  g.M = g.N * g.H * g.W;
-  g.Ktot = g.R * g.S * g.Cout;
-  BDV_REQUIRE((int64_t)3 * g.Cin * g.Ktot * 2 < (1ll << 31), "bdv_conv_dgrad_pl: weight planes exceed 2^31 bytes");
-  hipStream_t s = (hipStream_t)stream;
+  const bool pl = cp.family == BDV_CONV_PL;
+  BDV_REQUIRE(!cp.f16 || (amax_dy != nullptr && planes != nullptr), "%s: null pointer (amax_dy, planes_dgrad)", who);
+  BDV_REQUIRE(pl || !cp.reads_planes || planes != nullptr,
+              "%s: this site runs on the weight planes (bdv_conv_plan_query: reads_planes), planes_dgrad is NULL", who);
+  BnStat stat;
+  if (int e = make_bn_stat(who, bn_stat, gg, cp, &stat)) return e;
+  BDV_REQUIRE(dy && dx && (pl ? planes != nullptr : w != nullptr), "%s: null pointer", who);
+  BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(pl ? planes : (const void*)w) && bdv_aligned16(dx) && bdv_aligned16(workspace),
+              "%s: pointers must be 16-byte aligned", who);
+  BDV_REQUIRE(add_src != nullptr || add_mask_src == nullptr, "%s: add_mask_src without add_src", who);
+  const Geom g = dgrad_geom(gg);
+  BDV_REQUIRE(!pl || (int64_t)3 * g.Cin * g.Ktot * 2 < (1ll << 31), "%s: weight planes exceed 2^31 bytes", who);
+  const size_t ws_bytes = ksplit_workspace(workspace, workspace_bytes);
   const int st = g.stride;
-  const int Mc0 = g.N * ((g.H + st - 1) / st) * ((g.W + st - 1) / st);  // largest parity class
-  PlPlan p = plan_pl(cp.cfg, st == 1 ? g.M : Mc0, g.Cin, g.Ktot / BK,
-                     workspace ? (workspace_bytes < kMaxSplitWorkspace ? workspace_bytes : kMaxSplitWorkspace) : 0, st == 1 && !h16);
-  BDV_REQUIRE(st * st * p.MT == cp.stat_rows, "bdv_conv_dgrad_pl: row tiles %d != planned %d", st * st * p.MT, cp.stat_rows);
+  const hipStream_t s = (hipStream_t)stream;
+  float* const slab = (float*)workspace;
+  // parity classes of odd-sized inputs have fewer row tiles than the largest: their rows of the statistics partial stay zero
+  const size_t stat_zero_bytes = bn_stat != nullptr && st != 1 ? (size_t)2 * stat.MT * g.Cin * sizeof(float) : 0;
+  if (!pl) {
+    const float* const dyf = (const float*)dy;
+    const float* const addf = (const float*)add_src;
+    float* const dxf = (float*)dx;
+    const FdPlan p = plan_dgrad(g, ws_bytes, cp.family == BDV_CONV_X3);
+    BDV_REQUIRE(st * st * p.MT == cp.stat_rows && p.wide == cp.wide, "%s: row tiles %d != planned %d", who, st * st * p.MT, cp.stat_rows);
+    if (stat_zero_bytes) (void)hipMemsetAsync(stat.partial, 0, stat_zero_bytes, s);
+    const dim3 grid(p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split, st * st);
+    if (debug_plan())
+      fprintf(stderr, "[bdv plan] dgrad %dx%d Cin %d Cout %d k%d s%d: tiles %d nk %d -> dp %d rem %d split %d\n", g.H, g.W,
+              g.Cin, g.Cout, g.R, g.stride, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split);
+    if (cp.family == BDV_CONV_X3)
+      hipLaunchKernelGGL((conv_dgrad_x3_kernel<128, 128, 2, 2, true>), grid, dim3(256), 0, s, dyf, (const float*)planes, dxf, addf, add_mask_src, g, p.NT, p.wk, slab, stat);
+    else if (p.wide)
+      hipLaunchKernelGGL((conv_dgrad_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, dyf, w, dxf, addf, add_mask_src, g, p.NT, p.wk, slab, stat);
+    else
+      hipLaunchKernelGGL((conv_dgrad_kernel<128, 64, 2, 2>), grid, dim3(256), 0, s, dyf, w, dxf, addf, add_mask_src, g, p.NT, p.wk, slab, stat);
+    if (int e = launch_check(who)) return e;
+    if (p.wk.split > 1) {
+      const dim3 fg(p.wk.rem_tiles);
+      if (p.wide)
+        hipLaunchKernelGGL((conv_dgrad_fixup_kernel<128, 128, 2, 2>), fg, dim3(256), 0, s, (const float*)slab, dxf, addf, add_mask_src, g, p.NT, p.wk, stat);
+      else
+        hipLaunchKernelGGL((conv_dgrad_fixup_kernel<128, 64, 2, 2>), fg, dim3(256), 0, s, (const float*)slab, dxf, addf, add_mask_src, g, p.NT, p.wk, stat);
+      return launch_check(who, "(fixup)");
+    }
+    return BDV_OK;
+  }
+  const bool h16 = gg->act_dtype == BDV_ACT_BF16;
+  const PlGemm m = pl_gemm(gg, kDgrad);   // stride 2: the largest parity class, no K split
+  PlPlan p = plan_pl(cp.cfg, m.M, m.ncols, m.nk, ws_bytes, m.ksplit_ok && !h16);
+  BDV_REQUIRE(st * st * p.MT == cp.stat_rows, "%s: row tiles %d != planned %d", who, st * st * p.MT, cp.stat_rows);
   if (st != 1) p.wk.dp_tiles = ((p.MT + 7) / 8) * 8 * p.NT;  // padded grid per parity class
-  // the statistics partial has one row per row tile of THIS kernel (stride 2: per parity class and row tile)
-  stat.MT = st * st * p.MT;
-  if (st != 1 && stat.y != nullptr)
-    (void)hipMemsetAsync(stat.partial, 0, (size_t)2 * stat.MT * g.Cin * sizeof(float), s);
-  const int work_items = p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split;
-  const dim3 grid(work_items, st * st);
-  float* slab = (float*)workspace;
-  const unsigned short* dp = (const unsigned short*)planes_dgrad;
+  if (stat_zero_bytes) (void)hipMemsetAsync(stat.partial, 0, stat_zero_bytes, s);
+  const dim3 grid(p.wk.dp_tiles + p.wk.rem_tiles * p.wk.split, st * st);
   if (debug_plan())
     fprintf(stderr, "[bdv plan] dgrad_pl %dx%d Cin %d Cout %d k%d s%d: cfg %d tiles %d nk %d -> dp %d rem %d split %d (est %.0f us)\n", g.H,
             g.W, g.Cin, g.Cout, g.R, g.stride, p.cfg, p.MT * p.NT, p.nk, p.wk.dp_tiles, p.wk.rem_tiles, p.wk.split, p.est_us);
-#define BDV_DGRAD_PL(BM_, BN_, WM_, WN_, NB_)                                                                                          \
-  do {                                                                                                                                 \
-    if (cp.f16)                                                                                                                        \
-      hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 2, 4, F16Pieces>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, \
-                         add_src, add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                        \
-    else if (h16)                                                                                                                      \
-      hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 1, 2>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, add_src,  \
-                         add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                                 \
-    else if (pieces == 1)                                                                                                              \
-      hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 1>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, add_src,     \
-                         add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                                 \
-    else if (pieces == 2)                                                                                                              \
-      hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 2>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, add_src,     \
-                         add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                                 \
-    else                                                                                                                               \
-      hipLaunchKernelGGL((conv_dgrad_pl_kernel<BM_, BN_, WM_, WN_, NB_, 3>), grid, dim3(64 * WM_ * WN_), 0, s, dy, dp, dx, add_src,     \
-                         add_mask_src, g, p.NT, p.wk, slab, stat, ps);                                                                 \
-    BDV_LAUNCH_CHECK("bdv_conv_dgrad_pl");                                                                                             \
-    if (p.wk.split > 1) {                                                                                                              \
-      hipLaunchKernelGGL((conv_dgrad_fixup_kernel<BM_, BN_, WM_, WN_>), dim3(p.wk.rem_tiles), dim3(64 * WM_ * WN_), 0, s,              \
-                         (const float*)slab, (float*)dx, (const float*)add_src, add_mask_src, g, p.NT, p.wk, stat);                                          \
-      BDV_LAUNCH_CHECK("bdv_conv_dgrad_pl(fixup)");                                                                                    \
-    }                                                                                                                                  \
-  } while (0)
-  if (p.cfg == 0) BDV_DGRAD_PL(128, 256, 2, 4, 2);
-  else if (p.cfg == 1) BDV_DGRAD_PL(256, 128, 4, 2, 2);
-  else if (p.cfg == 2) BDV_DGRAD_PL(256, 256, 2, 4, 1);
-  else if (p.cfg == 4) BDV_DGRAD_PL(64, 128, 2, 2, 1);
-  else if (p.cfg == 5) BDV_DGRAD_PL(128, 128, 2, 2, 1);
-  else BDV_DGRAD_PL(256, 64, 4, 2, 2);
-#undef BDV_DGRAD_PL
+  const PieceScales ps = {cp.f16 ? amax_dy : nullptr, cp.f16 ? f16x2_weight_amax(planes, gg) : nullptr};
+  const unsigned short* const dp = (const unsigned short*)planes;
+  const int variant = pl_arith(cp, gg, arith, false);
+  bool launched = false;
+  static_index<kNumPlTiles>(p.cfg, [&](auto tile) {
+    constexpr PlTile k = kPlTiles[decltype(tile)::value];
+    static_index<kNumPlAriths>(variant, [&](auto ar) {
+      constexpr int A = decltype(ar)::value;
+      constexpr PlArith a = kPlAriths[A];
+      if constexpr (!a.pre) {
+        launched = true;
+        hipLaunchKernelGGL((conv_dgrad_pl_kernel<k.BM, k.BN, k.WM, k.WN, k.NBUF, a.NP, a.ES, PlPieces<A>>), grid, dim3(64 * k.WM * k.WN), 0,
+                           s, dy, dp, dx, add_src, add_mask_src, g, p.NT, p.wk, slab, stat, ps);
+      }
+    });
+  });
+  BDV_REQUIRE(launched, "%s: no kernel is compiled for tile %d, variant %d", who, p.cfg, variant);
+  if (int e = launch_check(who)) return e;
+  if (p.wk.split > 1) {
+    static_index<kNumPlTiles>(p.cfg, [&](auto tile) {
+      constexpr PlTile k = kPlTiles[decltype(tile)::value];
+      hipLaunchKernelGGL((conv_dgrad_fixup_kernel<k.BM, k.BN, k.WM, k.WN>), dim3(p.wk.rem_tiles), dim3(64 * k.WM * k.WN), 0, s,
+                         (const float*)slab, (float*)dx, (const float*)add_src, add_mask_src, g, p.NT, p.wk, stat);
+    });
+    return launch_check(who, "(fixup)");
+  }
   return BDV_OK;
 }
 }  // namespace
 
+extern "C" int bdv_conv_dgrad(const float* dy, const float* w, float* dx, const float* add_src,
+                              const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  return conv_dgrad_launch("bdv_conv_dgrad", dy, w, nullptr, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, 0, nullptr,
+                           stream);
+}
+
 extern "C" int bdv_conv_dgrad_pl(const void* dy, const float* w, const void* planes_dgrad, void* dx, const void* add_src,
                                  const uint32_t* add_mask_src, const bdv_conv_geom* gg, const bdv_bn_stat_fuse* bn_stat,
                                  void* workspace, size_t workspace_bytes, int pieces, void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_dgrad_pl")) return e;
   BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_dgrad_pl: pieces = %d (3, 2 or 1)", pieces);
-  return conv_dgrad_pl_impl(dy, w, planes_dgrad, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, pieces, nullptr, stream);
+  return conv_dgrad_launch("bdv_conv_dgrad_pl", dy, w, planes_dgrad, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes,
+                           pieces, nullptr, stream);
 }
 
 extern "C" int bdv_conv_dgrad_f16x2(const void* dy, const void* amax_dy, const float* w, const void* planes_dgrad, void* dx,
                                     const void* add_src, const uint32_t* add_mask_src, const bdv_conv_geom* gg,
                                     const bdv_bn_stat_fuse* bn_stat, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int e = check_geom(gg, "bdv_conv_dgrad_f16x2")) return e;
-  return conv_dgrad_pl_impl(dy, w, planes_dgrad, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes, kArithF16x2,
-                            (const unsigned*)amax_dy, stream);
+  return conv_dgrad_launch("bdv_conv_dgrad_f16x2", dy, w, planes_dgrad, dx, add_src, add_mask_src, gg, bn_stat, workspace, workspace_bytes,
+                           kArithF16x2, (const unsigned*)amax_dy, stream);
 }
 
 namespace {
-
-// main kernel of a BDV_CONV_WGRAD_F32 plan: split-K partial products into `slab` (the plan's `splits` slices of dw's size)
-int wgrad_partial(const char* who, const float* dy, const float* x, const bdv_conv_geom* gg, void* workspace, size_t workspace_bytes,
-                  hipStream_t s, int* splits_out, const ConvPlan& cp) {
-  const WgradPlan& p = cp.wg;
-  const size_t need = (size_t)p.splits * gg->Cout * gg->R * gg->S * gg->Cin * sizeof(float);
-  if (workspace_bytes < need) {
-    bdv_set_error("%s: workspace %zu < required %zu bytes", who, workspace_bytes, need);
+// Split-K partial products of the weight gradient into `slab` (the plan's `splits` slices of dw's size, reduced by wgrad_reduce_*).
+// arith as in conv_fprop_launch; the amax words only with kArithF16x2.
+int conv_wgrad_partial_launch(const char* who, const void* dy, const void* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes,
+                              int arith, const float* pre_scale, const float* pre_shift, const unsigned* amax_dy,
+                              const unsigned* amax_x, void* stream, int* splits_out = nullptr) {
+  const ConvPlan cp = plan_conv(gg, kWgrad, arith, pre_scale != nullptr);
+  if (cp.family < 0) return BDV_EINVAL;
+  const bool pl = cp.family == BDV_CONV_WGRAD_PL;
+  BDV_REQUIRE(!cp.f16 || (amax_dy != nullptr && amax_x != nullptr), "%s: null pointer (amax_dy, amax_x)", who);
+  BDV_REQUIRE(pre_scale == nullptr || pre_shift != nullptr, "%s: pre_scale without pre_shift", who);
+  BDV_REQUIRE(dy && x && slab, "%s: null pointer", who);
+  BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(x) && bdv_aligned16(slab), "%s: pointers must be 16-byte aligned", who);
+  const size_t need = (size_t)cp.splits * gg->Cout * (gg->Rt > 1 ? gg->Rt : 1) * gg->R * gg->S * gg->Cin * sizeof(float);
+  if (slab_bytes < need) {
+    bdv_set_error("%s: %s %zu < required %zu bytes", who, pl ? "slab" : "workspace", slab_bytes, need);
     return BDV_EWORKSPACE;
   }
-  Geom g = make_geom(gg);
-  g.M = g.N * g.Ho * g.Wo;
-  g.Ktot = g.Rt * g.R * g.S * g.Cin;
-  float* slab = (float*)workspace;
+  if (splits_out != nullptr) *splits_out = cp.splits;
+  const Geom g = fprop_geom(gg);
+  const hipStream_t s = (hipStream_t)stream;
+  const int incr = g.Ho * g.Wo > BK && BK / g.Wo + 1 <= g.Ho;
+  if (!pl) {
+    const WgradPlan& p = cp.wg;
+    const float* const dyf = (const float*)dy;
+    const float* const xf = (const float*)x;
+    const dim3 grid(p.MTw * p.NTw * p.splits);
+    if (debug_plan())
+      fprintf(stderr, "[bdv plan] wgrad %dx%d Cin %d Cout %d k%d s%d: tiles %d -> splits %d x %d k-iters (%s)\n", gg->H, gg->W,
+              gg->Cin, gg->Cout, gg->R, gg->stride, p.MTw * p.NTw, p.splits, p.kt_per_split, p.small ? "64x64" : "128x128");
+    static_index<2>(incr, [&](auto ic) {
+      constexpr bool INCR = decltype(ic)::value != 0;
+      if (!p.small)
+        hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 2, 2, false, INCR>), grid, dim3(256), 0, s, dyf, xf, (float*)slab, g, p.MTw, p.NTw, p.kt_per_split);
+      else if (p.c4)
+        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, true, INCR>), grid, dim3(256), 0, s, dyf, xf, (float*)slab, g, p.MTw, p.NTw, p.kt_per_split);
+      else
+        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, false, INCR>), grid, dim3(256), 0, s, dyf, xf, (float*)slab, g, p.MTw, p.NTw, p.kt_per_split);
+    });
+    return launch_check(who);
+  }
+  const WgradPlPlan& p = cp.wpl;
+  const bool h16 = gg->act_dtype == BDV_ACT_BF16;
+  const PieceScales ps = {cp.f16 ? amax_dy : nullptr, cp.f16 ? amax_x : nullptr};
   const dim3 grid(p.MTw * p.NTw * p.splits);
   if (debug_plan())
-    fprintf(stderr, "[bdv plan] wgrad %dx%d Cin %d Cout %d k%d s%d: tiles %d -> splits %d x %d k-iters (%s)\n", gg->H, gg->W,
-            gg->Cin, gg->Cout, gg->R, gg->stride, p.MTw * p.NTw, p.splits, p.kt_per_split, p.small ? "64x64" : "128x128");
-  const bool incr = g.Ho * g.Wo > BK && BK / g.Wo + 1 <= g.Ho;
-#define BDV_WGRAD(BMN, C4F)                                                                                                    \
-  do {                                                                                                                         \
-    if (incr)                                                                                                                  \
-      hipLaunchKernelGGL((conv_wgrad_kernel<BMN, BMN, 2, 2, C4F, true>), grid, dim3(256), 0, s, dy, x, slab, g, p.MTw, p.NTw,   \
-                         p.kt_per_split);                                                                                      \
-    else                                                                                                                       \
-      hipLaunchKernelGGL((conv_wgrad_kernel<BMN, BMN, 2, 2, C4F, false>), grid, dim3(256), 0, s, dy, x, slab, g, p.MTw, p.NTw,  \
-                         p.kt_per_split);                                                                                      \
-  } while (0)
-  if (!p.small) {
-    BDV_WGRAD(128, false);
-  } else if (p.c4) {
-    BDV_WGRAD(64, true);
-  } else {
-    BDV_WGRAD(64, false);
-  }
-#undef BDV_WGRAD
-  BDV_LAUNCH_CHECK(who);
-  *splits_out = p.splits;
-  return BDV_OK;
+    fprintf(stderr, "[bdv plan] wgrad_pl %dx%d Cin %d Cout %d k%d s%d: %dx%d tiles %d -> splits %d x %d k-iters\n", gg->H, gg->W, gg->Cin,
+            gg->Cout, gg->R, gg->stride, p.BM, p.BN, p.MTw * p.NTw, p.splits, p.kt_per_split);
+  // the two-stage loop where the tile has one, unless BDVCIL_WGRAD_2STAGE=0; never with bf16 tensors (a 16-pixel stage is half a
+  // 16-byte unit per thread): no bf16-storage kernel is instantiated with KW = 16
+  const int two_stage = kWgradTiles[p.tile].two_stage && wgrad_two_stage() && !h16;
+  const int variant = pl_arith(cp, gg, arith, false);   // (the producer's BatchNorm is a run-time argument of this kernel)
+  bool launched = false;
+  static_index<kNumWgradTiles>(p.tile, [&](auto tile) {
+    constexpr WgradTile k = kWgradTiles[decltype(tile)::value];
+    static_index<kNumPlAriths>(variant, [&](auto ar) {
+      constexpr int A = decltype(ar)::value;
+      constexpr PlArith a = kPlAriths[A];
+      static_index<4>(2 * two_stage + incr, [&](auto loop) {
+        constexpr bool INCR = decltype(loop)::value % 2 != 0, TWO = decltype(loop)::value / 2 != 0;
+        if constexpr (!a.pre && (!TWO || (k.two_stage && a.ES == 4))) {
+          launched = true;
+          hipLaunchKernelGGL((conv_wgrad_pl_kernel<k.BM, k.BN, k.WM, k.WN, INCR, a.NP, k.MTAP, TWO ? 16 : 32, a.ES, PlPieces<A>>), grid,
+                             dim3(64 * k.WM * k.WN), 0, s, dy, x, (float*)slab, g, p.MTw, p.NTw, p.kt_per_split, pre_scale, pre_shift, ps);
+        }
+      });
+    });
+  });
+  BDV_REQUIRE(launched, "%s: no kernel is compiled for tile %d, variant %d", who, p.tile, variant);
+  return launch_check(who);
 }
-
 }  // namespace
 
 extern "C" int bdv_conv_wgrad(const float* dy, const float* x, float* dw, float beta, const bdv_conv_geom* gg,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  const ConvPlan cp = plan_conv(gg, kWgrad, 0, false);
-  if (cp.family < 0) return BDV_EINVAL;
-  BDV_REQUIRE(dy && x && dw && workspace, "bdv_conv_wgrad: null pointer");
-  BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(x) && bdv_aligned16(dw) && bdv_aligned16(workspace),
-              "bdv_conv_wgrad: pointers must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
+  BDV_REQUIRE(dw != nullptr, "bdv_conv_wgrad: null pointer");
+  BDV_REQUIRE(bdv_aligned16(dw), "bdv_conv_wgrad: pointers must be 16-byte aligned");
   int splits = 0;
-  if (int e = wgrad_partial("bdv_conv_wgrad", dy, x, gg, workspace, workspace_bytes, s, &splits, cp)) return e;
+  if (int e = conv_wgrad_partial_launch("bdv_conv_wgrad", dy, x, gg, workspace, workspace_bytes, 0, nullptr, nullptr, nullptr, nullptr, stream,
+                                        &splits))
+    return e;
   const int64_t numel4 = (int64_t)gg->Cout * gg->R * gg->S * gg->Cin / 4;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((int)((numel4 + 63) / 64)), dim3(256), 0, s, (const float*)workspace, dw, beta, splits,
-                     numel4);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((int)((numel4 + 63) / 64)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dw, beta,
+                     splits, numel4);
   BDV_LAUNCH_CHECK("bdv_conv_wgrad(reduce)");
   return BDV_OK;
 }
 
 extern "C" int bdv_conv_wgrad_partial(const float* dy, const float* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes,
                                       void* stream) {
-  const ConvPlan cp = plan_conv(gg, kWgrad, 0, false);
-  if (cp.family < 0) return BDV_EINVAL;
-  BDV_REQUIRE(dy && x && slab, "bdv_conv_wgrad_partial: null pointer");
-  BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(x) && bdv_aligned16(slab), "bdv_conv_wgrad_partial: pointers must be 16-byte aligned");
-  int splits = 0;
-  return wgrad_partial("bdv_conv_wgrad_partial", dy, x, gg, slab, slab_bytes, (hipStream_t)stream, &splits, cp);
+  return conv_wgrad_partial_launch("bdv_conv_wgrad_partial", dy, x, gg, slab, slab_bytes, 0, nullptr, nullptr, nullptr, nullptr, stream);
 }
-
-namespace {
-int conv_wgrad_partial_pl_impl(const void* dy, const void* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes, int pieces,
-                               const float* pre_scale, const float* pre_shift, const unsigned* amax_dy, const unsigned* amax_x,
-                               void* stream) {
-  const ConvPlan cp = plan_conv(gg, kWgrad, pieces, pre_scale != nullptr);
-  if (cp.family < 0) return BDV_EINVAL;
-  if (pieces == kArithF16x2 && !cp.f16) pieces = 3;
-  const PieceScales ps = {cp.f16 ? amax_dy : nullptr, cp.f16 ? amax_x : nullptr};
-  BDV_REQUIRE(!cp.f16 || (amax_dy != nullptr && amax_x != nullptr), "bdv_conv_wgrad_partial_f16x2: null pointer (amax_dy, amax_x)");
-  BDV_REQUIRE(pre_scale == nullptr || pre_shift != nullptr, "bdv_conv_wgrad_partial_pl: pre_scale without pre_shift");
-  BDV_REQUIRE(dy && x && slab, "bdv_conv_wgrad_partial_pl: null pointer");
-  BDV_REQUIRE(bdv_aligned16(dy) && bdv_aligned16(x) && bdv_aligned16(slab), "bdv_conv_wgrad_partial_pl: pointers must be 16-byte aligned");
-  const bool h16 = gg->act_dtype == BDV_ACT_BF16;
-  if (cp.family != BDV_CONV_WGRAD_PL) {
-    int splits = 0;
-    return wgrad_partial("bdv_conv_wgrad_partial_pl", (const float*)dy, (const float*)x, gg, slab, slab_bytes, (hipStream_t)stream, &splits, cp);
-  }
-  const WgradPlPlan& p = cp.wpl;
-  const size_t need = (size_t)p.splits * gg->Cout * (gg->Rt > 1 ? gg->Rt : 1) * gg->R * gg->S * gg->Cin * sizeof(float);
-  if (slab_bytes < need) {
-    bdv_set_error("bdv_conv_wgrad_partial_pl: slab %zu < required %zu bytes", slab_bytes, need);
-    return BDV_EWORKSPACE;
-  }
-  Geom g = make_geom(gg);
-  g.M = g.N * g.Ho * g.Wo;
-  g.Ktot = g.Rt * g.R * g.S * g.Cin;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(p.MTw * p.NTw * p.splits);
-  if (debug_plan())
-    fprintf(stderr, "[bdv plan] wgrad_pl %dx%d Cin %d Cout %d k%d s%d: %dx%d tiles %d -> splits %d x %d k-iters\n", gg->H, gg->W, gg->Cin,
-            gg->Cout, gg->R, gg->stride, p.BM, p.BN, p.MTw * p.NTw, p.splits, p.kt_per_split);
-  const bool incr = g.Ho * g.Wo > BK && BK / g.Wo + 1 <= g.Ho;
-#define BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, INCR_, NP_, MTAP_, KW_, ES_)                                                                \
-  hipLaunchKernelGGL((conv_wgrad_pl_kernel<BM_, BN_, WM_, WN_, INCR_, NP_, MTAP_, KW_, ES_>), grid, dim3(64 * WM_ * WN_), 0, s, dy, x, \
-                     (float*)slab, g, p.MTw, p.NTw, p.kt_per_split, pre_scale, pre_shift, ps)
-#define BDV_WGRAD_F16(BM_, BN_, WM_, WN_, INCR_, MTAP_, KW_)                                                                        \
-  hipLaunchKernelGGL((conv_wgrad_pl_kernel<BM_, BN_, WM_, WN_, INCR_, 2, MTAP_, KW_, 4, F16Pieces>), grid, dim3(64 * WM_ * WN_), 0, s, \
-                     dy, x, (float*)slab, g, p.MTw, p.NTw, p.kt_per_split, pre_scale, pre_shift, ps)
-#define BDV_WGRAD_PL(BM_, BN_, WM_, WN_, MTAP_, KW_)                                                                             \
-  do {                                                                                                                           \
-    if (cp.f16 && incr) BDV_WGRAD_F16(BM_, BN_, WM_, WN_, true, MTAP_, KW_);                                                     \
-    else if (cp.f16) BDV_WGRAD_F16(BM_, BN_, WM_, WN_, false, MTAP_, KW_);                                                       \
-    else if (h16 && incr) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, true, 1, MTAP_, (KW_ == 16 ? 32 : KW_), 2);                          \
-    else if (h16) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, false, 1, MTAP_, (KW_ == 16 ? 32 : KW_), 2);                                 \
-    else if (incr && pieces == 3) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, true, 3, MTAP_, KW_, 4);                                     \
-    else if (pieces == 3) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, false, 3, MTAP_, KW_, 4);                                            \
-    else if (incr && pieces == 2) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, true, 2, MTAP_, KW_, 4);                                     \
-    else if (pieces == 2) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, false, 2, MTAP_, KW_, 4);                                            \
-    else if (incr) BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, true, 1, MTAP_, KW_, 4);                                                    \
-    else BDV_WGRAD_PL2(BM_, BN_, WM_, WN_, false, 1, MTAP_, KW_, 4);                                                             \
-  } while (0)
-  const bool two_stage = wgrad_two_stage() && !h16;   // (bf16 tensors: a 16-pixel stage is half a 16-byte unit per thread)
-  if (p.form == 1) BDV_WGRAD_PL(64, 192, 2, 2, true, 32);
-  else if (p.form == 2) BDV_WGRAD_PL(64, 64, 2, 2, false, 32);
-  else if (p.form == 3) BDV_WGRAD_PL(256, 64, 4, 1, false, 32);
-  else if (p.form == 4) BDV_WGRAD_PL(64, 256, 1, 4, false, 32);
-  else if (p.form == 5) BDV_WGRAD_PL(64, 256, 1, 4, true, 32);
-  else if (p.BM == 256 && p.BN == 256) BDV_WGRAD_PL(256, 256, 2, 4, false, 32);   // two register sets would spill here (128 accumulators)
-  else if (p.BM == 256 && two_stage) BDV_WGRAD_PL(256, 128, 2, 4, false, 16);
-  else if (p.BM == 256) BDV_WGRAD_PL(256, 128, 2, 4, false, 32);
-  else if (p.BN == 256 && two_stage) BDV_WGRAD_PL(128, 256, 2, 4, false, 16);
-  else if (p.BN == 256) BDV_WGRAD_PL(128, 256, 2, 4, false, 32);
-  else BDV_WGRAD_PL(128, 128, 2, 4, false, 32);
-#undef BDV_WGRAD_PL
-#undef BDV_WGRAD_F16
-#undef BDV_WGRAD_PL2
-  BDV_LAUNCH_CHECK("bdv_conv_wgrad_partial_pl");
-  return BDV_OK;
-}
-}  // namespace
 
 extern "C" int bdv_conv_wgrad_partial_pl(const void* dy, const void* x, const bdv_conv_geom* gg, void* slab, size_t slab_bytes,
                                          int pieces, const float* pre_scale, const float* pre_shift, void* stream) {
   BDV_REQUIRE(pieces >= 1 && pieces <= 3, "bdv_conv_wgrad_partial_pl: pieces = %d (3, 2 or 1)", pieces);
-  return conv_wgrad_partial_pl_impl(dy, x, gg, slab, slab_bytes, pieces, pre_scale, pre_shift, nullptr, nullptr, stream);
+  return conv_wgrad_partial_launch("bdv_conv_wgrad_partial_pl", dy, x, gg, slab, slab_bytes, pieces, pre_scale, pre_shift, nullptr, nullptr,
+                                   stream);
 }
 
 extern "C" int bdv_conv_wgrad_partial_f16x2(const void* dy, const void* amax_dy, const void* x, const void* amax_x,
                                             const bdv_conv_geom* gg, void* slab, size_t slab_bytes, const float* pre_scale,
                                             const float* pre_shift, void* stream) {
-  return conv_wgrad_partial_pl_impl(dy, x, gg, slab, slab_bytes, kArithF16x2, pre_scale, pre_shift, (const unsigned*)amax_dy,
-                                    (const unsigned*)amax_x, stream);
+  return conv_wgrad_partial_launch("bdv_conv_wgrad_partial_f16x2", dy, x, gg, slab, slab_bytes, kArithF16x2, pre_scale, pre_shift,
+                                   (const unsigned*)amax_dy, (const unsigned*)amax_x, stream);
 }
 
 // ---- fp16 pieces: amax word of a tensor, planes of a weight ------------------------------------------------------------------
