@@ -7,6 +7,10 @@ Restates, in plain torch on the CPU, the reference arithmetic that ``csrc/repr.h
 * ``class_means``         libs/cil/cil.py:1079-1083
 * ``herding_select``      libs/cil/memory_selection.py:70-92 (greedy loop) and :150-164 (calc_mean_features)
 
+Every function computes in the dtype of its inputs: fp32 inputs give the reference's own arithmetic, fp64 inputs the high-precision
+restatement that tests/test_repr_edges_gpu.py holds the kernels against (``herding_margin`` / ``argmax_margin`` say how far a selection
+is from flipping; ``softmax_mean`` / ``topk_hit_counts`` restate the two evaluation kernels of csrc/head_loss.hip).
+
 Pinning: ``herding_select`` is checked against ``tests/golden/herding_golden.npz``, produced by the reference's own
 ``Herding.construct_exemplar`` (tests/golden/make_golden_herding.py).  The three cil.py snippets live inside a
 LightningModule that cannot be imported here (pytorch_lightning / mmaction absent): they are a handful of torch calls
@@ -55,8 +59,9 @@ def _remove_row(t: torch.Tensor, idx) -> torch.Tensor:
     return t[keep]
 
 
-def herding_select(features: torch.Tensor, num_exemplars: int, cosine_distance: bool):
-    """features (n, dims) of one class -> (class_mean (1, dims), indices, dist)."""
+def herding_trace(features: torch.Tensor, num_exemplars: int, cosine_distance: bool):
+    """The greedy loop in the dtype of ``features`` -> (class_mean (1, dims), indices, dist, steps); ``steps[i]`` holds the distances
+    of every row still available at step i, ascending."""
     if cosine_distance:
         normalized = F.normalize(features, p=2, dim=-1)
     else:
@@ -64,8 +69,8 @@ def herding_select(features: torch.Tensor, num_exemplars: int, cosine_distance: 
     mean = features.view(-1, features.size(-1)).mean(0, keepdim=True)
     class_mean = F.normalize(mean, p=2) if cosine_distance else mean
     indexer = torch.arange(features.size(0))
-    moving = torch.zeros(1, features.size(-1))
-    indices, dists = [], []
+    moving = torch.zeros(1, features.size(-1), dtype=features.dtype)
+    indices, dists, steps = [], [], []
     for n in range(1, num_exemplars + 1):
         tmp = moving * (n - 1) / n + normalized / n
         if cosine_distance:
@@ -76,9 +81,50 @@ def herding_select(features: torch.Tensor, num_exemplars: int, cosine_distance: 
         moving = moving * (n - 1) / n + normalized[row] / n
         indices.append(indexer[row].item())
         dists.append(dist[row].item())
+        steps.append(torch.sort(dist).values)
         normalized = _remove_row(normalized, row)
         indexer = _remove_row(indexer, row)
-    return class_mean, indices, dists
+    return class_mean, indices, dists, steps
+
+
+def herding_select(features: torch.Tensor, num_exemplars: int, cosine_distance: bool):
+    """features (n, dims) of one class -> (class_mean (1, dims), indices, dist), in the dtype of ``features``."""
+    return herding_trace(features, num_exemplars, cosine_distance)[:3]
+
+
+def herding_margin(features: torch.Tensor, num_exemplars: int, cosine_distance: bool, distinct: bool = False):
+    """fp64: (smallest gap between the best and the second-best distance over all greedy steps, largest selected distance).  A step
+    with one row left has no runner-up and does not count.  ``distinct``: the runner-up is the nearest row at a *different*
+    distance, for inputs with a planted duplicate row (whose distance is bit-identical in any arithmetic)."""
+    _, _, dists, steps = herding_trace(features.double(), num_exemplars, cosine_distance)
+    gap = float('inf')
+    for d in steps:
+        rest = d[d > d[0]] if distinct else d[1:]
+        if rest.numel():
+            gap = min(gap, (rest[0] - d[0]).item())
+    return gap, max(dists, default=0.0)
+
+
+def argmax_margin(sim: torch.Tensor) -> torch.Tensor:
+    """Per row: best minus second-best value (inf for a single column)."""
+    if sim.size(1) < 2:
+        return torch.full((sim.size(0),), float('inf'), dtype=sim.dtype)
+    top = torch.topk(sim, 2, dim=1).values
+    return top[:, 0] - top[:, 1]
+
+
+def softmax_mean(s: torch.Tensor, B: int, n: int, apply_softmax: bool) -> torch.Tensor:
+    """average_clip in fp64: s (B*n, K) -> (B, K), the mean over n of the (softmaxed) rows."""
+    s = s.double().view(B, n, -1)
+    return (torch.softmax(s, dim=2) if apply_softmax else s).mean(dim=1)
+
+
+def topk_hit_counts(score, labels, ks=(1, 5)):
+    """NumPy: for each k the number of rows whose label has fewer than k classes scoring strictly higher (ties are not higher)."""
+    import numpy as np
+    score, labels = np.asarray(score), np.asarray(labels)
+    greater = (score > score[np.arange(score.shape[0]), labels][:, None]).sum(axis=1)
+    return tuple(int((greater < k).sum()) for k in ks)
 
 
 def herding_class_features(features: torch.Tensor, storing_methods: str) -> torch.Tensor:
