@@ -253,6 +253,22 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 }
 
+// the fix-up kernels' read of what store_partial wrote: the `split` slices of remainder tile `rt`, summed in slice order; all
+// loads of one slice are independent and stay in flight together
+template <int TM, int TN, int NT>
+__device__ __forceinline__ void load_partials(const float* __restrict__ slab, int rt, int split, f32x16 (&acc)[TM][TN], int tid) {
+  zero_acc<TM, TN>(acc);
+  for (int sl = 0; sl < split; ++sl) {
+    const float* src = slab + (size_t)(rt * split + sl) * (TM * TN * 16) * NT + tid;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][j][e] += src[(size_t)((i * TN + j) * 16 + e) * NT];
+  }
+}
+
 __device__ __forceinline__ void fprop_store(float* __restrict__ y, const Geom& g, int row, int col, float v) {
   if (row < g.M) y[(size_t)row * g.Cout + col] = v;
 }
@@ -627,113 +643,11 @@ __device__ __forceinline__ void fprop_epilogue(const f32x16 (&acc)[BM / WM / 32]
   }
 }
 
-// =========================================================================================
-// fprop: y[m, co] = sum_{tap, ci} x_shift[n, ho*st + r - p, wo*st + s - p, ci] * w[co, tap, ci]
-// K order is tap-fastest: the R*S taps of one 32-channel chunk are consecutive K-steps, so the shifted re-reads of
-// the same activation rows hit L1/L2 instead of going back to the fabric R*S times.
-// =========================================================================================
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256, 3) void conv_fprop_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                          float* __restrict__ y, Geom g, int NT, Work wk,
-                                                          float* __restrict__ slab, FpropEpi epi) {
-  constexpr int LDA = BM, LDB = BN;
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int AP = BM / 32, BP = BN / 32;
-  __shared__ __attribute__((aligned(16))) float smem[BK * (LDA + LDB)];
-  float* const As = smem;
-  float* const Bs = smem + BK * LDA;
-
-  // Tile order: Cout-tile fastest, so the blocks that share an activation row-tile are consecutive and
-  // (through xcd_remap) land on one XCD / one L2.
-  const int nk = g.Ktot / BK;
-  const WorkItem it = get_work(blockIdx.x, wk, nk);
-  const int mt = it.tile / NT, nt = it.tile - mt * NT;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm0 = (wave / WN) * 32, wn0 = (wave % WN) * 32;  // tile i / j of the wave: + 32*WM*i / + 32*WN*j
-  const int arow = tid >> 3, kg = tid & 7;
-  const int HoWo = g.Ho * g.Wo;
-  const int frame_bytes = g.H * g.W * g.Cin * 4;
-
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, g.N * frame_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, g.Cout * g.Ktot * 4, 0x00020000);
-
-  int a_base[AP], a_t[AP], a_hi0[AP], a_wi0[AP];
-#pragma unroll
-  for (int p = 0; p < AP; ++p) {
-    const int m = mt * BM + arow + 32 * p;
-    const bool ok = m < g.M;
-    int n, rem, ho, wo;
-    fast_divmod(ok ? m : 0, HoWo, g.rcp_HoWo, n, rem);
-    fast_divmod(rem, g.Wo, g.rcp_Wo, ho, wo);
-    a_t[p] = n % g.T;
-    a_hi0[p] = ok ? ho * g.stride - g.pad : -(1 << 20);  // rows past M fail every bounds test
-    a_wi0[p] = wo * g.stride - g.pad_w;
-    a_base[p] = ((n * g.H + ho * g.stride - g.pad) * g.W + wo * g.stride - g.pad_w) * g.Cin * 4 + 16 * kg;
-  }
-  int b_base[BP];
-#pragma unroll
-  for (int p = 0; p < BP; ++p) b_base[p] = ((nt * BN + arow + 32 * p) * g.Ktot + 4 * kg) * 4;
-
-  // K index state (uniform): K-step kt = chunk * R*S + r * S + s
-  const int RS = g.R * g.S;
-  int chunk = it.kb / RS, r, s;
-  {
-    const int tap = it.kb - chunk * RS;
-    r = tap / g.S;
-    s = tap - r * g.S;
-  }
-
-  float4 ra[AP], rb[BP];
-  auto load = [&]() {
-    const int cls = shift_class(chunk * BK + 4 * kg, g.fold);
-    const int koff_a = ((r * g.W + s) * g.Cin + chunk * BK) * 4;
-    const int koff_b = ((r * g.S + s) * g.Cin + chunk * BK) * 4;
-#pragma unroll
-    for (int p = 0; p < AP; ++p) {
-      const bool v = (unsigned)(a_hi0[p] + r) < (unsigned)g.H && (unsigned)(a_wi0[p] + s) < (unsigned)g.W &&
-                     (unsigned)(a_t[p] + cls) < (unsigned)g.T;
-      // invalid lanes: set the top bit -> beyond num_records -> the load returns zeros
-      ra[p] = buf_load16(xr, (a_base[p] + koff_a + cls * frame_bytes) | (v ? 0 : kOOB), 0);
-    }
-#pragma unroll
-    for (int p = 0; p < BP; ++p) rb[p] = buf_load16(wr, b_base[p], koff_b);
-    // advance to the next K-step (branch-free)
-    s += 1;
-    const int ws_ = (s == g.S) ? 1 : 0;
-    s = ws_ ? 0 : s;
-    r += ws_;
-    const int wr_ = (r == g.R) ? 1 : 0;
-    r = wr_ ? 0 : r;
-    chunk += wr_;
-  };
-
-  f32x16 acc[TM][TN];
-  zero_acc<TM, TN>(acc);
-
-  load();
-  for (int kt = it.kb; kt < it.ke; ++kt) {
-    __syncthreads();  // everyone is done reading the previous stage
-    store_transposed<LDA, AP>(As, ra, tid);
-    store_transposed<LDB, BP>(Bs, rb, tid);
-    __syncthreads();
-    if (kt + 1 < it.ke) load();  // in flight during the MFMAs
-    mma_stage<LDA, LDB, TM, TN, 32 * WM, 32 * WN, true, true>(As, Bs, acc, wm0, wn0, lane);
-  }
-
-  if (it.pslot >= 0) {
-    store_partial<TM, TN>(slab, it.pslot, acc, tid);
-    return;
-  }
-  fprop_epilogue<BM, BN, WM, WN>(acc, smem, y, g, epi, mt, nt, tid);
-}
-
-// ---- experimental: fp32 products from bf16 pieces -------------------------------------------------
-// Same implicit GEMM, loader, work planner and epilogue as conv_fprop_kernel; only the K loop differs: every fp32 operand
-// value is split in registers into three round-to-nearest bf16 pieces (hi + mid + lo = 24 significand bits), the pieces go
-// to LDS as k-contiguous rows, and each 16-deep step accumulates the six piece products of relative weight >= 2^-16 with
-// v_mfma_f32_32x32x16_bf16 (smallest first).  The dropped products are below 2^-24 relative, the order of fp32 rounding.
+// ---- fp32 products from bf16 pieces in the four-wave kernels ---------------------------------------
+// Every fp32 operand value is split in registers into three round-to-nearest bf16 pieces (hi + mid + lo = 24 significand
+// bits), the pieces go to LDS as k-contiguous rows, and each 16-deep step accumulates the six piece products of relative
+// weight >= 2^-16 with v_mfma_f32_32x32x16_bf16 (smallest first).  The dropped products are below 2^-24 relative, the order
+// of fp32 rounding.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 constexpr int X3_LDK = BK + 8;  // bf16 per LDS row: 80 bytes, the 16-byte fragment reads of 16 lanes cover all banks once
 
@@ -806,19 +720,173 @@ __device__ __forceinline__ void mma_stage_x3(const unsigned short* __restrict__ 
   }
 }
 
-// BPRE: w points at the F planes of bdv_conv_split_weights instead of the fp32 weights: the weight tile of a K-step is then
-// three contiguous blocks of 64-byte rows, loaded with 16-byte loads and stored as they are (no split VALU for that operand).
-template <int BM, int BN, int WM, int WN, bool BPRE = false>
-__global__ __launch_bounds__(256, 2) void conv_fprop_x3_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                          float* __restrict__ y, Geom g, int NT, Work wk,
-                                                          float* __restrict__ slab, FpropEpi epi) {
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int AP = BM / 32, BP = BN / 32;
-  static_assert(3 * (BM + BN) * X3_LDK * 2 >= WM * 32 * BN * 4, "the epilogue stages a tile pass in the same LDS");
-  __shared__ __attribute__((aligned(16))) unsigned short smem16[3 * (BM + BN) * X3_LDK];
-  unsigned short* const As = smem16;
-  unsigned short* const Bs = smem16 + 3 * BM * X3_LDK;
-  float* const smem = reinterpret_cast<float*>(smem16);
+// ---- stage policies of the four-wave kernels ------------------------------------------------------------------------------
+// A fp32-MFMA kernel and its bf16-piece twin are one tile body (fprop_tile, stem_tile, dgrad_tile).  A policy holds what differs:
+// the LDS image of a K-step (which also stages a pass of the epilogues: WM * 32 rows of BN floats), the registers of the weight
+// tile with their addressing, load and store, the MFMA stage, and the workgroups per CU the image leaves room for (kOcc, the
+// kernels' __launch_bounds__).  The activation tile is the same in both: a thread's 16-byte loads are row tid / 8 + 32 p,
+// K-group tid % 8.
+
+// fp32 MFMA.  BT: the weight tile arrives K-contiguous (rows of `ld` elements: fprop, transposing store); else as 32 K-rows, `ld`
+// elements apart, of BN contiguous columns (dgrad, direct store).
+template <int BM_, int BN_, int WM_, int WN_, bool BT>
+struct F32Stage {
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
+  static constexpr int kOcc = 3;
+  static constexpr bool kPlanes = false;
+  static constexpr int TM = BM / WM / 32, TN = BN / WN / 32, AP = BM / 32, NB = BN / 32;
+  static constexpr int LDA = BM, LDB = BN;
+  static constexpr int AOFF = (BK * LDA + 3) & ~3;  // keep the B image 16-byte aligned
+  static constexpr int kSmemFloats = (AOFF + BK * LDB) > (WM * 32 * BN) ? (AOFF + BK * LDB) : (WM * 32 * BN);
+  using BRegs = float4[NB];
+  static __device__ __forceinline__ int weight_bytes(int elems) { return elems * 4; }
+  static __device__ __forceinline__ void init_b(int (&b_base)[NB], int nt, int tid, int ld) {
+#pragma unroll
+    for (int p = 0; p < NB; ++p) {
+      if constexpr (BT) {
+        b_base[p] = ((nt * BN + (tid >> 3) + 32 * p) * ld + 4 * (tid & 7)) * 4;
+      } else {
+        const int idx = tid + 256 * p;
+        const int krow = idx / (BN / 4), c4 = idx - krow * (BN / 4);
+        b_base[p] = (krow * ld + nt * BN + 4 * c4) * 4;
+      }
+    }
+  }
+  static __device__ __forceinline__ void load_b(BRegs& rb, __amdgpu_buffer_rsrc_t wr, const int (&b_base)[NB], int soff, int) {
+#pragma unroll
+    for (int p = 0; p < NB; ++p) rb[p] = buf_load16(wr, b_base[p], soff);
+  }
+  static __device__ __forceinline__ void store(float* __restrict__ smem, const float4 (&ra)[AP], const BRegs& rb, int tid) {
+    store_transposed<LDA, AP>(smem, ra, tid);
+    if constexpr (BT) store_transposed<LDB, NB>(smem + AOFF, rb, tid);
+    else store_direct<LDB, BN, NB>(smem + AOFF, rb, tid);
+  }
+  static __device__ __forceinline__ void mma(const float* __restrict__ smem, f32x16 (&acc)[TM][TN], int wm0, int wn0, int lane) {
+    mma_stage<LDA, LDB, TM, TN, 32 * WM, 32 * WN, true, BT>(smem, smem + AOFF, acc, wm0, wn0, lane);
+  }
+};
+
+// Three bf16 pieces per operand.  PLANES: the weight tile comes from the planes of bdv_conv_split_weights (F planes for fprop, D
+// planes for dgrad): per piece a contiguous block of 64-byte rows, loaded with 16-byte loads (row tid / 4 + 64 q, chunk tid % 4)
+// and stored as it is, so no split VALU is spent on that operand.  Else (the stem) the fp32 weights are split in the loader like
+// the activations; the stem addresses them by filter tap, without init_b / load_b.
+template <int BM_, int BN_, int WM_, int WN_, bool PLANES>
+struct X3Stage {
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
+  static constexpr int kOcc = 2;
+  static constexpr bool kPlanes = PLANES;
+  static constexpr int TM = BM / WM / 32, TN = BN / WN / 32, AP = BM / 32;
+  static constexpr int BQ = BN * 4 / 256;  // PLANES: 16-byte loads per plane and thread
+  static constexpr int NB = PLANES ? BQ : BN / 32;
+  static constexpr int kSmemFloats = 3 * (BM + BN) * X3_LDK / 2;
+  static_assert(kSmemFloats >= WM * 32 * BN, "the epilogue stages a tile pass in the same LDS");
+  using BRegs = std::conditional_t<PLANES, u32x4[3 * BQ], float4[BN / 32]>;
+  static __device__ __forceinline__ int weight_bytes(int elems) { return PLANES ? 3 * elems * 2 : elems * 4; }
+  static __device__ __forceinline__ void init_b(int (&b_base)[NB], int nt, int tid, int) {
+    static_assert(PLANES, "only the planes are addressed by (row, K-step)");
+#pragma unroll
+    for (int q = 0; q < BQ; ++q) b_base[q] = (nt * BN + (tid >> 2) + 64 * q) * 64 + 16 * (tid & 3);
+  }
+  static __device__ __forceinline__ void load_b(BRegs& rb, __amdgpu_buffer_rsrc_t wr, const int (&b_base)[NB], int soff, int plane_bytes) {
+    static_assert(PLANES, "only the planes are addressed by (row, K-step)");
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+      for (int q = 0; q < BQ; ++q) rb[pl * BQ + q] = __builtin_amdgcn_raw_buffer_load_b128(wr, b_base[q] + pl * plane_bytes, soff, 0);
+  }
+  static __device__ __forceinline__ void store(float* __restrict__ smem, const float4 (&ra)[AP], const BRegs& rb, int tid) {
+    unsigned short* const As = reinterpret_cast<unsigned short*>(smem);
+    unsigned short* const Bs = As + 3 * BM * X3_LDK;
+    store_split3<BM, AP>(As, ra, tid);
+    if constexpr (PLANES) {
+      const int brow = tid >> 2, bc = tid & 3;
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+        for (int q = 0; q < BQ; ++q) *reinterpret_cast<u32x4*>(Bs + (pl * BN + brow + 64 * q) * X3_LDK + 8 * bc) = rb[pl * BQ + q];
+    } else {
+      store_split3<BN, BN / 32>(Bs, rb, tid);
+    }
+  }
+  static __device__ __forceinline__ void mma(const float* __restrict__ smem, f32x16 (&acc)[TM][TN], int wm0, int wn0, int lane) {
+    const unsigned short* const As = reinterpret_cast<const unsigned short*>(smem);
+    mma_stage_x3<TM, TN, 32 * WM, 32 * WN, BM, BN>(As, As + 3 * BM * X3_LDK, acc, wm0, wn0, lane);
+  }
+};
+
+// =========================================================================================
+// fprop: y[m, co] = sum_{tap, ci} x_shift[n, ho*st + r - p, wo*st + s - p, ci] * w[co, tap, ci]
+// K order is tap-fastest: the R*S taps of one 32-channel chunk are consecutive K-steps, so the shifted re-reads of
+// the same activation rows hit L1/L2 instead of going back to the fabric R*S times.
+// =========================================================================================
+
+// One activation row (output pixel m) of a thread of the Cin % 32 == 0 kernels: its frame in the clip (temporal shift), the input
+// pixel of filter tap (0, 0) for the bounds tests, and the byte offset of that pixel's 16-byte group kg (ES bytes per element).
+// The callers loop over their passes (the rows of a pass are 32 apart in the four-wave kernels, NTHR / KG in the plane kernels).
+template <int ES>
+__device__ __forceinline__ void fprop_row(const Geom& g, int m, int kg, int& a_base, int& a_t, int& a_hi0, int& a_wi0) {
+  const int HoWo = g.Ho * g.Wo;
+  const bool ok = m < g.M;
+  int n, rem, ho, wo;
+  fast_divmod(ok ? m : 0, HoWo, g.rcp_HoWo, n, rem);
+  fast_divmod(rem, g.Wo, g.rcp_Wo, ho, wo);
+  a_t = n % g.T;
+  a_hi0 = ok ? ho * g.stride - g.pad : -(1 << 20);  // rows past M fail every bounds test
+  a_wi0 = wo * g.stride - g.pad_w;
+  a_base = ((n * g.H + ho * g.stride - g.pad) * g.W + wo * g.stride - g.pad_w) * g.Cin * ES + 16 * kg;
+}
+
+// The stem's rows (Cin = 4 on NHWC4: a pixel is one 16-byte load; up to 2^23 output pixels: exact integer division), 32 apart.
+// TAPS: temporal taps; a_t0 is then the input frame (in its clip) that temporal tap 0 reads.
+template <bool TAPS, int AP>
+__device__ __forceinline__ void stem_rows(const Geom& g, int m0, int (&a_base)[AP], int (&a_hi0)[AP], int (&a_wi0)[AP],
+                                          int (&a_t0)[AP]) {
+  const int HoWo = g.Ho * g.Wo;
+  const int pad_t = g.Rt / 2;
+#pragma unroll
+  for (int p = 0; p < AP; ++p) {
+    const int m = m0 + 32 * p;
+    const bool ok = m < g.M;
+    const int mm = ok ? m : 0;
+    const int n = mm / HoWo;
+    const int rem = mm - n * HoWo;
+    const int ho = rem / g.Wo, wo = rem - ho * g.Wo;
+    a_hi0[p] = ok ? ho * g.stride - g.pad : -(1 << 20);
+    a_wi0[p] = wo * g.stride - g.pad_w;
+    if constexpr (TAPS) a_t0[p] = (n % g.T) * g.st_t - pad_t;
+    const int frame = TAPS ? n * g.st_t - pad_t : n;
+    a_base[p] = ((frame * g.H + ho * g.stride - g.pad) * g.W + wo * g.stride - g.pad_w) * 16;
+  }
+}
+
+// K-step of the Cin % 32 == 0 kernels (uniform): kt = chunk * R*S + r * S + s
+struct FpropKStep {
+  int chunk, r, s;
+  __device__ __forceinline__ FpropKStep(const Geom& g, int kb) {
+    const int RS = g.R * g.S;
+    chunk = kb / RS;
+    const int tap = kb - chunk * RS;
+    r = tap / g.S;
+    s = tap - r * g.S;
+  }
+  __device__ __forceinline__ void advance(const Geom& g) {  // branch-free
+    s += 1;
+    const int ws_ = (s == g.S) ? 1 : 0;
+    s = ws_ ? 0 : s;
+    r += ws_;
+    const int wr_ = (r == g.R) ? 1 : 0;
+    r = wr_ ? 0 : r;
+    chunk += wr_;
+  }
+};
+
+// The four-wave forward tile for Cin % 32 == 0.  w: the fp32 weights, or (Stage::kPlanes) the F planes, stored in K-step order.
+template <class Stage>
+__device__ __forceinline__ void fprop_tile(float* __restrict__ smem, const float* __restrict__ x, const float* __restrict__ w,
+                                           float* __restrict__ y, const Geom& g, int NT, const Work& wk, float* __restrict__ slab,
+                                           const FpropEpi& epi) {
+  constexpr int BM = Stage::BM, BN = Stage::BN, WM = Stage::WM, WN = Stage::WN;
+  constexpr int TM = Stage::TM, TN = Stage::TN, AP = Stage::AP;
 
   // Tile order: Cout-tile fastest, so the blocks that share an activation row-tile are consecutive and
   // (through xcd_remap) land on one XCD / one L2.
@@ -830,74 +898,37 @@ __global__ __launch_bounds__(256, 2) void conv_fprop_x3_kernel(const float* __re
   const int lane = tid & 63, wave = tid >> 6;
   const int wm0 = (wave / WN) * 32, wn0 = (wave % WN) * 32;  // tile i / j of the wave: + 32*WM*i / + 32*WN*j
   const int arow = tid >> 3, kg = tid & 7;
-  const int HoWo = g.Ho * g.Wo;
   const int frame_bytes = g.H * g.W * g.Cin * 4;
+  const int plane_bytes = g.Cout * g.Ktot * 2;
 
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, g.N * frame_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, BPRE ? 3 * g.Cout * g.Ktot * 2 : g.Cout * g.Ktot * 4, 0x00020000);
-  constexpr int BQ = BN * 4 / 256;                    // BPRE: 16-byte loads per plane and thread
-  const int brow = tid >> 2, bc = tid & 3;
-  const int plane_bytes = g.Cout * g.Ktot * 2;
-  int kt_w = it.kb;
+  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, Stage::weight_bytes(g.Cout * g.Ktot), 0x00020000);
 
   int a_base[AP], a_t[AP], a_hi0[AP], a_wi0[AP];
 #pragma unroll
-  for (int p = 0; p < AP; ++p) {
-    const int m = mt * BM + arow + 32 * p;
-    const bool ok = m < g.M;
-    int n, rem, ho, wo;
-    fast_divmod(ok ? m : 0, HoWo, g.rcp_HoWo, n, rem);
-    fast_divmod(rem, g.Wo, g.rcp_Wo, ho, wo);
-    a_t[p] = n % g.T;
-    a_hi0[p] = ok ? ho * g.stride - g.pad : -(1 << 20);  // rows past M fail every bounds test
-    a_wi0[p] = wo * g.stride - g.pad_w;
-    a_base[p] = ((n * g.H + ho * g.stride - g.pad) * g.W + wo * g.stride - g.pad_w) * g.Cin * 4 + 16 * kg;
-  }
-  int b_base[BP];
-#pragma unroll
-  for (int p = 0; p < BP; ++p) b_base[p] = ((nt * BN + arow + 32 * p) * g.Ktot + 4 * kg) * 4;
+  for (int p = 0; p < AP; ++p) fprop_row<4>(g, mt * BM + arow + 32 * p, kg, a_base[p], a_t[p], a_hi0[p], a_wi0[p]);
+  int b_base[Stage::NB];
+  Stage::init_b(b_base, nt, tid, g.Ktot);
 
-  // K index state (uniform): K-step kt = chunk * R*S + r * S + s
-  const int RS = g.R * g.S;
-  int chunk = it.kb / RS, r, s;
-  {
-    const int tap = it.kb - chunk * RS;
-    r = tap / g.S;
-    s = tap - r * g.S;
-  }
+  FpropKStep k(g, it.kb);
+  int kt_w = it.kb;
 
-  float4 ra[AP], rb[BP];
-  u32x4 rbp[BPRE ? 3 * BQ : 1];
+  float4 ra[AP];
+  typename Stage::BRegs rb;
   auto load = [&]() {
-    const int cls = shift_class(chunk * BK + 4 * kg, g.fold);
-    const int koff_a = ((r * g.W + s) * g.Cin + chunk * BK) * 4;
-    const int koff_b = ((r * g.S + s) * g.Cin + chunk * BK) * 4;
+    const int cls = shift_class(k.chunk * BK + 4 * kg, g.fold);
+    const int koff_a = ((k.r * g.W + k.s) * g.Cin + k.chunk * BK) * 4;
+    const int koff_b = Stage::kPlanes ? kt_w * g.Cout * 64 : ((k.r * g.S + k.s) * g.Cin + k.chunk * BK) * 4;
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
-      const bool v = (unsigned)(a_hi0[p] + r) < (unsigned)g.H && (unsigned)(a_wi0[p] + s) < (unsigned)g.W &&
+      const bool v = (unsigned)(a_hi0[p] + k.r) < (unsigned)g.H && (unsigned)(a_wi0[p] + k.s) < (unsigned)g.W &&
                      (unsigned)(a_t[p] + cls) < (unsigned)g.T;
       // invalid lanes: set the top bit -> beyond num_records -> the load returns zeros
       ra[p] = buf_load16(xr, (a_base[p] + koff_a + cls * frame_bytes) | (v ? 0 : kOOB), 0);
     }
-    if (BPRE) {
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-        for (int q = 0; q < BQ; ++q)
-          rbp[pl * BQ + q] = __builtin_amdgcn_raw_buffer_load_b128(wr, (nt * BN + brow + 64 * q) * 64 + 16 * bc + pl * plane_bytes, kt_w * g.Cout * 64, 0);
-      kt_w += 1;
-    } else {
-#pragma unroll
-      for (int p = 0; p < BP; ++p) rb[p] = buf_load16(wr, b_base[p], koff_b);
-    }
-    // advance to the next K-step (branch-free)
-    s += 1;
-    const int ws_ = (s == g.S) ? 1 : 0;
-    s = ws_ ? 0 : s;
-    r += ws_;
-    const int wr_ = (r == g.R) ? 1 : 0;
-    r = wr_ ? 0 : r;
-    chunk += wr_;
+    Stage::load_b(rb, wr, b_base, koff_b, plane_bytes);
+    kt_w += 1;
+    k.advance(g);
   };
 
   f32x16 acc[TM][TN];
@@ -906,18 +937,10 @@ __global__ __launch_bounds__(256, 2) void conv_fprop_x3_kernel(const float* __re
   load();
   for (int kt = it.kb; kt < it.ke; ++kt) {
     __syncthreads();  // everyone is done reading the previous stage
-    store_split3<BM, AP>(As, ra, tid);
-    if (BPRE) {
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-        for (int q = 0; q < BQ; ++q) *reinterpret_cast<u32x4*>(Bs + (pl * BN + brow + 64 * q) * X3_LDK + 8 * bc) = rbp[pl * BQ + q];
-    } else {
-      store_split3<BN, BP>(Bs, rb, tid);
-    }
+    Stage::store(smem, ra, rb, tid);
     __syncthreads();
     if (kt + 1 < it.ke) load();  // in flight during the MFMAs
-    mma_stage_x3<TM, TN, 32 * WM, 32 * WN, BM, BN>(As, Bs, acc, wm0, wn0, lane);
+    Stage::mma(smem, acc, wm0, wn0, lane);
   }
 
   if (it.pslot >= 0) {
@@ -927,118 +950,64 @@ __global__ __launch_bounds__(256, 2) void conv_fprop_x3_kernel(const float* __re
   fprop_epilogue<BM, BN, WM, WN>(acc, smem, y, g, epi, mt, nt, tid);
 }
 
-// fprop for the stem (Cin = 4 on NHWC4): one filter tap per 16-byte load, K = R*S*4 padded to a multiple of 32
 template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256, 3) void conv_fprop_c4_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                             float* __restrict__ y, Geom g, int NT, FpropEpi epi) {
-  constexpr int LDA = BM, LDB = BN;
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int AP = BM / 32, BP = BN / 32;
-  __shared__ __attribute__((aligned(16))) float smem[BK * (LDA + LDB)];
-  float* const As = smem;
-  float* const Bs = smem + BK * LDA;
+__global__ __launch_bounds__(256, (F32Stage<BM, BN, WM, WN, true>::kOcc)) void conv_fprop_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                          float* __restrict__ y, Geom g, int NT, Work wk,
+                                                          float* __restrict__ slab, FpropEpi epi) {
+  using Stage = F32Stage<BM, BN, WM, WN, true>;
+  __shared__ __attribute__((aligned(16))) float smem[Stage::kSmemFloats];
+  fprop_tile<Stage>(smem, x, w, y, g, NT, wk, slab, epi);
+}
+
+// BPRE: w points at the F planes of bdv_conv_split_weights; no other form is compiled.
+template <int BM, int BN, int WM, int WN, bool BPRE = false>
+__global__ __launch_bounds__(256, (X3Stage<BM, BN, WM, WN, true>::kOcc)) void conv_fprop_x3_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                          float* __restrict__ y, Geom g, int NT, Work wk,
+                                                          float* __restrict__ slab, FpropEpi epi) {
+  static_assert(BPRE, "the weight operand of the bf16-piece kernels comes from the planes");
+  using Stage = X3Stage<BM, BN, WM, WN, true>;
+  __shared__ __attribute__((aligned(16))) float smem[Stage::kSmemFloats];
+  fprop_tile<Stage>(smem, x, w, y, g, NT, wk, slab, epi);
+}
+
+// The stem (Cin = 4): one filter tap per 16-byte load of either operand, K = Rt*R*S*4 padded to a multiple of 32, no K split.
+// TAPS: the filter has temporal taps, tap = (dt * R + r) * S + s.
+template <class Stage, bool TAPS>
+__device__ __forceinline__ void stem_tile(float* __restrict__ smem, const float* __restrict__ x, const float* __restrict__ w,
+                                          float* __restrict__ y, const Geom& g, int NT, const FpropEpi& epi) {
+  constexpr int BM = Stage::BM, BN = Stage::BN, WM = Stage::WM, WN = Stage::WN;
+  constexpr int TM = Stage::TM, TN = Stage::TN, AP = Stage::AP, BP = BN / 32;
   const int tile = xcd_remap(blockIdx.x, epi.MT * NT);
   const int mt = tile / NT, nt = tile - mt * NT;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm0 = (wave / WN) * 32, wn0 = (wave % WN) * 32;  // tile i / j of the wave: + 32*WM*i / + 32*WN*j
   const int arow = tid >> 3, kg = tid & 7;
-  const int HoWo = g.Ho * g.Wo;
-  const int RS = g.R * g.S;
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, g.N * g.H * g.W * 16, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, g.Cout * g.Ktot * 4, 0x00020000);
-
-  int a_base[AP], a_hi0[AP], a_wi0[AP];
-#pragma unroll
-  for (int p = 0; p < AP; ++p) {
-    const int m = mt * BM + arow + 32 * p;
-    const bool ok = m < g.M;
-    const int mm = ok ? m : 0;  // up to 2^23 output pixels here: exact integer division
-    const int n = mm / HoWo;
-    const int rem = mm - n * HoWo;
-    const int ho = rem / g.Wo, wo = rem - ho * g.Wo;
-    a_hi0[p] = ok ? ho * g.stride - g.pad : -(1 << 20);
-    a_wi0[p] = wo * g.stride - g.pad_w;
-    a_base[p] = ((n * g.H + ho * g.stride - g.pad) * g.W + wo * g.stride - g.pad_w) * 16;
-  }
-  float4 ra[AP], rb[BP];
-  auto load = [&](int kt) {
-    const int tap = kt * (BK / 4) + kg;  // this thread's filter tap
-    const int r = tap / g.S, s = tap - r * g.S;
-    const bool kv = tap < RS;
-#pragma unroll
-    for (int p = 0; p < AP; ++p) {
-      const bool v = kv && (unsigned)(a_hi0[p] + r) < (unsigned)g.H && (unsigned)(a_wi0[p] + s) < (unsigned)g.W;
-      ra[p] = buf_load16(xr, (a_base[p] + (r * g.W + s) * 16) | (v ? 0 : kOOB), 0);
-    }
-#pragma unroll
-    for (int p = 0; p < BP; ++p)
-      rb[p] = buf_load16(wr, (((nt * BN + arow + 32 * p) * g.Ktot + tap * 4) * 4) | (kv ? 0 : kOOB), 0);
-  };
-  f32x16 acc[TM][TN];
-  zero_acc<TM, TN>(acc);
-  const int nk = (g.Ktot + BK - 1) / BK;
-  load(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    __syncthreads();
-    store_transposed<LDA, AP>(As, ra, tid);
-    store_transposed<LDB, BP>(Bs, rb, tid);
-    __syncthreads();
-    if (kt + 1 < nk) load(kt + 1);
-    mma_stage<LDA, LDB, TM, TN, 32 * WM, 32 * WN, true, true>(As, Bs, acc, wm0, wn0, lane);
-  }
-  fprop_epilogue<BM, BN, WM, WN>(acc, smem, y, g, epi, mt, nt, tid);
-}
-
-// The stem in the bf16-piece arithmetic: loader of conv_fprop_c4_kernel, K loop of conv_fprop_x3_kernel (both operands are
-// split in the loader; a thread's 16-byte load is one filter tap = 4 consecutive K-values, which is store_split3's mapping).
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256, 2) void conv_fprop_c4_x3_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                   float* __restrict__ y, Geom g, int NT, FpropEpi epi) {
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int AP = BM / 32, BP = BN / 32;
-  static_assert(3 * (BM + BN) * X3_LDK * 2 >= WM * 32 * BN * 4, "the epilogue stages a tile pass in the same LDS");
-  __shared__ __attribute__((aligned(16))) unsigned short smem16[3 * (BM + BN) * X3_LDK];
-  unsigned short* const As = smem16;
-  unsigned short* const Bs = smem16 + 3 * BM * X3_LDK;
-  float* const smem = reinterpret_cast<float*>(smem16);
-  const int tile = xcd_remap(blockIdx.x, epi.MT * NT);
-  const int mt = tile / NT, nt = tile - mt * NT;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm0 = (wave / WN) * 32, wn0 = (wave % WN) * 32;
-  const int arow = tid >> 3, kg = tid & 7;
-  const int HoWo = g.Ho * g.Wo;
-  const int RS = g.R * g.S, RST = RS * g.Rt;
-  const int Tin = g.T * g.st_t, pad_t = g.Rt / 2;
-  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, g.N * g.st_t * g.H * g.W * 16, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, g.Cout * g.Ktot * 4, 0x00020000);
+  const int RS = g.R * g.S, ntaps = TAPS ? RS * g.Rt : RS;
+  const int Tin = g.T * g.st_t;
+  const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, g.N * (TAPS ? g.st_t : 1) * g.H * g.W * 16, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, Stage::weight_bytes(g.Cout * g.Ktot), 0x00020000);
 
   int a_base[AP], a_hi0[AP], a_wi0[AP], a_t0[AP];
-#pragma unroll
-  for (int p = 0; p < AP; ++p) {
-    const int m = mt * BM + arow + 32 * p;
-    const bool ok = m < g.M;
-    const int mm = ok ? m : 0;  // up to 2^23 output pixels here: exact integer division
-    const int n = mm / HoWo;
-    const int rem = mm - n * HoWo;
-    const int ho = rem / g.Wo, wo = rem - ho * g.Wo;
-    a_hi0[p] = ok ? ho * g.stride - g.pad : -(1 << 20);
-    a_wi0[p] = wo * g.stride - g.pad_w;
-    a_t0[p] = (n % g.T) * g.st_t - pad_t;       // input frame (in its clip) that temporal tap 0 reads; T = 1 without temporal taps
-    a_base[p] = (((n * g.st_t - pad_t) * g.H + ho * g.stride - g.pad) * g.W + wo * g.stride - g.pad_w) * 16;
-  }
-  float4 ra[AP], rb[BP];
+  stem_rows<TAPS>(g, mt * BM + arow, a_base, a_hi0, a_wi0, a_t0);
+  float4 ra[AP];
+  typename Stage::BRegs rb;
   auto load = [&](int kt) {
-    const int tap = kt * (BK / 4) + kg;  // this thread's filter tap = (dt * R + r) * S + s
-    int dt, rs, r, s;
-    fast_divmod(tap, RS, g.rcp_RS, dt, rs);
-    fast_divmod(rs, g.S, g.rcp_S, r, s);
-    const bool kv = tap < RST;
+    const int tap = kt * (BK / 4) + kg;  // this thread's filter tap
+    int dt = 0, r, s;
+    if constexpr (TAPS) {
+      int rs;
+      fast_divmod(tap, RS, g.rcp_RS, dt, rs);
+      fast_divmod(rs, g.S, g.rcp_S, r, s);
+    } else {
+      r = tap / g.S;
+      s = tap - r * g.S;
+    }
+    const bool kv = tap < ntaps;
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
       const bool v = kv && (unsigned)(a_hi0[p] + r) < (unsigned)g.H && (unsigned)(a_wi0[p] + s) < (unsigned)g.W &&
-                     (unsigned)(a_t0[p] + dt) < (unsigned)Tin;
+                     (!TAPS || (unsigned)(a_t0[p] + dt) < (unsigned)Tin);
       ra[p] = buf_load16(xr, (a_base[p] + ((dt * g.H + r) * g.W + s) * 16) | (v ? 0 : kOOB), 0);
     }
 #pragma unroll
@@ -1051,13 +1020,30 @@ __global__ __launch_bounds__(256, 2) void conv_fprop_c4_x3_kernel(const float* _
   load(0);
   for (int kt = 0; kt < nk; ++kt) {
     __syncthreads();
-    store_split3<BM, AP>(As, ra, tid);
-    store_split3<BN, BP>(Bs, rb, tid);
+    Stage::store(smem, ra, rb, tid);
     __syncthreads();
     if (kt + 1 < nk) load(kt + 1);
-    mma_stage_x3<TM, TN, 32 * WM, 32 * WN, BM, BN>(As, Bs, acc, wm0, wn0, lane);
+    Stage::mma(smem, acc, wm0, wn0, lane);
   }
   fprop_epilogue<BM, BN, WM, WN>(acc, smem, y, g, epi, mt, nt, tid);
+}
+
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256, (F32Stage<BM, BN, WM, WN, true>::kOcc)) void conv_fprop_c4_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                             float* __restrict__ y, Geom g, int NT, FpropEpi epi) {
+  using Stage = F32Stage<BM, BN, WM, WN, true>;
+  __shared__ __attribute__((aligned(16))) float smem[Stage::kSmemFloats];
+  stem_tile<Stage, false>(smem, x, w, y, g, NT, epi);
+}
+
+// The stem in the bf16-piece arithmetic, with the temporal taps of the I3D stem: both operands are split in the loader (a
+// thread's 16-byte load is one filter tap = 4 consecutive K-values, which is store_split3's mapping).
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256, (X3Stage<BM, BN, WM, WN, false>::kOcc)) void conv_fprop_c4_x3_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                   float* __restrict__ y, Geom g, int NT, FpropEpi epi) {
+  using Stage = X3Stage<BM, BN, WM, WN, false>;
+  __shared__ __attribute__((aligned(16))) float smem[Stage::kSmemFloats];
+  stem_tile<Stage, true>(smem, x, w, y, g, NT, epi);
 }
 
 // fix-up for the K-split remainder tiles: sum the `split` partial accumulators in slice order, then the same
@@ -1067,24 +1053,12 @@ template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN) void conv_fprop_fixup_kernel(const float* __restrict__ slab, float* __restrict__ y, Geom g,
                                                                 int NT, Work wk, FpropEpi epi) {
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int NACC = TM * TN * 16;
-  constexpr int NTHR = 64 * WM * WN;
   __shared__ __attribute__((aligned(16))) float smem[WM * 32 * BN];
   const int rt = blockIdx.x, tile = wk.dp_tiles + rt;
   const int mt = tile / NT, nt = tile - mt * NT;
   const int tid = threadIdx.x;
-  // all NACC loads of one slice are independent: keep them in flight together, slices summed in order
   f32x16 acc[TM][TN];
-  zero_acc<TM, TN>(acc);
-  for (int sl = 0; sl < wk.split; ++sl) {
-    const float* src = slab + (size_t)(rt * wk.split + sl) * NACC * NTHR + tid;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] += src[(size_t)((i * TN + j) * 16 + e) * NTHR];
-  }
+  load_partials<TM, TN, 64 * WM * WN>(slab, rt, wk.split, acc, tid);
   fprop_epilogue<BM, BN, WM, WN>(acc, smem, y, g, epi, mt, nt, tid);
 }
 
@@ -1094,103 +1068,17 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fprop_fixup_kernel(const fl
 // taps whose (h+p-r) is even, so no MFMA work is spent on structural zeros.
 // epilogue: temporal un-shift (scatter to frame t+/-1) + optional masked residual-gradient add.
 // =========================================================================================
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256, 3) void conv_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w,
-                                                          float* __restrict__ dx, const float* __restrict__ add_src,
-                                                          const uint32_t* __restrict__ add_mask, Geom g, int NT, Work wk,
-                                                          float* __restrict__ slab, BnStat stat) {
-  constexpr int LDA = BM, LDB = BN;
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int AP = BM / 32, BP = BN / 32;
-  constexpr int BV = BN / 4;
-  constexpr int AOFF = (BK * LDA + 3) & ~3;  // keep the B image 16-byte aligned
-  constexpr int SMEM = (AOFF + BK * LDB) > (WM * 32 * BN) ? (AOFF + BK * LDB) : (WM * 32 * BN);
-  __shared__ __attribute__((aligned(16))) float smem[SMEM];
-  float* const As = smem;
-  float* const Bs = smem + AOFF;
 
-  // parity class of the input pixel (stride 1: a single class)
-  const int st = g.stride;
-  const int ph = blockIdx.y / st, pw = blockIdx.y - ph * st;
-  const int Hc = (g.H - ph + st - 1) / st, Wc = (g.W - pw + st - 1) / st;
-  const int Mc = g.N * Hc * Wc;
-  const int MT = (Mc + BM - 1) / BM;
-  const int r0 = (ph + g.pad) % st, s0 = (pw + g.pad_w) % st;
-  const int nr = r0 < g.R ? (g.R - r0 + st - 1) / st : 0;
-  const int ns = s0 < g.S ? (g.S - s0 + st - 1) / st : 0;
-  const int bh = (ph + g.pad - r0) / st, bw = (pw + g.pad_w - s0) / st;
-  const int ntap = nr * ns;
-  const int nk = ntap * g.Cout / BK;  // 0 for a class no filter tap reaches (e.g. 1x1 stride 2, odd pixels)
-
-  int mt, nt;
-  WorkItem it;
-  if (st == 1) {
-    it = get_work(blockIdx.x, wk, nk);
-    mt = it.tile / NT;
-    nt = it.tile - mt * NT;
-  } else {  // parity classes have different sizes: padded grid, no K split
-    const int id = blockIdx.x;
-    const int xcd = id & 7, jj = id >> 3;
-    mt = (jj / NT) * 8 + xcd;
-    nt = jj % NT;
-    if (mt >= MT) return;
-    it.tile = 0;
-    it.kb = 0;
-    it.ke = nk;
-    it.pslot = -1;
-  }
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm0 = (wave / WN) * 32, wn0 = (wave % WN) * 32;  // tile i / j of the wave: + 32*WM*i / + 32*WN*j
-  const int arow = tid >> 3, kg = tid & 7;
-  const int HcWc = Hc * Wc;
-  const int RS = g.R * g.S;
-  const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, g.N * g.Ho * g.Wo * g.Cout * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, g.Cout * RS * g.Cin * 4, 0x00020000);
-
-  int a_base[AP], a_h[AP], a_w[AP];
-#pragma unroll
-  for (int p = 0; p < AP; ++p) {
-    const int m = mt * BM + arow + 32 * p;
-    const bool ok = m < Mc;
-    const int mm = ok ? m : 0;
-    const int n = mm / HcWc;
-    const int rem = mm - n * HcWc;
-    const int hc = rem / Wc, wc = rem - hc * Wc;
-    a_h[p] = ok ? hc + bh : -(1 << 20);
-    a_w[p] = wc + bw;
-    a_base[p] = ((n * g.Ho + hc + bh) * g.Wo + wc + bw) * g.Cout * 4 + 16 * kg;
-  }
-  // weights: tile [32 co rows][BN ci] of tap `tap`: element ((co0 + krow) * RS + tap) * Cin + nt*BN + 4*c4
-  int b_base[BP];
-#pragma unroll
-  for (int p = 0; p < BP; ++p) {
-    const int idx = tid + 256 * p;
-    const int krow = idx / BV, c4 = idx - krow * BV;
-    b_base[p] = (krow * RS * g.Cin + nt * BN + 4 * c4) * 4;
-  }
-
-  // K index state (uniform): kt = chunk * ntap + ir * ns + is  (tap-fastest)
-  int chunk = ntap > 0 ? it.kb / ntap : 0, ir, is;
-  {
-    const int ct = ntap > 0 ? it.kb - chunk * ntap : 0;
+// K-step of a parity class (uniform): kt = chunk * ntap + ir * ns + is  (tap-fastest; ntap = nr * ns taps reach the class)
+struct DgradKStep {
+  int chunk, ir, is;
+  __device__ __forceinline__ DgradKStep(int kb, int ntap, int ns) {
+    chunk = ntap > 0 ? kb / ntap : 0;
+    const int ct = ntap > 0 ? kb - chunk * ntap : 0;
     ir = ns > 0 ? ct / ns : 0;
     is = ct - ir * ns;
   }
-
-  float4 ra[AP], rb[BP];
-  auto load = [&]() {
-    const int tap = (r0 + ir * st) * g.S + (s0 + is * st);
-    const int koff_a = (chunk * BK - (ir * g.Wo + is) * g.Cout) * 4;
-    const int koff_b = (chunk * BK * RS + tap) * g.Cin * 4;
-#pragma unroll
-    for (int p = 0; p < AP; ++p) {
-      const bool v = (unsigned)(a_h[p] - ir) < (unsigned)g.Ho && (unsigned)(a_w[p] - is) < (unsigned)g.Wo;
-      ra[p] = buf_load16(yr, (a_base[p] + koff_a) | (v ? 0 : kOOB), 0);
-    }
-#pragma unroll
-    for (int p = 0; p < BP; ++p) rb[p] = buf_load16(wr, b_base[p], koff_b);
+  __device__ __forceinline__ void advance(int ns, int nr) {  // branch-free
     is += 1;
     const int w1 = (is == ns) ? 1 : 0;
     is = w1 ? 0 : is;
@@ -1198,54 +1086,31 @@ __global__ __launch_bounds__(256, 3) void conv_dgrad_kernel(const float* __restr
     const int w2 = (ir == nr) ? 1 : 0;
     ir = w2 ? 0 : ir;
     chunk += w2;
-  };
-
-  f32x16 acc[TM][TN];
-  zero_acc<TM, TN>(acc);
-
-  if (it.ke > it.kb) {
-    load();
-    for (int kt = it.kb; kt < it.ke; ++kt) {
-      __syncthreads();
-      store_transposed<LDA, AP>(As, ra, tid);
-      store_direct<LDB, BN, BP>(Bs, rb, tid);
-      __syncthreads();
-      if (kt + 1 < it.ke) load();
-      mma_stage<LDA, LDB, TM, TN, 32 * WM, 32 * WN, true, false>(As, Bs, acc, wm0, wn0, lane);
-    }
   }
-  if (it.pslot >= 0) {
-    store_partial<TM, TN>(slab, it.pslot, acc, tid);
-    return;
-  }
+};
 
-  // Epilogue.  Forward read xs[frame n] = x[frame n + cls]; so the gradient of row m goes to
-  // frame n + cls when that frame is inside the clip.  Rows whose target falls outside the clip
-  // ("orphans") instead write the zero that the unreachable frame at the other clip end needs,
-  // which makes the scatter a bijection over dx.
-  dgrad_epilogue<BM, BN, WM, WN, BN == 64>(acc, smem, tid, dx, add_src, add_mask, g, mt, nt, Mc, stat, [&](int mrow) {
+// dgrad_epilogue's row map: tile row of parity class (ph, pw) -> dx pixel index (the identity for stride 1)
+struct DgradRowMap {
+  int st, ph, pw, Wc, HcWc, H, W;
+  __device__ __forceinline__ int operator()(int mrow) const {
     if (st == 1) return mrow;
     const int n = mrow / HcWc;
     const int rem = mrow - n * HcWc;
     const int hc = rem / Wc;
-    return (n * g.H + hc * st + ph) * g.W + (rem - hc * Wc) * st + pw;
-  });
-}
+    return (n * H + hc * st + ph) * W + (rem - hc * Wc) * st + pw;
+  }
+};
 
-template <int BM, int BN, int WM, int WN, bool BPRE = false>
-__global__ __launch_bounds__(256, 2) void conv_dgrad_x3_kernel(const float* __restrict__ dy, const float* __restrict__ wt,
-                                                          float* __restrict__ dx, const float* __restrict__ add_src,
-                                                          const uint32_t* __restrict__ add_mask, Geom g, int NT, Work wk,
-                                                          float* __restrict__ slab, BnStat stat) {
-  // bf16-piece variant of conv_dgrad_kernel (see conv_fprop_x3_kernel).  wt = the weights transposed per tap,
-  // [R*S][Cin][Cout], so that the B operand is k-contiguous like dy; BPRE: wt = the D planes of bdv_conv_split_weights.
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int AP = BM / 32, BP = BN / 32;
-  static_assert(3 * (BM + BN) * X3_LDK * 2 >= WM * 32 * BN * 4, "the epilogue stages a tile pass in the same LDS");
-  __shared__ __attribute__((aligned(16))) unsigned short smem16[3 * (BM + BN) * X3_LDK];
-  unsigned short* const As = smem16;
-  unsigned short* const Bs = smem16 + 3 * BM * X3_LDK;
-  float* const smem = reinterpret_cast<float*>(smem16);
+// The four-wave data-gradient tile.  w: the fp32 weights [Cout][R*S][Cin] (tile of a K-step: 32 co rows of BN ci), or
+// (Stage::kPlanes) the D planes (rows = input channels ci, contraction over (tap, co) with co contiguous).
+// DERIVE, PIPE: dgrad_epilogue's.
+template <class Stage, bool DERIVE, bool PIPE>
+__device__ __forceinline__ void dgrad_tile(float* __restrict__ smem, const float* __restrict__ dy, const float* __restrict__ w,
+                                           float* __restrict__ dx, const float* __restrict__ add_src,
+                                           const uint32_t* __restrict__ add_mask, const Geom& g, int NT, const Work& wk,
+                                           float* __restrict__ slab, const BnStat& stat) {
+  constexpr int BM = Stage::BM, BN = Stage::BN, WM = Stage::WM, WN = Stage::WN;
+  constexpr int TM = Stage::TM, TN = Stage::TN, AP = Stage::AP;
 
   // parity class of the input pixel (stride 1: a single class)
   const int st = g.stride;
@@ -1284,12 +1149,10 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_x3_kernel(const float* __re
   const int arow = tid >> 3, kg = tid & 7;
   const int HcWc = Hc * Wc;
   const int RS = g.R * g.S;
-  const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, g.N * g.Ho * g.Wo * g.Cout * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)wt, 0, BPRE ? 3 * g.Cout * RS * g.Cin * 2 : g.Cout * RS * g.Cin * 4, 0x00020000);
-  constexpr int BQ = BN * 4 / 256;
-  const int brow = tid >> 2, bc = tid & 3;
   const int plane_bytes = g.Cout * RS * g.Cin * 2;
   const int nchunk = g.Cout / BK;
+  const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)dy, 0, g.N * g.Ho * g.Wo * g.Cout * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, Stage::weight_bytes(g.Cout * RS * g.Cin), 0x00020000);
 
   int a_base[AP], a_h[AP], a_w[AP];
 #pragma unroll
@@ -1304,48 +1167,24 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_x3_kernel(const float* __re
     a_w[p] = wc + bw;
     a_base[p] = ((n * g.Ho + hc + bh) * g.Wo + wc + bw) * g.Cout * 4 + 16 * kg;
   }
-  // transposed weights: row ci = nt*BN + arow + 32p of tap `tap`, 4 consecutive co: (tap * Cin + ci) * Cout + co0 + 4*kg
-  int b_base[BP];
-#pragma unroll
-  for (int p = 0; p < BP; ++p) b_base[p] = ((nt * BN + arow + 32 * p) * g.Cout + 4 * kg) * 4;
+  int b_base[Stage::NB];
+  Stage::init_b(b_base, nt, tid, RS * g.Cin);
 
-  // K index state (uniform): kt = chunk * ntap + ir * ns + is  (tap-fastest)
-  int chunk = ntap > 0 ? it.kb / ntap : 0, ir, is;
-  {
-    const int ct = ntap > 0 ? it.kb - chunk * ntap : 0;
-    ir = ns > 0 ? ct / ns : 0;
-    is = ct - ir * ns;
-  }
+  DgradKStep k(it.kb, ntap, ns);
 
-  float4 ra[AP], rb[BP];
-  u32x4 rbp[BPRE ? 3 * BQ : 1];
+  float4 ra[AP];
+  typename Stage::BRegs rb;
   auto load = [&]() {
-    const int tap = (r0 + ir * st) * g.S + (s0 + is * st);
-    const int koff_a = (chunk * BK - (ir * g.Wo + is) * g.Cout) * 4;
-    const int koff_b = (tap * g.Cin * g.Cout + chunk * BK) * 4;
+    const int tap = (r0 + k.ir * st) * g.S + (s0 + k.is * st);
+    const int koff_a = (k.chunk * BK - (k.ir * g.Wo + k.is) * g.Cout) * 4;
+    const int koff_b = Stage::kPlanes ? (tap * nchunk + k.chunk) * g.Cin * 64 : (k.chunk * BK * RS + tap) * g.Cin * 4;
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
-      const bool v = (unsigned)(a_h[p] - ir) < (unsigned)g.Ho && (unsigned)(a_w[p] - is) < (unsigned)g.Wo;
+      const bool v = (unsigned)(a_h[p] - k.ir) < (unsigned)g.Ho && (unsigned)(a_w[p] - k.is) < (unsigned)g.Wo;
       ra[p] = buf_load16(yr, (a_base[p] + koff_a) | (v ? 0 : kOOB), 0);
     }
-    if (BPRE) {
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-        for (int q = 0; q < BQ; ++q)
-          rbp[pl * BQ + q] = __builtin_amdgcn_raw_buffer_load_b128(wr, (nt * BN + brow + 64 * q) * 64 + 16 * bc + pl * plane_bytes,
-                                                                   (tap * nchunk + chunk) * g.Cin * 64, 0);
-    } else {
-#pragma unroll
-      for (int p = 0; p < BP; ++p) rb[p] = buf_load16(wr, b_base[p], koff_b);
-    }
-    is += 1;
-    const int w1 = (is == ns) ? 1 : 0;
-    is = w1 ? 0 : is;
-    ir += w1;
-    const int w2 = (ir == nr) ? 1 : 0;
-    ir = w2 ? 0 : ir;
-    chunk += w2;
+    Stage::load_b(rb, wr, b_base, koff_b, plane_bytes);
+    k.advance(ns, nr);
   };
 
   f32x16 acc[TM][TN];
@@ -1355,18 +1194,10 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_x3_kernel(const float* __re
     load();
     for (int kt = it.kb; kt < it.ke; ++kt) {
       __syncthreads();
-      store_split3<BM, AP>(As, ra, tid);
-      if (BPRE) {
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-          for (int q = 0; q < BQ; ++q) *reinterpret_cast<u32x4*>(Bs + (pl * BN + brow + 64 * q) * X3_LDK + 8 * bc) = rbp[pl * BQ + q];
-      } else {
-        store_split3<BN, BP>(Bs, rb, tid);
-      }
+      Stage::store(smem, ra, rb, tid);
       __syncthreads();
       if (kt + 1 < it.ke) load();
-      mma_stage_x3<TM, TN, 32 * WM, 32 * WN, BM, BN>(As, Bs, acc, wm0, wn0, lane);
+      Stage::mma(smem, acc, wm0, wn0, lane);
     }
   }
   if (it.pslot >= 0) {
@@ -1378,13 +1209,29 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_x3_kernel(const float* __re
   // frame n + cls when that frame is inside the clip.  Rows whose target falls outside the clip
   // ("orphans") instead write the zero that the unreachable frame at the other clip end needs,
   // which makes the scatter a bijection over dx.
-  dgrad_epilogue<BM, BN, WM, WN, true, 4, true>(acc, smem, tid, dx, add_src, add_mask, g, mt, nt, Mc, stat, [&](int mrow) {
-    if (st == 1) return mrow;
-    const int n = mrow / HcWc;
-    const int rem = mrow - n * HcWc;
-    const int hc = rem / Wc;
-    return (n * g.H + hc * st + ph) * g.W + (rem - hc * Wc) * st + pw;
-  });
+  dgrad_epilogue<BM, BN, WM, WN, DERIVE, 4, PIPE>(acc, smem, tid, dx, add_src, add_mask, g, mt, nt, Mc, stat, DgradRowMap{st, ph, pw, Wc, HcWc, g.H, g.W});
+}
+
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256, (F32Stage<BM, BN, WM, WN, false>::kOcc)) void conv_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                          float* __restrict__ dx, const float* __restrict__ add_src,
+                                                          const uint32_t* __restrict__ add_mask, Geom g, int NT, Work wk,
+                                                          float* __restrict__ slab, BnStat stat) {
+  using Stage = F32Stage<BM, BN, WM, WN, false>;
+  __shared__ __attribute__((aligned(16))) float smem[Stage::kSmemFloats];
+  dgrad_tile<Stage, BN == 64, false>(smem, dy, w, dx, add_src, add_mask, g, NT, wk, slab, stat);
+}
+
+// BPRE: wt points at the D planes of bdv_conv_split_weights; no other form is compiled.
+template <int BM, int BN, int WM, int WN, bool BPRE = false>
+__global__ __launch_bounds__(256, (X3Stage<BM, BN, WM, WN, true>::kOcc)) void conv_dgrad_x3_kernel(const float* __restrict__ dy, const float* __restrict__ wt,
+                                                          float* __restrict__ dx, const float* __restrict__ add_src,
+                                                          const uint32_t* __restrict__ add_mask, Geom g, int NT, Work wk,
+                                                          float* __restrict__ slab, BnStat stat) {
+  static_assert(BPRE, "the weight operand of the bf16-piece kernels comes from the planes");
+  using Stage = X3Stage<BM, BN, WM, WN, true>;
+  __shared__ __attribute__((aligned(16))) float smem[Stage::kSmemFloats];
+  dgrad_tile<Stage, true, true>(smem, dy, wt, dx, add_src, add_mask, g, NT, wk, slab, stat);
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -1393,23 +1240,12 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_dgrad_fixup_kernel(const fl
                                                                 const uint32_t* __restrict__ add_mask, Geom g, int NT, Work wk,
                                                                 BnStat stat) {
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  constexpr int NACC = TM * TN * 16;
-  constexpr int NTHR = 64 * WM * WN;
   __shared__ __attribute__((aligned(16))) float smem[WM * 32 * BN];
   const int rt = blockIdx.x, tile = wk.dp_tiles + rt;
   const int mt = tile / NT, nt = tile - mt * NT;
   const int tid = threadIdx.x;
   f32x16 acc[TM][TN];
-  zero_acc<TM, TN>(acc);
-  for (int sl = 0; sl < wk.split; ++sl) {
-    const float* src = slab + (size_t)(rt * wk.split + sl) * NACC * NTHR + tid;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] += src[(size_t)((i * TN + j) * 16 + e) * NTHR];
-  }
+  load_partials<TM, TN, 64 * WM * WN>(slab, rt, wk.split, acc, tid);
   dgrad_epilogue<BM, BN, WM, WN>(acc, smem, tid, dx, add_src, add_mask, g, mt, nt, g.M, stat, [](int mrow) { return mrow; });
 }
 
@@ -2243,30 +2079,14 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
 
   int a_base[AP], a_t[AP], a_hi0[AP], a_wi0[AP];
 #pragma unroll
-  for (int p = 0; p < AP; ++p) {
-    const int m = mt * BM + arow + (NTHR / KG) * p;
-    const bool ok = m < g.M;
-    int n, rem, ho, wo;
-    fast_divmod(ok ? m : 0, HoWo, g.rcp_HoWo, n, rem);
-    fast_divmod(rem, g.Wo, g.rcp_Wo, ho, wo);
-    a_t[p] = n % g.T;
-    a_hi0[p] = ok ? ho * g.stride - g.pad : -(1 << 20);  // rows past M fail every bounds test
-    a_wi0[p] = wo * g.stride - g.pad_w;
-    a_base[p] = ((n * g.H + ho * g.stride - g.pad) * g.W + wo * g.stride - g.pad_w) * g.Cin * ES + 16 * kg;
-  }
+  for (int p = 0; p < AP; ++p) fprop_row<ES>(g, mt * BM + arow + (NTHR / KG) * p, kg, a_base[p], a_t[p], a_hi0[p], a_wi0[p]);
   int b_base[BPP];
   const bool b_active = BN * 4 >= NTHR || tid < BN * 4;   // a 64-row weight tile is loaded by the first four waves only
 #pragma unroll
   for (int q = 0; q < BPP; ++q) b_base[q] = b_active ? (nt * BN + brow + (NTHR / 4) * q) * 64 + 16 * bc : kOOB;
 
-  // K index state (uniform): K-step kt = chunk * R*S + r * S + s; the weight planes are stored in this order
-  const int RS = g.R * g.S;
-  int chunk = it.kb / RS, r, s, kt_w = it.kb;
-  {
-    const int tap = it.kb - chunk * RS;
-    r = tap / g.S;
-    s = tap - r * g.S;
-  }
+  FpropKStep k(g, it.kb);
+  int kt_w = it.kb;   // the weight planes are stored in K-step order
 
   constexpr int NSET = NBUF;           // two stages: two register sets (pl_pipeline2)
   float4 ra[NSET][AP];
@@ -2279,16 +2099,16 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
   auto load = [&](auto set) __attribute__((always_inline)) {
     constexpr int SET = decltype(set)::value;
     if constexpr (PRE) {
-      psc[SET] = *reinterpret_cast<const float4*>(epi.pre_scale + chunk * BK + 4 * kg);   // (PRE: fp32 tensors only, KG = 8)
-      psh[SET] = *reinterpret_cast<const float4*>(epi.pre_shift + chunk * BK + 4 * kg);
+      psc[SET] = *reinterpret_cast<const float4*>(epi.pre_scale + k.chunk * BK + 4 * kg);   // (PRE: fp32 tensors only, KG = 8)
+      psh[SET] = *reinterpret_cast<const float4*>(epi.pre_shift + k.chunk * BK + 4 * kg);
       pvalid[SET] = 0u;
     }
-    const int cls = shift_class(chunk * BK + (BK / KG) * kg, g.fold);
-    const int koff_a = ((r * g.W + s) * g.Cin + chunk * BK) * ES;
+    const int cls = shift_class(k.chunk * BK + (BK / KG) * kg, g.fold);
+    const int koff_a = ((k.r * g.W + k.s) * g.Cin + k.chunk * BK) * ES;
     const int koff_b = kt_w * g.Cout * 64;
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
-      const bool v = (unsigned)(a_hi0[p] + r) < (unsigned)g.H && (unsigned)(a_wi0[p] + s) < (unsigned)g.W &&
+      const bool v = (unsigned)(a_hi0[p] + k.r) < (unsigned)g.H && (unsigned)(a_wi0[p] + k.s) < (unsigned)g.W &&
                      (unsigned)(a_t[p] + cls) < (unsigned)g.T;
       ra[SET][p] = buf_load16(xr, (a_base[p] + koff_a + cls * frame_bytes) | (v ? 0 : kOOB), 0);   // ES = 2: eight bf16, as raw bits
       if constexpr (PRE) pvalid[SET] |= (v ? 1u : 0u) << p;
@@ -2298,13 +2118,7 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
 #pragma unroll
       for (int q = 0; q < BPP; ++q) rb[SET][pl * BPP + q] = __builtin_amdgcn_raw_buffer_load_b128(wr, b_base[q] + pl * plane_bytes, koff_b, 0);
     kt_w += 1;
-    s += 1;
-    const int ws_ = (s == g.S) ? 1 : 0;
-    s = ws_ ? 0 : s;
-    r += ws_;
-    const int wr_ = (r == g.R) ? 1 : 0;
-    r = wr_ ? 0 : r;
-    chunk += wr_;
+    k.advance(g);
   };
   // LDS offsets of this thread: stores (rows arow + 64 p / brow + 128 q keep (row >> 2) & 3) and fragment reads
   const int st_a = ES == 2 ? pl_off(arow, kg) : pl_off(arow, kg >> 1) + 8 * (kg & 1), st_b = pl_off(brow, bc);
@@ -2363,6 +2177,7 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
       }
       const int nchunk = g.Cin / BK;
       float4 re[APR];
+      const int RS = g.R * g.S;
       int chunk_a = it.kb / RS, r_a = (it.kb - chunk_a * RS) / 3;   // the group the next loadA loads
       auto loadA = [&](auto part) __attribute__((always_inline)) {
         constexpr int P0 = 2 * decltype(part)::value, P1 = P0 == 4 ? APR : P0 + 2;
@@ -2410,7 +2225,7 @@ __global__ __launch_bounds__(64 * WM * WN, pl_waves_per_simd(WM * WN, NP, BN == 
               *reinterpret_cast<u32x4*>(Bst + stage * (NP * PB) + st_b + (pl * PB + (NTHR / 4) * q * 64)) = rb[SET][pl * BPP + q];
         }
       };
-      pl_pipeline_rr(it.ke - it.kb, s, loadA, nextA, storeA, loadB, storeB, [&](int img, auto part, int stage) __attribute__((always_inline)) {
+      pl_pipeline_rr(it.ke - it.kb, k.s, loadA, nextA, storeA, loadB, storeB, [&](int img, auto part, int stage) __attribute__((always_inline)) {
         mma_stage_rr<BM, BN, WM, WN, NP, PT, PAR>(smem_b + img * (NP * PAR), Bst + stage * (NP * PB), acc, fa3[decltype(part)::value], fb);
       }, g.stagger != 0 && wave >= WM * WN / 2);
       rr_done = true;
@@ -2529,13 +2344,7 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
 #pragma unroll
   for (int q = 0; q < BPP; ++q) b_base[q] = b_active ? (nt * BN + brow + (NTHR / 4) * q) * 64 + 16 * bc : kOOB;
 
-  // K index state (uniform): kt = chunk * ntap + ir * ns + is  (tap-fastest)
-  int chunk = ntap > 0 ? it.kb / ntap : 0, ir, is;
-  {
-    const int ct = ntap > 0 ? it.kb - chunk * ntap : 0;
-    ir = ns > 0 ? ct / ns : 0;
-    is = ct - ir * ns;
-  }
+  DgradKStep k(it.kb, ntap, ns);
   const int nchunk = g.Cout / BK;
 
   constexpr int NSET = NBUF;
@@ -2543,25 +2352,19 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
   u32x4 rb[NSET][NP * BPP];
   auto load = [&](auto set) __attribute__((always_inline)) {
     constexpr int SET = decltype(set)::value;
-    const int tap = (r0 + ir * st) * g.S + (s0 + is * st);
-    const int koff_a = (chunk * BK - (ir * g.Wo + is) * g.Cout) * ES;
-    const int koff_b = (tap * nchunk + chunk) * g.Cin * 64;
+    const int tap = (r0 + k.ir * st) * g.S + (s0 + k.is * st);
+    const int koff_a = (k.chunk * BK - (k.ir * g.Wo + k.is) * g.Cout) * ES;
+    const int koff_b = (tap * nchunk + k.chunk) * g.Cin * 64;
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
-      const bool v = (unsigned)(a_h[p] - ir) < (unsigned)g.Ho && (unsigned)(a_w[p] - is) < (unsigned)g.Wo;
+      const bool v = (unsigned)(a_h[p] - k.ir) < (unsigned)g.Ho && (unsigned)(a_w[p] - k.is) < (unsigned)g.Wo;
       ra[SET][p] = buf_load16(yr, (a_base[p] + koff_a) | (v ? 0 : kOOB), 0);   // ES = 2: eight bf16, as raw bits
     }
 #pragma unroll
     for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
       for (int q = 0; q < BPP; ++q) rb[SET][pl * BPP + q] = __builtin_amdgcn_raw_buffer_load_b128(wr, b_base[q] + pl * plane_bytes, koff_b, 0);
-    is += 1;
-    const int w1 = (is == ns) ? 1 : 0;
-    is = w1 ? 0 : is;
-    ir += w1;
-    const int w2 = (ir == nr) ? 1 : 0;
-    ir = w2 ? 0 : ir;
-    chunk += w2;
+    k.advance(ns, nr);
   };
   // LDS offsets of this thread: stores (rows arow + 64 p / brow + 128 q keep (row >> 2) & 3) and fragment reads
   const int st_a = ES == 2 ? pl_off(arow, kg) : pl_off(arow, kg >> 1) + 8 * (kg & 1), st_b = pl_off(brow, bc);
@@ -2642,21 +2445,15 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
       auto loadB = [&](auto set) __attribute__((always_inline)) {
         constexpr int SET = decltype(set)::value;
         const int off = kt_b < it.ke ? 0 : kOOB;
-        const int tap = (r0 + ir * st) * g.S + (s0 + is * st);
-        const int koff_b = (tap * nchunk + chunk) * g.Cin * 64;
+        const int tap = (r0 + k.ir * st) * g.S + (s0 + k.is * st);
+        const int koff_b = (tap * nchunk + k.chunk) * g.Cin * 64;
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
           for (int q = 0; q < BPP; ++q)
             rb[SET][pl * BPP + q] = __builtin_amdgcn_raw_buffer_load_b128(wr, (b_base[q] + pl * plane_bytes) | off, off ? 0 : koff_b, 0);
         kt_b += 1;
-        is += 1;
-        const int w1 = (is == ns) ? 1 : 0;
-        is = w1 ? 0 : is;
-        ir += w1;
-        const int w2 = (ir == nr) ? 1 : 0;
-        ir = w2 ? 0 : ir;
-        chunk += w2;
+        k.advance(ns, nr);
       };
       auto storeB = [&](int stage, auto set) __attribute__((always_inline)) {
         constexpr int SET = decltype(set)::value;
@@ -2668,7 +2465,7 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
               *reinterpret_cast<u32x4*>(Bst + stage * (NP * PB) + st_b + (pl * PB + (NTHR / 4) * q * 64)) = rb[SET][pl * BPP + q];
         }
       };
-      pl_pipeline_rr(it.ke - it.kb, is, loadA, nextA, storeA, loadB, storeB, [&](int img, auto part, int stage) __attribute__((always_inline)) {
+      pl_pipeline_rr(it.ke - it.kb, k.is, loadA, nextA, storeA, loadB, storeB, [&](int img, auto part, int stage) __attribute__((always_inline)) {
         mma_stage_rr<BM, BN, WM, WN, NP, PT, PAR>(smem_b + img * (NP * PAR), Bst + stage * (NP * PB), acc, fa3[2 - decltype(part)::value], fb);
       }, g.stagger != 0 && wave >= WM * WN / 2);
       rr_done = true;
@@ -2698,13 +2495,7 @@ __global__ __launch_bounds__(64 * WM * WN, BM == 64 ? 4 : pl_waves_per_simd(WM *
     return;
   }
   constexpr bool EPI_PIPE = TM * TN <= 4 && NP >= 2 && BM != 64;   // 64 accumulator registers, two waves per SIMD
-  dgrad_epilogue<BM, BN, WM, WN, true, ES, EPI_PIPE>(acc, smem, tid, dx, add_src, add_mask, g, mt, nt, Mc, stat, [&](int mrow) {
-    if (st == 1) return mrow;
-    const int n = mrow / HcWc;
-    const int rem = mrow - n * HcWc;
-    const int hc = rem / Wc;
-    return (n * g.H + hc * st + ph) * g.W + (rem - hc * Wc) * st + pw;
-  });
+  dgrad_epilogue<BM, BN, WM, WN, true, ES, EPI_PIPE>(acc, smem, tid, dx, add_src, add_mask, g, mt, nt, Mc, stat, DgradRowMap{st, ph, pw, Wc, HcWc, g.H, g.W});
   BDV_STAMP(3);
   BDV_STAMP(4);
 }

@@ -8,7 +8,9 @@ tests/test_conv_bits_gpu.py launch`` re-records it) runs what the first leaves o
 'f16x2' arithmetic, bf16 storage, the eval-mode BatchNorm epilogue, the producer's BatchNorm in the fprop and wgrad loaders, the ReLU
 sign derived from y in the dgrad statistics, the small weight-gradient tile forms with and without the two-stage loop, and the
 remaining (arithmetic, tile) pairs of the plane kernels; tests/test_conv_launch_cpu.py checks that the two lists together plan every
-kernel name of tests/golden/conv_plan_sites.json."""
+kernel name of tests/golden/conv_plan_sites.json.  Its last seven cases take each kernel family through what its tile prologue and
+K-step state decide: a stride-2 site of odd size (unequal parity classes, blocks of the padded grid that exit), a ragged last row
+tile, K-split remainder tiles with the fix-up launch, the temporal shift, and the stem's temporal taps."""
 import contextlib
 import hashlib
 import json
@@ -48,8 +50,16 @@ WGRAD_SHAPES = [
     (2, 14, 14, 128, 256, 1, 1, 0, 1, 0),
     (2, 14, 14, 256, 128, 1, 1, 0, 1, 0),
 ]
-ALL_SHAPES = SHAPES + WGRAD_SHAPES
-NEW = tuple(range(len(SHAPES), len(ALL_SHAPES)))
+# what the shapes above leave out of the tile prologues: a 3x3 site with the temporal shift and a K long enough for a K split, and the
+# stem on an odd size (a ragged last row tile), without and with temporal taps (two more fields: Rt, st_t; N = output frames)
+PROLOGUE_SHAPES = [
+    (2, 9, 9, 128, 128, 3, 1, 1, 2, 16),
+    (2, 13, 13, 4, 64, 7, 2, 3, 1, 0),
+    (4, 13, 13, 4, 64, 7, 2, 3, 2, 0, 3, 2),
+]
+ALL_SHAPES = SHAPES + WGRAD_SHAPES + PROLOGUE_SHAPES
+NEW = tuple(range(len(SHAPES), len(SHAPES) + len(WGRAD_SHAPES)))
+PRO = tuple(range(len(SHAPES) + len(WGRAD_SHAPES), len(ALL_SHAPES)))
 # (shape index, arithmetic, forced tile, variant).  Variants: 'plain' = the calls of the first list; 'onestage' = the same with
 # BDVCIL_WGRAD_2STAGE=0; 'affine' = conv_fprop(affine=(scale, shift, residual, True)); 'pre_bn' = conv_fprop / conv_wgrad with the
 # producer's BatchNorm in the loader; 'relu_affine' = conv_dgrad with the 5-tuple bn_stats (ReLU sign derived from y)
@@ -61,6 +71,12 @@ LAUNCH_PARAMS += [(i, 'bf16x3', -1, v) for v in ('plain', 'onestage') for i in N
 LAUNCH_PARAMS += [(2, 'bf16x3', -1, 'pre_bn'), (NEW[2], 'bf16x3', -1, 'pre_bn'), (NEW[2], 'bf16x3', 2, 'pre_bn'), (0, 'bf16x3', 5, 'pre_bn')]
 LAUNCH_PARAMS += [(NEW[2], 'bf16x3', 2, 'plain'), (NEW[2], 'bf16x2', -1, 'plain'), (NEW[3], 'bf16x1', 0, 'plain'), (NEW[3], 'bf16x1', 1, 'plain')]
 LAUNCH_PARAMS += [(i, m, -1, 'plain') for i in (2, 5) for m in ('bf16x1', 'bf16x2')]
+# the tile prologues and K-step state, per kernel family (forced tile 6 = none: the conv_*_x3 kernels where a plane tile would run):
+# stride 2 on an odd size with a K split (conv_fprop_x3_kernel) and through the parity classes of conv_dgrad_pl_kernel; the temporal
+# shift together with K-split remainder tiles in the x3, the fp32-MFMA and the plane kernels; the ragged stem, and its temporal taps
+LAUNCH_PARAMS += [(3, 'bf16x3', 6, 'plain'), (3, 'bf16x3', 1, 'plain')]
+LAUNCH_PARAMS += [(PRO[0], 'bf16x3', 6, 'plain'), (PRO[0], 'f32mfma', -1, 'plain'), (PRO[0], 'bf16x3', -1, 'plain')]
+LAUNCH_PARAMS += [(PRO[1], 'f32mfma', -1, 'plain'), (PRO[2], 'bf16x3', -1, 'plain')]
 
 
 def _sha(t):
@@ -93,12 +109,13 @@ def _setup(mode, tile, variant):
 
 
 def conv_hashes(si, mode, tile, dev, variant='plain'):
-    N, H, W, Cin, Cout, R, st, pad, T, fold = ALL_SHAPES[si]
+    N, H, W, Cin, Cout, R, st, pad, T, fold = ALL_SHAPES[si][:10]
+    rt, st_t = ALL_SHAPES[si][10:] or (0, 0)
     gen = torch.Generator().manual_seed(4000 + si)
-    x = torch.randn(N, H, W, Cin, generator=gen)
+    x = torch.randn(N * max(st_t, 1), H, W, Cin, generator=gen)
     if Cin == 4:
         x[..., 3] = 0
-    w = torch.randn(Cout, R, R, Cin, generator=gen) / (Cin * R * R) ** 0.5
+    w = torch.randn(Cout, max(rt, 1) * R, R, Cin, generator=gen) / (Cin * R * R) ** 0.5
     Ho, Wo = (H + 2 * pad - R) // st + 1, (W + 2 * pad - R) // st + 1
     dy = torch.randn(N, Ho, Wo, Cout, generator=gen)
     add = torch.randn(N, H, W, Cin, generator=gen)
@@ -109,7 +126,7 @@ def conv_hashes(si, mode, tile, dev, variant='plain'):
     tag = f'bits-{si}-{mode}-{tile}'       # a workspace of its own: the K-split must not depend on what ran before in the process
     out = {}
     with _setup(mode, tile, variant) as K:
-        g = K.make_geom(N, H, W, Cin, Cout, R, R, st, pad, T, fold)
+        g = K.make_geom(N, H, W, Cin, Cout, R, R, st, pad, T, fold, rt=rt, st_t=st_t)
         xd, wd, dyd = x.to(dev), w.to(dev), dy.to(dev)
         if variant in ('plain', 'onestage'):
             y, part = K.conv_fprop(xd, wd, g, bn_stats=True, ws_tag=tag)
@@ -148,11 +165,12 @@ def conv_hashes(si, mode, tile, dev, variant='plain'):
 
 def planned_kernels(si, mode, tile, variant):
     """Host only: the kernel names ``conv_plan`` gives for the calls of ``conv_hashes`` of this case."""
-    N, H, W, Cin, Cout, R, st, pad, T, fold = ALL_SHAPES[si]
+    N, H, W, Cin, Cout, R, st, pad, T, fold = ALL_SHAPES[si][:10]
+    rt, st_t = ALL_SHAPES[si][10:] or (0, 0)
     pre = variant == 'pre_bn'
     kinds = {'affine': ('fprop',), 'pre_bn': ('fprop', 'wgrad'), 'relu_affine': ('dgrad',)}.get(variant, ('fprop', 'dgrad', 'wgrad'))
     with _setup(mode, tile, variant) as K:
-        g = K.make_geom(N, H, W, Cin, Cout, R, R, st, pad, T, fold)
+        g = K.make_geom(N, H, W, Cin, Cout, R, R, st, pad, T, fold, rt=rt, st_t=st_t)
         g.act_dtype = 1 if mode == 'bf16' else 0
         return [K.conv_plan(g, kind, pre=pre).kernel.decode() for kind in kinds if kind != 'dgrad' or Cin % 64 == 0]
 

@@ -11,7 +11,8 @@ global (the time stamps of the diagnostic build) holds the distance to it in its
 kernel counts as equal when size and metadata are equal and every differing 32-bit word changed by exactly the change of that
 distance; the summary says how many there are.
 
-Prints a summary line, the kernels only one object has, the kernels that differ, and with ``--list`` one line per common kernel.
+Prints a summary line, the kernels only one object has, the kernels that differ (each with its old and new metadata figures), and with
+``--list`` one line per common kernel that does not differ.
 Exit status 0 when the two sets are equal and no kernel differs, else 1.  This is how a refactor of host code shows that it did
 not reach device code (profiles/conv_plan_refactor.txt, profiles/conv_launch_refactor.txt)."""
 import argparse
@@ -139,6 +140,8 @@ def main():
     for n in differ:
         what = [w for w, i in (('size', 0), ('code', 1), ('metadata', 2)) if old[n][i] != new[n][i]]
         print(f'DIFFERS ({", ".join(what)}): {pretty[n]}   size {old[n][0]} -> {new[n][0]}')
+        print('    ' + '  '.join(f'{short} {o}' + ('' if o == v else f' -> {v}')
+                                 for (_, short), o, v in zip(NOTE_KEYS, _note_fields(old[n][2]), _note_fields(new[n][2]))))
     if a.list:
         width = max([len(pretty[n]) for n in both] + [10])
         print()
