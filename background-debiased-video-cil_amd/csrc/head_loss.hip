@@ -105,7 +105,11 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
   }
 }
 
-// LSC backward, part A (grid N): dcos[n,:] from dsim; dx[n,:] = sum_j G[n,j] w_j - a_n x_n
+// LSC backward, part A (grid N): dcos[n,:] from dsim; dx[n,:] = sum_j G[n,j] (w_j - t_j x^_n), t_j = cos[n,j] |w_j|, x^ = x / |x|.
+// Every weight row loses its component along x_n as it is added.  Summed apart (sum_j G_j w_j - a_n x_n, a_n = sum_j dcos_j cos_j /
+// |x|^2) the two sides are each rounded at their own size and what they leave is an ulp of that size, not of the gradient: 1.5e-7
+// where the gradient is 0 (D = 1, where the cosine is +-1 whatever x is), and the same loss of digits whenever the features lie
+// along their proxies.  Term by term the difference is formed from w_j and its own projection, and is 0 exactly at D = 1.
 __global__ __launch_bounds__(256) void lsc_bwd_dx_kernel(const float* __restrict__ dsim, const float* __restrict__ x,
                                                           const float* __restrict__ w, const float* __restrict__ xnorm,
                                                           const float* __restrict__ wnorm, const float* __restrict__ cosbuf,
@@ -113,11 +117,9 @@ __global__ __launch_bounds__(256) void lsc_bwd_dx_kernel(const float* __restrict
                                                           int P) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* G = sm;  // K*P
-  __shared__ float red[4];
-  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = blockIdx.x, tid = threadIdx.x;
   const int KP = K * P;
   const float nx = xnorm[n];
-  float part = 0.f;
   for (int k = tid; k < K; k += 256) {
     const float* c = cosbuf + (size_t)n * KP + k * P;
     float mx = c[0];
@@ -135,44 +137,42 @@ __global__ __launch_bounds__(256) void lsc_bwd_dx_kernel(const float* __restrict
       const float dc = g * a * (1.f + c[p] - sbar);
       dcos_ws[(size_t)n * KP + k * P + p] = dc;
       G[k * P + p] = dc / (nx * wnorm[k * P + p]);
-      part += dc * c[p];
     }
   }
-  part = wave_sum(part);
-  if (lane == 0) red[wave] = part;
   __syncthreads();
-  const float a_n = (red[0] + red[1] + red[2] + red[3]) / (nx * nx);
+  const float* cn = cosbuf + (size_t)n * KP;
   for (int d = tid; d < D; d += 256) {
+    const float xh = x[(size_t)n * D + d] / nx;
     float acc = 0.f;
-    for (int j = 0; j < KP; ++j) acc += G[j] * w[(size_t)j * D + d];
-    dx[(size_t)n * D + d] = acc - a_n * x[(size_t)n * D + d];
+    for (int j = 0; j < KP; ++j) {
+      const float g = G[j];
+      acc += g * w[(size_t)j * D + d];
+      acc -= (g * (cn[j] * wnorm[j])) * xh;
+    }
+    dx[(size_t)n * D + d] = acc;
   }
 }
 
-// LSC backward, part B (grid K*P): dw[j,:] = beta*dw + sum_n G[n,j] x_n - b_j w_j
+// LSC backward, part B (grid K*P): dw[j,:] = beta*dw + sum_n G[n,j] (x_n - s_n w^_j), s_n = cos[n,j] |x_n|, w^ = w / |w| (as part A)
 __global__ __launch_bounds__(256) void lsc_bwd_dw_kernel(const float* __restrict__ dcos, const float* __restrict__ x,
                                                           const float* __restrict__ w, const float* __restrict__ xnorm,
                                                           const float* __restrict__ wnorm, const float* __restrict__ cosbuf,
                                                           float* __restrict__ dw, float beta, int N, int D, int KP) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* G = sm;  // N
-  __shared__ float red[4];
-  const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = blockIdx.x, tid = threadIdx.x;
   const float nw = wnorm[j];
-  float part = 0.f;
-  for (int n = tid; n < N; n += 256) {
-    const float dc = dcos[(size_t)n * KP + j];
-    G[n] = dc / (xnorm[n] * nw);
-    part += dc * cosbuf[(size_t)n * KP + j];
-  }
-  part = wave_sum(part);
-  if (lane == 0) red[wave] = part;
+  for (int n = tid; n < N; n += 256) G[n] = dcos[(size_t)n * KP + j] / (xnorm[n] * nw);
   __syncthreads();
-  const float b_j = (red[0] + red[1] + red[2] + red[3]) / (nw * nw);
   for (int d = tid; d < D; d += 256) {
+    const float wh = w[(size_t)j * D + d] / nw;
     float acc = 0.f;
-    for (int n = 0; n < N; ++n) acc += G[n] * x[(size_t)n * D + d];
-    float v = acc - b_j * w[(size_t)j * D + d];
+    for (int n = 0; n < N; ++n) {
+      const float g = G[n];
+      acc += g * x[(size_t)n * D + d];
+      acc -= (g * (cosbuf[(size_t)n * KP + j] * xnorm[n])) * wh;
+    }
+    float v = acc;
     if (beta != 0.f) v += beta * dw[(size_t)j * D + d];
     dw[(size_t)j * D + d] = v;
   }
@@ -274,6 +274,14 @@ __global__ void dropout_kernel(const float* __restrict__ x, float* __restrict__ 
   }
 }
 
+// lsc_logit: s_k = eta * (sim_k - margin) with the product rounded on its own.  Left to the compiler, "eta * (..) - mx" becomes one
+// fused multiply-add whose result at the arg-max is the rounding error of the product, not 0: a single class then gave a loss of
+// some 1e-9 where the reference gives 0 exactly, and every row's largest term was exp(1e-9) in place of exp(0).
+__device__ __forceinline__ float lsc_logit(float eta, float v, float margin) {
+#pragma clang fp contract(off)
+  return eta * (v - margin);
+}
+
 // ---------------------------------------------------------------------------------------
 // LSCLoss (lsc_loss.py:36-56): one block, waves stride over rows, fixed-order final reduce.
 // ---------------------------------------------------------------------------------------
@@ -295,7 +303,7 @@ __global__ __launch_bounds__(256) void lsc_loss_kernel(const float* __restrict__
     float mx = -INFINITY;
     int am = 0x7fffffff;
     for (int k = lane; k < K; k += 64) {
-      const float s = eta * (row[k] - margin);
+      const float s = lsc_logit(eta, row[k], margin);
       if (s > mx) { mx = s; am = k; }
     }
     // wave argmax with first-index tie break
@@ -306,10 +314,10 @@ __global__ __launch_bounds__(256) void lsc_loss_kernel(const float* __restrict__
     }
     float esum = 0.f;
     for (int k = lane; k < K; k += 64)
-      if (k != y) esum += expf(eta * (row[k] - margin) - mx);
+      if (k != y) esum += expf(lsc_logit(eta, row[k], margin) - mx);
     esum = wave_sum(esum);
     const float den = 1.f + esum;  // exp(0) of the zeroed positive slot (Appendix C.1)
-    const float num = eta * (row[y] - margin) - mx;
+    const float num = lsc_logit(eta, row[y], margin) - mx;
     const float wgt = class_weights != nullptr ? class_weights[y] : 1.f;
     const float l = wgt * (logf(den) - num);
     const bool active = !hinge || l >= 0.f;
@@ -318,7 +326,7 @@ __global__ __launch_bounds__(256) void lsc_loss_kernel(const float* __restrict__
     for (int k = lane; k < K; k += 64) {
       float g = 0.f;  // dl/ds_k
       if (active) {
-        g = (k == y) ? -1.f : expf(eta * (row[k] - margin) - mx) / den;
+        g = (k == y) ? -1.f : expf(lsc_logit(eta, row[k], margin) - mx) / den;
         if (k == am) g += 1.f / den;  // gradient through the row-max subtraction
         g *= wgt;
       }
