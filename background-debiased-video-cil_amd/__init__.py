@@ -13,6 +13,7 @@ Import as ``bdvcil_amd`` (see ``bdvcil_amd.py`` at the repo root).  Layout:
 * ``background``   background extraction: temporal median + JPEG encode of the frames of a video (bg_extraction_tmf); resized crop +
                    NaN-aware median / mean for moving-camera videos (sim_cam_motion_bg_extract)
 * ``augment``      RandAugment for batches of uint8 clips (draws + device tables; pixels in csrc/augment.hip)
+* ``blending``     ``train_cfg.blending``: MixupBlending / CutmixBlending on the clip-blend kernels (csrc/blend.hip)
 * ``cil_step``     training-step arithmetic of BaseCIL / ICARLModel + a step engine
 * ``ddp``          bucketed gradient all-reduce over RCCL
 * ``representation``  predict_step / NME classifier / class means / herding
@@ -46,12 +47,13 @@ from .kernels import bump_weight_epoch  # noqa: F401,E402
 from .kernels import CONV_ARITH_MODES, conv_arith, get_conv_arith, set_conv_arith  # noqa: F401,E402
 
 from . import _lib, kernels  # noqa: F401,E402
-from .registry import (BACKBONES, HEADS, LOSSES, OPTIMIZER_BUILDERS, RECOGNIZERS, Registry, build_backbone,  # noqa: F401
-                       build_head, build_loss, build_model)
+from .registry import (BACKBONES, BLENDINGS, HEADS, LOSSES, OPTIMIZER_BUILDERS, RECOGNIZERS, Registry, build_backbone,  # noqa: F401
+                       build_blending, build_head, build_loss, build_model)
 from .resnet_tsm import Nhwc4Frames, ResNetTSM, TemporalShift  # noqa: F401
-from .heads import LSC, AvgConsensus, IncrementalNet, IncrementalTSMHead  # noqa: F401
+from .heads import LSC, AvgConsensus, IncrementalNet, IncrementalTSMHead, TSMHead  # noqa: F401
 from .losses import ACMSmoothCE, CrossEntropyLoss, LSCLoss, SoftTargetCrossEntropy  # noqa: F401
 from .recognizer import CILRecognizer2D, Recognizer2D  # noqa: F401
+from .blending import CutmixBlending, MixupBlending  # noqa: F401
 from .resnet3d import I3DHead, Recognizer3D, ResNet3d  # noqa: F401
 from .hooks import OutputHook, rgetattr  # noqa: F401
 from .optim import (CILTSMOptimizerConstructor, CILTSMOptimizerConstructorImprovised, FusedSGD, build_lr_scheduler,  # noqa: F401

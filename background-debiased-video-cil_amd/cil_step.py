@@ -14,6 +14,7 @@ from . import kernels as K
 from .ddp import GradAllReducer
 from .hooks import OutputHook
 from .losses import SoftTargetCrossEntropy
+from .resnet_tsm import Nhwc4Frames
 
 
 def base_training_step(current_model: nn.Module, batch_data: Dict[str, torch.Tensor], current_task: int = 0,
@@ -118,21 +119,26 @@ def icarl_video_mix_training_step(current_model: nn.Module, batch_data: Dict[str
                                   prev_model: Optional[nn.Module] = None, previous_task_num_classes: int = 0) -> torch.Tensor:
     """``ICARLVideoMix.training_step`` (libs/cil/icarl_video_mix.py:20-45): with probability ``video_mix_prob`` a box of
     every frame is overwritten, in place, by the same box of a permuted sample and the one-hot targets are mixed by the
-    box area; then the iCaRL step on the mixed clips.  ``imgs`` must be the (B, T, 3, H, W) tensor (the box copy is a
-    strided tensor copy).  The config's ``video_mix_alpha`` reaches ``np.random.beta`` as a 1-tuple in the reference
-    (trailing comma at :22); pass the config value, the tuple is made here."""
+    box area; then the iCaRL step on the mixed clips.  ``imgs``: the (B, T, 3, H, W) tensor or the fused front-end's ``Nhwc4Frames``;
+    the box copy is ``kernels.blend_box_`` (csrc/blend.hip), which moves the boxes only.  The config's ``video_mix_alpha`` reaches
+    ``np.random.beta`` as a 1-tuple in the reference (trailing comma at :22); pass the config value, the tuple is made here."""
     imgs, labels = batch_data['imgs'], batch_data['label']
-    if not torch.is_tensor(imgs) or imgs.dim() != 5:
-        raise TypeError('icarl_video_mix_training_step needs imgs as a (B, T, 3, H, W) tensor')
+    if isinstance(imgs, Nhwc4Frames):
+        data, B, outer, inner = imgs.data, imgs.batches, imgs.num_segments, 4
+    elif torch.is_tensor(imgs) and imgs.dim() == 5:
+        data, B, outer, inner = imgs, imgs.size(0), imgs.size(1) * imgs.size(2), 1
+    else:
+        raise TypeError('icarl_video_mix_training_step needs imgs as a (B, T, 3, H, W) tensor or an Nhwc4Frames')
+    rows, cols = imgs.size(-2), imgs.size(-1)
     alpha = (video_mix_alpha,)
-    draw = tubemix_draw(imgs.size(0), imgs.size(-2), imgs.size(-1), alpha, video_mix_prob)
+    draw = tubemix_draw(B, rows, cols, alpha, video_mix_prob)
     base = None
     if draw is not None:
-        batch_idx, (r1, c1, r2, c2), lam = draw
-        perm = batch_idx.to(imgs.device)
-        imgs[:, :, :, r1:r2, c1:c2] = imgs[perm][:, :, :, r1:r2, c1:c2]
+        batch_idx, box, lam = draw
+        perm = K._blend_perm(batch_idx, B, data.device, 'icarl_video_mix_training_step')
+        K.blend_box_(data, batch_idx, box, outer, rows, cols, inner, perm_dev=perm)
         flat = labels.reshape(-1).contiguous()
-        lam_t = torch.full((flat.numel(),), lam, dtype=torch.float32, device=imgs.device)
+        lam_t = torch.full((flat.numel(),), lam, dtype=torch.float32, device=data.device)
         # y * lam + y[batch_idx] * (1 - lam) on one-hot rows = the smooth-label kernel with exponent 1
         base = K.acm_targets(flat, flat[perm].contiguous(), lam_t, 1.0, num_classes)
     cls_score = current_model(imgs, return_loss=False)

@@ -192,3 +192,30 @@ class IncrementalTSMHead(nn.Module):
         else:
             losses['loss_cls'] = loss_cls
         return losses
+
+
+class HipLinear(nn.Linear):
+    """``nn.Linear`` (same parameters and state-dict keys) whose forward is the HIP linear kernel."""
+
+    def forward(self, x):
+        return Fn.LinearFn.apply(x, self.weight, self.bias)
+
+
+@HEADS.register_module()
+class TSMHead(IncrementalTSMHead):
+    """UPSTREAM TSMHead (the head of configs/recognition/tsm/*.py): the forward and ``loss`` of ``IncrementalTSMHead`` over a plain
+    linear ``fc_cls`` (weight ~ N(0, init_std), bias 0; state-dict keys ``fc_cls.weight`` / ``fc_cls.bias``).  It does not grow."""
+
+    def __init__(self, num_classes, in_channels, **kwargs):
+        if 'inc_head_config' in kwargs:
+            raise TypeError('TSMHead takes no inc_head_config (IncrementalTSMHead does)')
+        super().__init__(num_classes, in_channels, **kwargs)
+        del self.inc_head_config
+        self.fc_cls = HipLinear(self.in_channels, self.num_classes)
+
+    def init_weights(self):
+        nn.init.normal_(self.fc_cls.weight, 0, self.init_std)
+        nn.init.constant_(self.fc_cls.bias, 0)
+
+    def update_fc(self, nb_classes):
+        raise ValueError('TSMHead has a fixed classifier; use IncrementalTSMHead for class-incremental training')

@@ -1623,3 +1623,59 @@ def randaug_apply(frames_u8, op_i, op_d, out=None):
     check(lib().bdv_randaug_apply(_p(frames_u8), _p(out), _p(op_i), _p(op_d), B, T, H, W, _p(ws), ws.numel(), _stream()),
           'bdv_randaug_apply')
     return out
+
+
+# ---- clip blending: train_cfg.blending (Mixup / CutMix) and VideoMix -----------------------------------------------------------
+
+def _blend_perm(perm, B: int, device, who: str) -> torch.Tensor:
+    """The HOST index vector of a blend (``torch.randperm`` output, a list) -> device int64 (B,).  Its range is checked here, on the
+    host copy, so the kernels never form an address outside the batch and nothing is copied back."""
+    if isinstance(perm, torch.Tensor) and perm.is_cuda:
+        raise TypeError(f'{who}: perm must be a host tensor (its range is checked before the upload)')
+    host = torch.as_tensor(perm, dtype=torch.int64).reshape(-1).contiguous()
+    if host.numel() != B:
+        raise ValueError(f'{who}: perm has {host.numel()} entries for a batch of {B}')
+    if B and (int(host.min()) < 0 or int(host.max()) >= B):
+        raise ValueError(f'{who}: perm entries must lie in [0, {B}), got [{int(host.min())}, {int(host.max())}]')
+    return host.to(device)
+
+
+def blend_mix(x, perm, lam, out=None, perm_dev=None):
+    """``bdv_blend_mix_f32``: ``lam * x + (1 - lam) * x[perm]`` over the first dimension of ``x`` (any contiguous fp32 layout), bit for
+    bit, as a NEW tensor (or into ``out``, which must not overlap ``x``).  ``perm``: host int64 (B,); ``lam``: a Python float or a
+    0-dim host tensor, taken as fp32.  ``perm_dev``: the upload of ``perm`` made by an earlier call's ``_blend_perm``."""
+    _chk(x, name='x')
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f'blend_mix: expected a non-empty (B, ...) tensor, got {tuple(x.shape)}')
+    B = int(x.shape[0])
+    dev = _blend_perm(perm, B, x.device, 'blend_mix') if perm_dev is None else _chk(perm_dev, (B,), torch.int64, 'perm_dev')
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk(out, tuple(x.shape), name='out')
+    lam32 = float(torch.as_tensor(lam, dtype=torch.float32))
+    check(lib().bdv_blend_mix_f32(_p(x), _p(dev), lam32, _p(out), B, x.numel() // B, _stream()), 'bdv_blend_mix_f32')
+    return out
+
+
+def blend_box_(x, perm, box, outer: int, H: int, W: int, inner: int = 1, perm_dev=None):
+    """``bdv_blend_box_f32``, in place: ``x[b, :, r1:r2, c1:c2, :] = x[perm[b], :, r1:r2, c1:c2, :]`` (gather, then assign) on samples of
+    ``outer * H * W * inner`` floats; ``box = (r1, c1, r2, c2)``.  The batch size is ``x.numel()`` over the sample size (the NHWC4
+    frames tensor has B * T rows).  Returns ``x``."""
+    _chk(x, name='x')
+    outer, H, W, inner = int(outer), int(H), int(W), int(inner)
+    if inner not in (1, 4) or outer <= 0 or H <= 0 or W <= 0:
+        raise ValueError(f'blend_box_: outer {outer}, H {H}, W {W}, inner {inner} (inner is 1 or 4)')
+    S = outer * H * W * inner
+    if x.numel() == 0 or x.numel() % S:
+        raise ValueError(f'blend_box_: {tuple(x.shape)} is not a batch of samples of {outer} x {H} x {W} x {inner}')
+    B = x.numel() // S
+    r1, c1, r2, c2 = (int(v) for v in box)
+    if not (0 <= r1 <= r2 <= H and 0 <= c1 <= c2 <= W):
+        raise ValueError(f'blend_box_: box rows {r1}:{r2}, columns {c1}:{c2} outside the {H} x {W} grid')
+    dev = _blend_perm(perm, B, x.device, 'blend_box_') if perm_dev is None else _chk(perm_dev, (B,), torch.int64, 'perm_dev')
+    if r1 == r2 or c1 == c2:
+        return x
+    ws = workspace(lib().bdv_blend_box_scratch_bytes(B, outer, inner, r1, c1, r2, c2), x.device, 'blend')
+    check(lib().bdv_blend_box_f32(_p(x), _p(dev), B, outer, H, W, inner, r1, c1, r2, c2, _p(ws), ws.numel(), _stream()), 'bdv_blend_box_f32')
+    return x

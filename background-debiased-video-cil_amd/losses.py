@@ -33,6 +33,21 @@ def _weighted_ce(score, labels, cw):
     return Fn.SoftCEFn.apply(score, rows, None)
 
 
+def _soft_label_ce(score, soft, cw):
+    """UPSTREAM CrossEntropyLoss, soft-label branch (``cls_score.size() == label.size()``): mean_b(-sum_k label * log_softmax(score)), or
+    with class weights sum_b sum_k(-label * w * lsm) / sum_b sum_k(w * label): the soft-target kernel on rows scaled as in ``_weighted_ce``."""
+    soft = soft.to(torch.float32).contiguous()
+    if cw is None:
+        return Fn.SoftCEFn.apply(score, soft, None)
+    rows = soft * cw.view(1, -1)
+    return Fn.SoftCEFn.apply(score, rows * (soft.shape[0] / rows.sum()), None)                  # (B, K)-sized plumbing
+
+
+def is_soft_label(cls_score, label) -> bool:
+    """UPSTREAM's test for the soft-label branch: the label has the scores' size (a blending made (B, K) rows of it)."""
+    return cls_score.size() == label.size()
+
+
 @LOSSES.register_module()
 class LSCLoss(nn.Module):
     """libs/losses/lsc_loss.py:8-58.  ``forward(similarities (B,K), targets (B,), **kwargs) -> scalar``."""
@@ -48,6 +63,9 @@ class LSCLoss(nn.Module):
         self.eta = nn.Parameter(torch.Tensor([eta]), requires_grad=self.learnable_eta)
 
     def forward(self, similarities: torch.Tensor, targets: torch.Tensor, **kwargs):
+        if targets.is_floating_point():
+            raise ValueError('LSCLoss takes integer class targets; the soft labels of a train_cfg blending (Mixup / CutMix) need '
+                             'CrossEntropyLoss')
         if targets.dim() == 0:
             targets = targets.unsqueeze(0)
         cw = _class_weights(self.class_weights, similarities)
@@ -58,9 +76,9 @@ class LSCLoss(nn.Module):
 
 @LOSSES.register_module()
 class CrossEntropyLoss(nn.Module):
-    """Mean cross-entropy on integer labels (BASELINE config 2 "CE loss only").  Unlike UPSTREAM mmaction
-    CrossEntropyLoss it tolerates the ``batch_data`` / ``num_classes`` kwargs CILRecognizer2D adds
-    (SURVEY Appendix A notes the upstream one would raise on them)."""
+    """Mean cross-entropy on integer labels (BASELINE config 2 "CE loss only"), or on the (B, K) soft labels of a blending when the label
+    has the scores' size (UPSTREAM's soft-label branch).  Unlike UPSTREAM mmaction CrossEntropyLoss it tolerates the ``batch_data`` /
+    ``num_classes`` kwargs CILRecognizer2D adds (SURVEY Appendix A notes the upstream one would raise on them)."""
 
     def __init__(self, loss_weight=1.0, class_weight=None):
         super().__init__()
@@ -70,7 +88,8 @@ class CrossEntropyLoss(nn.Module):
     def forward(self, cls_score, label, **kwargs):
         if label.dim() == 0:
             label = label.unsqueeze(0)
-        loss = _weighted_ce(cls_score, label, _class_weights(self.class_weight, cls_score))
+        cw = _class_weights(self.class_weight, cls_score)
+        loss = _soft_label_ce(cls_score, label, cw) if is_soft_label(cls_score, label) else _weighted_ce(cls_score, label, cw)
         return loss if self.loss_weight == 1.0 else loss * self.loss_weight
 
 

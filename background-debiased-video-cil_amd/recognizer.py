@@ -7,10 +7,24 @@ import torch.nn as nn
 
 from . import functional as Fn
 from . import kernels as K
-from .registry import RECOGNIZERS, build_backbone, build_head
+from .registry import RECOGNIZERS, build_backbone, build_blending, build_head
 from .resnet_tsm import Nhwc4Frames
 
 
+def blending_from(train_cfg):
+    """UPSTREAM BaseRecognizer.__init__: ``train_cfg['blending']`` -> the built blending, else None."""
+    if train_cfg is not None and 'blending' in train_cfg:
+        return build_blending(train_cfg['blending'])
+    return None
+
+
+def hard_labels(labels):
+    """``labels.squeeze()`` of UPSTREAM forward_train for integer labels; the (B, K) soft labels of a blending pass through as they are
+    (a squeeze would collapse a batch of one)."""
+    return labels if labels.is_floating_point() else labels.squeeze()
+
+
+@RECOGNIZERS.register_module()
 class Recognizer2D(nn.Module):
     def __init__(self, backbone, cls_head=None, neck=None, train_cfg=None, test_cfg=None):
         super().__init__()
@@ -20,6 +34,7 @@ class Recognizer2D(nn.Module):
         self.cls_head = build_head(cls_head) if cls_head else None
         self.train_cfg = train_cfg
         self.test_cfg = dict(test_cfg) if test_cfg else {}
+        self.blending = blending_from(train_cfg)
         self.init_weights()
 
     @property
@@ -35,6 +50,8 @@ class Recognizer2D(nn.Module):
         if return_loss:
             if label is None:
                 raise ValueError('Label should not be None.')
+            if self.blending is not None:                   # UPSTREAM BaseRecognizer.forward: training only, before forward_train
+                imgs, label = self.blending(imgs, label)
             return self.forward_train(imgs, label, **kwargs)
         return self.forward_test(imgs, **kwargs)
 
@@ -51,8 +68,14 @@ class Recognizer2D(nn.Module):
         x, batches, num_segs = self._frames(imgs)
         feat = self.backbone(x)
         cls_score = self.cls_head(feat, num_segs)
-        gt_labels = labels.squeeze()
+        gt_labels = hard_labels(labels)
         return dict(self.cls_head.loss(cls_score, gt_labels, **kwargs))
+
+    def forward_test(self, imgs):
+        """UPSTREAM Recognizer2D.forward_test without its ``.cpu().numpy()``: the clip-averaged scores stay on the device."""
+        if self.test_cfg.get('fcn_test', False):
+            raise NotImplementedError('fcn_test is not on the HIP path')
+        return self._do_test(imgs)
 
     def _do_test(self, imgs):
         x, batches, num_segs = self._frames(imgs)
@@ -83,11 +106,6 @@ class CILRecognizer2D(Recognizer2D):
 
     def forward_train(self, imgs, labels, **kwargs):
         return super().forward_train(imgs, labels, num_classes=self.cls_head.num_classes, **kwargs)
-
-    def forward_test(self, imgs):
-        if self.test_cfg.get('fcn_test', False):
-            raise NotImplementedError('fcn_test is not used by any CIL config')
-        return self._do_test(imgs)
 
     def update_fc(self, nb_classes):
         self.cls_head.update_fc(nb_classes)

@@ -82,6 +82,7 @@ BACKBONES = Registry('backbone')
 HEADS = Registry('head')
 LOSSES = Registry('loss')
 OPTIMIZER_BUILDERS = Registry('optimizer builder')
+BLENDINGS = Registry('blending')
 MODELS = RECOGNIZERS
 
 
@@ -95,6 +96,11 @@ def build_head(cfg):
 
 def build_loss(cfg):
     return LOSSES.build(cfg)
+
+
+def build_blending(cfg):
+    """``train_cfg['blending']`` -> the batch blending (UPSTREAM mmaction.datasets.builder.build_blending, called by BaseRecognizer)."""
+    return BLENDINGS.build(cfg)
 
 
 def build_recognizer(cfg, train_cfg=None, test_cfg=None):

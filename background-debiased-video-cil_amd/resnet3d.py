@@ -27,6 +27,7 @@ import torch.nn as nn
 from . import functional as Fn
 from . import kernels as K
 from .heads import AvgConsensus, HipDropout  # noqa: F401
+from .recognizer import blending_from, hard_labels
 from .registry import BACKBONES, HEADS, RECOGNIZERS, build_backbone, build_head, build_loss
 from .resnet_tsm import ResStage, _ResBlock
 
@@ -385,6 +386,7 @@ class Recognizer3D(nn.Module):
         self.cls_head = build_head(cls_head) if cls_head else None
         self.train_cfg = train_cfg
         self.test_cfg = dict(test_cfg) if test_cfg else {}
+        self.blending = blending_from(train_cfg)
         self.backbone.init_weights()
         if self.cls_head is not None:
             self.cls_head.init_weights()
@@ -393,13 +395,15 @@ class Recognizer3D(nn.Module):
         if return_loss:
             if label is None:
                 raise ValueError('Label should not be None.')
+            if self.blending is not None:                   # UPSTREAM BaseRecognizer.forward: training only, before forward_train
+                imgs, label = self.blending(imgs, label)
             return self.forward_train(imgs, label, **kwargs)
         return self.forward_test(imgs, **kwargs)
 
     def forward_train(self, imgs, labels, **kwargs):
         imgs = imgs.reshape((-1,) + imgs.shape[2:])
         cls_score = self.cls_head(self.backbone(imgs))
-        return dict(self.cls_head.loss(cls_score, labels.squeeze(), **kwargs))
+        return dict(self.cls_head.loss(cls_score, hard_labels(labels), **kwargs))
 
     def forward_test(self, imgs):
         batches, num_segs = imgs.shape[0], imgs.shape[1]

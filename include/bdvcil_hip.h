@@ -680,6 +680,27 @@ int bdv_gradcam_render(const float* map, const float* minmax, int B, int T, int 
                        uint8_t* overlay, const int32_t* box_off, const int32_t* box_off_host, const float* boxes,
                        const float* boxes_host, int nbox, float* sums, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- clip blending: train_cfg.blending (Mixup / CutMix) and VideoMix ---------------------------------------------------------
+ * A sample is one contiguous blob of outer x H x W x inner floats, the pixel grid in the middle: (B, T, 3, H, W) has outer = T * 3,
+ * inner = 1; the NHWC4 frames (B * T, H, W, 4) have outer = T, inner = 4; the 3-D recognizer's (B, clips, 3, T, H, W) has outer =
+ * clips * 3 * T, inner = 1.  perm: device int64 (B), every entry in [0, B) (the caller checks its host copy before the upload).
+ * Sample bases and box rows need only 4-byte alignment: 16-byte accesses are used where an address allows them.
+ *
+ * UPSTREAM mmaction/datasets/blending_utils.py MixupBlending.do_blending (`lam * imgs + (1 - lam) * imgs[rand_index, :]`; reached
+ * from configs/recognition/tsm/tsm_r50_mixup_1x1x8_50e_sthv1_rgb.py:24-25): out[b] = lam * x[b] + (1 - lam) * x[perm[b]], 1 - lam
+ * formed in fp32, both products and the sum rounded to fp32 (no fused multiply-add): torch's expression bit for bit.  out must not
+ * overlap x. */
+int bdv_blend_mix_f32(const float* x, const int64_t* perm, float lam, float* out, int B, int64_t sample_elems, void* stream);
+/* UPSTREAM CutmixBlending.do_blending (`imgs[:, ..., bby1:bby2, bbx1:bbx2] = imgs[rand_index, ..., bby1:bby2, bbx1:bbx2]`;
+ * configs/recognition/tsm/tsm_r50_cutmix_1x1x8_50e_sthv1_rgb.py:25-26) and tubemix (libs/cil/icarl_video_mix.py:59), in place:
+ * afterwards x[b, :, r1:r2, c1:c2, :] holds what x[perm[b], :, r1:r2, c1:c2, :] held BEFORE the call, for any index vector (cycles of
+ * any length, repeats; perm[b] == b costs nothing).  Two launches: the source boxes are packed into `scratch` per destination, then
+ * written into the boxes: 4 x the box bytes.  0 <= r1 <= r2 <= H, 0 <= c1 <= c2 <= W; an empty box returns at once.  inner: 1 | 4.
+ * scratch: 16-byte aligned, at least bdv_blend_box_scratch_bytes(...) bytes (0 for an empty box). */
+size_t bdv_blend_box_scratch_bytes(int B, int outer, int inner, int r1, int c1, int r2, int c2);
+int bdv_blend_box_f32(float* x, const int64_t* perm, int B, int outer, int H, int W, int inner, int r1, int c1, int r2, int c2,
+                      void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- optimizer: multi-tensor global-norm clip + SGD(momentum, wd) ---------------------------
  * torch.optim.SGD built at libs/cil/cil.py:467 with the groups of libs/models/cil_heads/tsm.py:273-303
  * and PL gradient_clip_val (cil.py:743).  Tables are device arrays, one entry per tensor. */
