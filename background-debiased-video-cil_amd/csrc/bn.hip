@@ -36,37 +36,105 @@ BnGrid bn_grid(int64_t M, int C) {
 
 bool bn_c_ok(int C) { return C >= 64 && (C % 256 == 0 || C == 64 || C == 128); }
 
+// ---- float4 arithmetic: every kernel below forms its sums and gradients with these, so one edit here changes them all ------------
+__device__ __forceinline__ void add4(float4& s, const float4 v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+__device__ __forceinline__ float4 mul4(const float4 a, const float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+// s += a * b
+__device__ __forceinline__ void acc_mul4(float4& s, const float4 a, const float4 b) {
+  s.x += a.x * b.x; s.y += a.y * b.y; s.z += a.z * b.z; s.w += a.w * b.w;
+}
+// The BatchNorm arithmetic, per element: the normalised value xhat, and the gradient of the train-mode BatchNorm with a, b, c =
+// coef[0..2] (bn_bwd_finalize_tail).  The float4 forms below go through these component by component, each component's chain
+// complete before the next starts (the order the kernels were compiled from before they shared this text).
+__device__ __forceinline__ float bn_xhat(float v, float mu, float is) { return (v - mu) * is; }
+__device__ __forceinline__ float bn_dx(float a, float b, float c, float g, float v, float mu, float is) {
+  return a * (g - b - bn_xhat(v, mu, is) * c);
+}
+__device__ __forceinline__ float4 bn_xhat4(const float4 v, const float4 mu, const float4 is) {
+  return make_float4(bn_xhat(v.x, mu.x, is.x), bn_xhat(v.y, mu.y, is.y), bn_xhat(v.z, mu.z, is.z), bn_xhat(v.w, mu.w, is.w));
+}
+// s += g * xhat: the second sum of every backward statistics pass
+__device__ __forceinline__ void acc_g_xhat4(float4& s, const float4 g, const float4 v, const float4 mu, const float4 is) {
+  s.x += g.x * bn_xhat(v.x, mu.x, is.x);
+  s.y += g.y * bn_xhat(v.y, mu.y, is.y);
+  s.z += g.z * bn_xhat(v.z, mu.z, is.z);
+  s.w += g.w * bn_xhat(v.w, mu.w, is.w);
+}
+__device__ __forceinline__ float4 bn_dx4(const float4 a, const float4 b, const float4 c, const float4 g, const float4 v, const float4 mu,
+                                         const float4 is) {
+  float4 d;
+  d.x = bn_dx(a.x, b.x, c.x, g.x, v.x, mu.x, is.x);
+  d.y = bn_dx(a.y, b.y, c.y, g.y, v.y, mu.y, is.y);
+  d.z = bn_dx(a.z, b.z, c.z, g.z, v.z, mu.z, is.z);
+  d.w = bn_dx(a.w, b.w, c.w, g.w, v.w, mu.w, is.w);
+  return d;
+}
+
+// ---- row blocks: the decomposition of the column reductions over [M][C] ----------------------------------------------------------
+// Block (x, y) of grid (RB, CC) owns rows [r0, r1) of the CVB float4 columns from y * CVB; thread tid is row lane rl = tid / CVB of
+// column cv = tid % CVB and walks rows r0 + rl, r0 + rl + RL, ...  (bn_grid: CVB * RL == 256)
+struct RowBlock {
+  int cv, rl, c4, CV;   // column in the block, row lane, float4 column index in the tensor, float4 columns of the tensor
+  int64_t r0, r1;
+  __device__ __forceinline__ RowBlock(int64_t M, int C, int CVB, int rows_per_block) {
+    const int tid = threadIdx.x;
+    cv = tid % CVB;
+    rl = tid / CVB;
+    c4 = blockIdx.y * CVB + cv;
+    r0 = (int64_t)blockIdx.x * rows_per_block;
+    r1 = r0 + rows_per_block;
+    if (r1 > M) r1 = M;
+    CV = C / 4;
+  }
+};
+// The N sums of a block's row lanes -> row blockIdx.x of the N partial slabs [RB][CV]: row lane 0 of each column adds lanes
+// 1 .. RL - 1 in lane order and stores.  (blockIdx.x is read behind the barrier, where the kernels read it before they shared this
+// text: read at the top, the compiler forms the LDS addresses of the loop another way.)
+template <int N>
+__device__ __forceinline__ void rowblock_colsum_store(float4 (&s)[N], const RowBlock& rb, int CVB, int RL, float* const (&slab)[N]) {
+  static_assert(N == 2 || N == 3, "two or three sums");
+  __shared__ float4 sh[N][256];
+  const int tid = threadIdx.x;
+  sh[0][tid] = s[0];
+  sh[1][tid] = s[1];
+  if constexpr (N == 3) sh[2][tid] = s[2];
+  __syncthreads();
+  if (rb.rl == 0) {
+    for (int k = 1; k < RL; ++k) {   // N is 2 or 3, written out: with loops over n in here the compiler unrolls the k loop another way
+      const float4 a = sh[0][k * CVB + rb.cv], b = sh[1][k * CVB + rb.cv];
+      float4 e;
+      if constexpr (N == 3) e = sh[2][k * CVB + rb.cv];
+      add4(s[0], a);
+      add4(s[1], b);
+      if constexpr (N == 3) add4(s[2], e);
+    }
+    // The stores keep the two forms the kernels had: the offset expression per store for two sums, one named
+    // offset for three.  Either form for both N changes the code of the kernels that had the other.
+    if constexpr (N == 2) {
+      reinterpret_cast<float4*>(slab[0])[(int64_t)blockIdx.x * rb.CV + rb.c4] = s[0];
+      reinterpret_cast<float4*>(slab[1])[(int64_t)blockIdx.x * rb.CV + rb.c4] = s[1];
+    } else {
+      const int64_t o = (int64_t)blockIdx.x * rb.CV + rb.c4;
+      reinterpret_cast<float4*>(slab[0])[o] = s[0];
+      reinterpret_cast<float4*>(slab[1])[o] = s[1];
+      reinterpret_cast<float4*>(slab[2])[o] = s[2];
+    }
+  }
+}
+
 // ---- forward statistics ------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ y, float* __restrict__ psum,
                                                           float* __restrict__ psq, int64_t M, int C, int CVB, int RL,
                                                           int rows_per_block) {
-  __shared__ float4 sh[2][256];
-  const int tid = threadIdx.x;
-  const int cv = tid % CVB, rl = tid / CVB;
-  const int c4 = blockIdx.y * CVB + cv;  // float4 column index
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > M) r1 = M;
-  const int CV = C / 4;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
+  const RowBlock rb(M, C, CVB, rows_per_block);
+  float4 s[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};   // sum y, sum y^2
   const float4* yp = reinterpret_cast<const float4*>(y);
-  for (int64_t r = r0 + rl; r < r1; r += RL) {
-    const float4 v = yp[r * CV + c4];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    q.x += v.x * v.x; q.y += v.y * v.y; q.z += v.z * v.z; q.w += v.w * v.w;
+  for (int64_t r = rb.r0 + rb.rl; r < rb.r1; r += RL) {
+    const float4 v = yp[r * rb.CV + rb.c4];
+    add4(s[0], v);
+    acc_mul4(s[1], v, v);
   }
-  sh[0][tid] = s;
-  sh[1][tid] = q;
-  __syncthreads();
-  if (rl == 0) {
-    for (int k = 1; k < RL; ++k) {
-      const float4 a = sh[0][k * CVB + cv], b = sh[1][k * CVB + cv];
-      s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
-      q.x += b.x; q.y += b.y; q.z += b.z; q.w += b.w;
-    }
-    reinterpret_cast<float4*>(psum)[(int64_t)blockIdx.x * CV + c4] = s;
-    reinterpret_cast<float4*>(psq)[(int64_t)blockIdx.x * CV + c4] = q;
-  }
+  rowblock_colsum_store<2>(s, rb, CVB, RL, {psum, psq});
 }
 
 // Fixed-order column sum of two [RB][C] fp32 slabs in fp64: 4 channels x FIN_LANES row-lanes per block (1024 threads).
@@ -77,8 +145,11 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
 // lanes per channel with four independent chains each; the lane sums are combined in a fixed order (16 groups of 16).
 constexpr int FIN_LANES = 256;
 
-__device__ __forceinline__ void slab_colsum2(const float* __restrict__ a, const float* __restrict__ b, int RB, int C, int c,
-                                             int rl, double (*sh)[FIN_LANES][5], double& sa, double& sb) {
+// Row lane rl of channel c: the fp64 sums of rows rl, rl + 256, ... of the two slabs, as four independent chains that are combined at
+// the end.  (It accumulates in locals and assigns xo / yo last: with the outputs initialised through the references at the top, the
+// four finalize kernels came out with other code.)
+__device__ __forceinline__ void slab_lane_chain(const float* __restrict__ a, const float* __restrict__ b, int RB, int C, int c, int rl,
+                                                double& xo, double& yo) {
   double x = 0.0, y = 0.0;
   if (c < C) {
     double x1 = 0.0, x2 = 0.0, x3 = 0.0, y1 = 0.0, y2 = 0.0, y3 = 0.0;
@@ -98,6 +169,14 @@ __device__ __forceinline__ void slab_colsum2(const float* __restrict__ a, const 
     x = (x + x1) + (x2 + x3);
     y = (y + y1) + (y2 + y3);
   }
+  xo = x;
+  yo = y;
+}
+
+__device__ __forceinline__ void slab_colsum2(const float* __restrict__ a, const float* __restrict__ b, int RB, int C, int c,
+                                             int rl, double (*sh)[FIN_LANES][5], double& sa, double& sb) {
+  double x, y;
+  slab_lane_chain(a, b, RB, C, c, rl, x, y);
   const int cl = threadIdx.x & 3;
   sh[0][rl][cl] = x;
   sh[1][rl][cl] = y;
@@ -127,10 +206,10 @@ __device__ __forceinline__ void slab_colsum2(const float* __restrict__ a, const 
 
 // ---- the same column sum over S blocks per channel group (S in {2, 4, 8, 16}) ---------------------------------------------
 // The LANES are split over blocks, not the rows: block (cb, s) runs row-lanes [s * 256 / S, (s + 1) * 256 / S) of its four
-// channels -- every lane does exactly the chain it does in slab_colsum2 -- reduces its 16 / S groups of 16 lanes in lane order
+// channels -- every lane runs slab_lane_chain for the lane it plays -- reduces its 16 / S groups of 16 lanes in lane order
 // and publishes those group sums (fp64) to `scratch` [2][C / 4][16][4].  The last block to arrive for cb (one ticket from an
 // atomic add on tickets[cb]; nobody spins, nobody waits for anybody) reads the 16 group sums in index order and does what the
-// tail of slab_colsum2 does: the same sequence of fp64 additions, hence the same bits.
+// tail of slab_colsum2 does: with slab_lane_chain shared, the same sequence of fp64 additions, hence the same bits.
 // Hand-off, the write-through form: every group sum is stored with a relaxed agent-scope atomic store (sc1: it goes through to
 // memory, so no release fence and no L2 write-back is needed) -> every storing wave drains vmcnt -> barrier -> one lane takes the
 // ticket with a relaxed agent-scope fetch_add; the block that draws S - 1 stores 0 back to the ticket (launches of one stream are
@@ -143,25 +222,8 @@ __device__ __forceinline__ bool slab_colsum2_split(const float* __restrict__ a, 
                                                    unsigned* tickets, double& sa, double& sb) {
   const int nl = FIN_LANES / S;        // lanes of this block
   const int rl = s * nl + ll;          // the lane of slab_colsum2 this thread plays
-  double x = 0.0, y = 0.0;
-  if (c < C) {
-    double x1 = 0.0, x2 = 0.0, x3 = 0.0, y1 = 0.0, y2 = 0.0, y3 = 0.0;
-    int r = rl;
-    for (; r + 3 * FIN_LANES < RB; r += 4 * FIN_LANES) {
-      const float a0 = a[(int64_t)r * C + c], a1 = a[(int64_t)(r + FIN_LANES) * C + c];
-      const float a2 = a[(int64_t)(r + 2 * FIN_LANES) * C + c], a3 = a[(int64_t)(r + 3 * FIN_LANES) * C + c];
-      const float b0 = b[(int64_t)r * C + c], b1 = b[(int64_t)(r + FIN_LANES) * C + c];
-      const float b2 = b[(int64_t)(r + 2 * FIN_LANES) * C + c], b3 = b[(int64_t)(r + 3 * FIN_LANES) * C + c];
-      x += (double)a0; x1 += (double)a1; x2 += (double)a2; x3 += (double)a3;
-      y += (double)b0; y1 += (double)b1; y2 += (double)b2; y3 += (double)b3;
-    }
-    for (; r < RB; r += FIN_LANES) {
-      x += (double)a[(int64_t)r * C + c];
-      y += (double)b[(int64_t)r * C + c];
-    }
-    x = (x + x1) + (x2 + x3);
-    y = (y + y1) + (y2 + y3);
-  }
+  double x, y;
+  slab_lane_chain(a, b, RB, C, c, rl, x, y);
   const int cl = threadIdx.x & 3;
   const int cb = blockIdx.x;
   sh[0][ll][cl] = x;
@@ -294,6 +356,15 @@ __device__ __forceinline__ float4 apply_nibble(float4 g, unsigned nib) {
   g.w = (nib & 8u) ? g.w : 0.f;
   return g;
 }
+// The gradient behind a ReLU.  MODE (the kernels' RELU / SIGN): 0 = no ReLU, 1 = the forward's 1-bit mask at flat float4 index i,
+// 2 = the sign bits the caller computes (sign2(): derive_nibble of y, or nibble_gt0 of the activation); sign2 runs for MODE 2 only.
+// (The callers capture by value: with captures by reference half of the instantiations came out with other code.)
+template <int MODE, class F>
+__device__ __forceinline__ float4 relu_grad(const float4 g, const uint32_t* __restrict__ mask, int64_t i, F&& sign2) {
+  if constexpr (MODE == 1) return apply_nibble(g, mask_nibble(mask, i));
+  else if constexpr (MODE == 2) return apply_nibble(g, sign2());
+  else return g;
+}
 
 // res_scale / res_shift (optional): the residual is itself a raw conv output that still needs its own BatchNorm
 // (the downsample branch of a block): r = res * res_scale + res_shift is formed here instead of in a pass of its own.
@@ -327,7 +398,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const void* __restrict__ 
           const float4 rs = res_scale[c4], rb = res_shift[c4];
           q.x = q.x * rs.x + rb.x; q.y = q.y * rs.y + rb.y; q.z = q.z * rs.z + rb.z; q.w = q.w * rs.w + rb.w;
         }
-        o[u].x += q.x; o[u].y += q.y; o[u].z += q.z; o[u].w += q.w;
+        add4(o[u], q);
       }
       if (RELU) {
         bits |= nibble_gt0(o[u]) << (4 * u);
@@ -354,41 +425,22 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const void* __restr
                                                               float* __restrict__ p2, int64_t M, int C, int CVB, int RL,
                                                               int rows_per_block, const float* __restrict__ rscale,
                                                               const float* __restrict__ rshift) {
-  __shared__ float4 sh[2][256];
-  const int tid = threadIdx.x;
-  const int cv = tid % CVB, rl = tid / CVB;
-  const int c4 = blockIdx.y * CVB + cv;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > M) r1 = M;
-  const int CV = C / 4;
+  const RowBlock rb(M, C, CVB, rows_per_block);
+  const int c4 = rb.c4;
   const float4 mu = reinterpret_cast<const float4*>(mean)[c4];
   const float4 is = reinterpret_cast<const float4*>(invstd)[c4];
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-  for (int64_t r = r0 + rl; r < r1; r += RL) {
-    const int64_t i = r * CV + c4;
+  float4 s[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};   // sum g, sum g * xhat
+  for (int64_t r = rb.r0 + rb.rl; r < rb.r1; r += RL) {
+    const int64_t i = r * rb.CV + c4;
     float4 g = act_ld4<ES>(dout, i);
     const float4 v = act_ld4<ES>(y, i);
-    if (RELU == 1) g = apply_nibble(g, mask_nibble(mask, i));
-    if (RELU == 2) g = apply_nibble(g, derive_nibble(v, reinterpret_cast<const float4*>(rscale)[c4], reinterpret_cast<const float4*>(rshift)[c4]));
-    s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
-    s2.x += g.x * ((v.x - mu.x) * is.x);
-    s2.y += g.y * ((v.y - mu.y) * is.y);
-    s2.z += g.z * ((v.z - mu.z) * is.z);
-    s2.w += g.w * ((v.w - mu.w) * is.w);
+    g = relu_grad<RELU>(g, mask, i, [=] {
+      return derive_nibble(v, reinterpret_cast<const float4*>(rscale)[c4], reinterpret_cast<const float4*>(rshift)[c4]);
+    });
+    add4(s[0], g);
+    acc_g_xhat4(s[1], g, v, mu, is);
   }
-  sh[0][tid] = s1;
-  sh[1][tid] = s2;
-  __syncthreads();
-  if (rl == 0) {
-    for (int k = 1; k < RL; ++k) {
-      const float4 a = sh[0][k * CVB + cv], b = sh[1][k * CVB + cv];
-      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
-      s2.x += b.x; s2.y += b.y; s2.z += b.z; s2.w += b.w;
-    }
-    reinterpret_cast<float4*>(p1)[(int64_t)blockIdx.x * CV + c4] = s1;
-    reinterpret_cast<float4*>(p2)[(int64_t)blockIdx.x * CV + c4] = s2;
-  }
+  rowblock_colsum_store<2>(s, rb, CVB, RL, {p1, p2});
 }
 
 // coef[0][c] = gamma*invstd, coef[1][c] = sum(g)/M, coef[2][c] = sum(g*xhat)/M
@@ -443,17 +495,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void* __restric
     for (int u = 0; u < U; ++u) {
       const int64_t i = iu * U + u;
       const int c4 = (int)(i % CV);
-      float4 g = gg[u];
       const float4 v = vv[u], mu = mean[c4], is = invstd[c4];
-      if (RELU == 1) g = apply_nibble(g, mask_nibble(mask, i));
-      if (RELU == 2) g = apply_nibble(g, derive_nibble(v, rscale[c4], rshift[c4]));
+      const float4 g = relu_grad<RELU>(gg[u], mask, i, [=] { return derive_nibble(v, rscale[c4], rshift[c4]); });
       const float4 a = coef[c4], b = coef[CV + c4], c = coef[2 * CV + c4];
-      float4 d;
-      d.x = a.x * (g.x - b.x - ((v.x - mu.x) * is.x) * c.x);
-      d.y = a.y * (g.y - b.y - ((v.y - mu.y) * is.y) * c.y);
-      d.z = a.z * (g.z - b.z - ((v.z - mu.z) * is.z) * c.z);
-      d.w = a.w * (g.w - b.w - ((v.w - mu.w) * is.w) * c.w);
-      dd[u] = d;
+      dd[u] = bn_dx4(a, b, c, g, v, mu, is);
     }
     act_st16<ES>(dy, iu, dd);
   }
@@ -461,8 +506,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void* __restric
 
 // ---- two BatchNorms behind one masked gradient (a block with a downsample branch) ----------------------------------------
 // g = dout (.) mask enters the block's last main unit (ya) and the downsample BatchNorm (yb).  Both kernels read dout and the mask
-// once; block / lane decomposition and every expression are those of bn_bwd_partial_kernel<1> / bn_bwd_apply_kernel<1>, so the
-// partial rows and the gradients carry the bits of two separate bdv_bn_backward calls.
+// once; they share RowBlock, rowblock_colsum_store, acc_g_xhat4 and bn_dx4 with bn_bwd_partial_kernel<1> / bn_bwd_apply_kernel<1>,
+// so the partial rows and the gradients carry the bits of two separate bdv_bn_backward calls.
 template <int ES = 4>
 __global__ __launch_bounds__(256) void bn_bwd_partial_pair_kernel(const void* __restrict__ dout, const uint32_t* __restrict__ mask,
                                                                    const void* __restrict__ ya, const float* __restrict__ mean_a,
@@ -471,51 +516,25 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_pair_kernel(const void* __
                                                                    float* __restrict__ p1, float* __restrict__ pa2,
                                                                    float* __restrict__ pb2, int64_t M, int C, int CVB, int RL,
                                                                    int rows_per_block) {
-  __shared__ float4 sh[3][256];
-  const int tid = threadIdx.x;
-  const int cv = tid % CVB, rl = tid / CVB;
-  const int c4 = blockIdx.y * CVB + cv;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > M) r1 = M;
-  const int CV = C / 4;
+  const RowBlock rb(M, C, CVB, rows_per_block);
+  const int c4 = rb.c4;
   const float4 mu = reinterpret_cast<const float4*>(mean_a)[c4];
   const float4 is = reinterpret_cast<const float4*>(invstd_a)[c4];
   const float4 mub = reinterpret_cast<const float4*>(mean_b)[c4];
   const float4 isb = reinterpret_cast<const float4*>(invstd_b)[c4];
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1, t2 = s1;   // sum(g) is the same chain for both BatchNorms: one slab
-  for (int64_t r = r0 + rl; r < r1; r += RL) {
-    const int64_t i = r * CV + c4;
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 s[3] = {z4, z4, z4};   // sum g (the same chain for both BatchNorms: one slab), sum g * xhat_a, sum g * xhat_b
+  for (int64_t r = rb.r0 + rb.rl; r < rb.r1; r += RL) {
+    const int64_t i = r * rb.CV + c4;
     float4 g = act_ld4<ES>(dout, i);
     const float4 v = act_ld4<ES>(ya, i);
     const float4 w = act_ld4<ES>(yb, i);
     g = apply_nibble(g, mask_nibble(mask, i));
-    s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
-    s2.x += g.x * ((v.x - mu.x) * is.x);
-    s2.y += g.y * ((v.y - mu.y) * is.y);
-    s2.z += g.z * ((v.z - mu.z) * is.z);
-    s2.w += g.w * ((v.w - mu.w) * is.w);
-    t2.x += g.x * ((w.x - mub.x) * isb.x);
-    t2.y += g.y * ((w.y - mub.y) * isb.y);
-    t2.z += g.z * ((w.z - mub.z) * isb.z);
-    t2.w += g.w * ((w.w - mub.w) * isb.w);
+    add4(s[0], g);
+    acc_g_xhat4(s[1], g, v, mu, is);
+    acc_g_xhat4(s[2], g, w, mub, isb);
   }
-  sh[0][tid] = s1;
-  sh[1][tid] = s2;
-  sh[2][tid] = t2;
-  __syncthreads();
-  if (rl == 0) {
-    for (int k = 1; k < RL; ++k) {
-      const float4 a = sh[0][k * CVB + cv], b = sh[1][k * CVB + cv], e = sh[2][k * CVB + cv];
-      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
-      s2.x += b.x; s2.y += b.y; s2.z += b.z; s2.w += b.w;
-      t2.x += e.x; t2.y += e.y; t2.z += e.z; t2.w += e.w;
-    }
-    const int64_t o = (int64_t)blockIdx.x * CV + c4;
-    reinterpret_cast<float4*>(p1)[o] = s1;
-    reinterpret_cast<float4*>(pa2)[o] = s2;
-    reinterpret_cast<float4*>(pb2)[o] = t2;
-  }
+  rowblock_colsum_store<3>(s, rb, CVB, RL, {p1, pa2, pb2});
 }
 
 template <bool NT = false, int ES = 4>
@@ -541,22 +560,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pair_kernel(const void* __re
       {
         const float4 v = vv[u], mu = mean_a[c4], is = invstd_a[c4];
         const float4 a = coef_a[c4], b = coef_a[CV + c4], c = coef_a[2 * CV + c4];
-        float4 d;
-        d.x = a.x * (g.x - b.x - ((v.x - mu.x) * is.x) * c.x);
-        d.y = a.y * (g.y - b.y - ((v.y - mu.y) * is.y) * c.y);
-        d.z = a.z * (g.z - b.z - ((v.z - mu.z) * is.z) * c.z);
-        d.w = a.w * (g.w - b.w - ((v.w - mu.w) * is.w) * c.w);
-        da[u] = d;
+        da[u] = bn_dx4(a, b, c, g, v, mu, is);
       }
       {
         const float4 v = ww[u], mu = mean_b[c4], is = invstd_b[c4];
         const float4 a = coef_b[c4], b = coef_b[CV + c4], c = coef_b[2 * CV + c4];
-        float4 d;
-        d.x = a.x * (g.x - b.x - ((v.x - mu.x) * is.x) * c.x);
-        d.y = a.y * (g.y - b.y - ((v.y - mu.y) * is.y) * c.y);
-        d.z = a.z * (g.z - b.z - ((v.z - mu.z) * is.z) * c.z);
-        d.w = a.w * (g.w - b.w - ((v.w - mu.w) * is.w) * c.w);
-        db[u] = d;
+        db[u] = bn_dx4(a, b, c, g, v, mu, is);
       }
     }
     act_st16<ES>(dya, iu, da);
@@ -567,7 +576,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pair_kernel(const void* __re
 // The same pass with R units per thread that share their channels: a thread's units lie L units apart, L = max(256, CV / U) a
 // multiple of both the block and the channel period, so the ten per-channel vectors of the two BatchNorms are loaded once per
 // thread instead of once per unit, and the 3 R streaming loads of a thread are in flight together.  A block covers R spans of
-// 4 KB.  Per element the expression is bn_bwd_apply_kernel's.
+// 4 KB.  Per element the gradient is bn_dx4, as in bn_bwd_apply_kernel.
 template <bool NT, int ES, int R>
 __global__ __launch_bounds__(256) void bn_bwd_apply_pair_rows_kernel(const void* __restrict__ dout, const uint32_t* __restrict__ mask,
                                                                       const void* __restrict__ ya, const float4* __restrict__ mean_a,
@@ -610,21 +619,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pair_rows_kernel(const void*
         const float4 g = apply_nibble(gg[k][u], nib[k][u]);
         {
           const float4 v = vv[k][u], mu = mua[u], is = isa[u], a = aa[u], b = ba[u], c = ca[u];
-          float4 d;
-          d.x = a.x * (g.x - b.x - ((v.x - mu.x) * is.x) * c.x);
-          d.y = a.y * (g.y - b.y - ((v.y - mu.y) * is.y) * c.y);
-          d.z = a.z * (g.z - b.z - ((v.z - mu.z) * is.z) * c.z);
-          d.w = a.w * (g.w - b.w - ((v.w - mu.w) * is.w) * c.w);
-          da[u] = d;
+          da[u] = bn_dx4(a, b, c, g, v, mu, is);
         }
         {
           const float4 v = ww[k][u], mu = mub[u], is = isb[u], a = ab[u], b = bb[u], c = cb[u];
-          float4 d;
-          d.x = a.x * (g.x - b.x - ((v.x - mu.x) * is.x) * c.x);
-          d.y = a.y * (g.y - b.y - ((v.y - mu.y) * is.y) * c.y);
-          d.z = a.z * (g.z - b.z - ((v.z - mu.z) * is.z) * c.z);
-          d.w = a.w * (g.w - b.w - ((v.w - mu.w) * is.w) * c.w);
-          db[u] = d;
+          db[u] = bn_dx4(a, b, c, g, v, mu, is);
         }
       }
       act_st16<ES>(dya, iu, da);
@@ -673,17 +672,13 @@ __global__ __launch_bounds__(256) void bn_bwd_pool_kernel(const void* __restrict
         if (!ok[k]) continue;
         const float4 gv = apply_nibble(g[k], mask_nibble(mask, pix[k]));
         const float4 v = y[pix[k]];
-        const float4 xh = make_float4((v.x - mu.x) * is.x, (v.y - mu.y) * is.y, (v.z - mu.z) * is.z, (v.w - mu.w) * is.w);
+        const float4 xh = bn_xhat4(v, mu, is);   // ahead of the branch, as before this kernel took the helpers: inside the else,
+                                                 // bn_bwd_pool_kernel<true, 2> comes out with other code of the same size
         if (APPLY) {
-          float4 d;
-          d.x = ca.x * (gv.x - cb.x - xh.x * cc.x);
-          d.y = ca.y * (gv.y - cb.y - xh.y * cc.y);
-          d.z = ca.z * (gv.z - cb.z - xh.z * cc.z);
-          d.w = ca.w * (gv.w - cb.w - xh.w * cc.w);
-          dy[pix[k]] = d;
+          dy[pix[k]] = bn_dx4(ca, cb, cc, gv, v, mu, is);
         } else {
-          s1.x += gv.x; s1.y += gv.y; s1.z += gv.z; s1.w += gv.w;
-          s2.x += gv.x * xh.x; s2.y += gv.y * xh.y; s2.z += gv.z * xh.z; s2.w += gv.w * xh.w;
+          add4(s1, gv);
+          acc_mul4(s2, gv, xh);
         }
       }
     }
@@ -695,8 +690,8 @@ __global__ __launch_bounds__(256) void bn_bwd_pool_kernel(const void* __restrict
     if (tid < CV) {
       for (int k = 1; k < 256 / CV; ++k) {
         const float4 a = sh[0][k * CV + tid], b = sh[1][k * CV + tid];
-        s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
-        s2.x += b.x; s2.y += b.y; s2.z += b.z; s2.w += b.w;
+        add4(s1, a);
+        add4(s2, b);
       }
       const int64_t slab_row = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
       reinterpret_cast<float4*>(p1)[slab_row * CV + tid] = s1;
@@ -727,19 +722,17 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const void* __restrict
     for (int u = 0; u < U; ++u) {
       const int64_t i = iu * U + u;
       const float4 sc = scale[(int)(i % CV)];
-      float4 g = gg[u];
-      if (SIGN == 1) g = apply_nibble(g, mask_nibble(mask, i));
-      if (SIGN == 2) g = apply_nibble(g, nibble_gt0(aa[u]));
+      const float4 g = relu_grad<SIGN>(gg[u], mask, i, [=] { return nibble_gt0(aa[u]); });
       gg[u] = g;
-      dd[u] = make_float4(g.x * sc.x, g.y * sc.y, g.z * sc.z, g.w * sc.w);
+      dd[u] = mul4(g, sc);
     }
     act_st16<ES>(dy, iu, dd);
     if (DZ) act_st16<ES>(dz, iu, gg);
   }
 }
 
-// With parameter gradients: bn_bwd_partial_kernel's block / lane decomposition and its two sums, expression for expression, with
-// the running statistics as mean / invstd; the lane that has g in registers writes dy (and dz) on the way.
+// With parameter gradients: bn_bwd_partial_kernel's block / lane decomposition and its two sums (RowBlock, add4, acc_g_xhat4,
+// rowblock_colsum_store), with the running statistics as mean / invstd; the lane that has g in registers writes dy (and dz) on the way.
 template <int SIGN, bool DZ, bool NT = false, int ES = 4>
 __global__ __launch_bounds__(256) void bn_eval_bwd_stats_kernel(const void* __restrict__ dout, const uint32_t* __restrict__ mask,
                                                                  const void* __restrict__ act, const void* __restrict__ y,
@@ -747,44 +740,25 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_stats_kernel(const void* __re
                                                                  const float* __restrict__ invstd, void* __restrict__ dy,
                                                                  void* __restrict__ dz, float* __restrict__ p1, float* __restrict__ p2,
                                                                  int64_t M, int C, int CVB, int RL, int rows_per_block) {
-  __shared__ float4 sh[2][256];
-  const int tid = threadIdx.x;
-  const int cv = tid % CVB, rl = tid / CVB;
-  const int c4 = blockIdx.y * CVB + cv;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t r1 = r0 + rows_per_block;
-  if (r1 > M) r1 = M;
-  const int CV = C / 4;
+  const RowBlock rb(M, C, CVB, rows_per_block);
+  const int c4 = rb.c4;
   const float4 mu = reinterpret_cast<const float4*>(mean)[c4];
   const float4 is = reinterpret_cast<const float4*>(invstd)[c4];
   const float4 sc = reinterpret_cast<const float4*>(scale)[c4];
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-  for (int64_t r = r0 + rl; r < r1; r += RL) {
-    const int64_t i = r * CV + c4;
+  float4 s[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};   // sum g, sum g * xhat
+  for (int64_t r = rb.r0 + rb.rl; r < rb.r1; r += RL) {
+    const int64_t i = r * rb.CV + c4;
     float4 g = act_ld4<ES, NT>(dout, i);
     const float4 v = act_ld4<ES, NT>(y, i);
-    if (SIGN == 1) g = apply_nibble(g, mask_nibble(mask, i));
-    if (SIGN == 2) g = apply_nibble(g, nibble_gt0(act_ld4<ES>(act, i)));
-    act_st4<ES>(dy, i, make_float4(g.x * sc.x, g.y * sc.y, g.z * sc.z, g.w * sc.w));
+    float4 av;   // loaded here, not in the lambda: its copy of `act` would not be __restrict__
+    if (SIGN == 2) av = act_ld4<ES>(act, i);
+    g = relu_grad<SIGN>(g, mask, i, [=] { return nibble_gt0(av); });
+    act_st4<ES>(dy, i, mul4(g, sc));
     if (DZ) act_st4<ES>(dz, i, g);
-    s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
-    s2.x += g.x * ((v.x - mu.x) * is.x);
-    s2.y += g.y * ((v.y - mu.y) * is.y);
-    s2.z += g.z * ((v.z - mu.z) * is.z);
-    s2.w += g.w * ((v.w - mu.w) * is.w);
+    add4(s[0], g);
+    acc_g_xhat4(s[1], g, v, mu, is);
   }
-  sh[0][tid] = s1;
-  sh[1][tid] = s2;
-  __syncthreads();
-  if (rl == 0) {
-    for (int k = 1; k < RL; ++k) {
-      const float4 a = sh[0][k * CVB + cv], b = sh[1][k * CVB + cv];
-      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
-      s2.x += b.x; s2.y += b.y; s2.z += b.z; s2.w += b.w;
-    }
-    reinterpret_cast<float4*>(p1)[(int64_t)blockIdx.x * CV + c4] = s1;
-    reinterpret_cast<float4*>(p2)[(int64_t)blockIdx.x * CV + c4] = s2;
-  }
+  rowblock_colsum_store<2>(s, rb, CVB, RL, {p1, p2});
 }
 
 template <int ES = 4>
@@ -795,7 +769,7 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const void* __restrict__ 
     float4 d = apply_nibble(act_ld4<ES>(dout, i), mask_nibble(mask, i));
     if (add != nullptr) {
       const float4 a = act_ld4<ES>(add, i);
-      d.x += a.x; d.y += a.y; d.z += a.z; d.w += a.w;
+      d.x += a.x; d.y += a.y; d.z += a.z; d.w += a.w;   // (through add4 the bf16 instantiation takes two more VGPRs)
     }
     act_st4<ES>(g, i, d);
   }
@@ -858,29 +832,91 @@ int bn_fin_resolve(int S, int rows, int C, const void* scratch, size_t scratch_b
   return S;
 }
 
+// One block per channel group (`one`), or S blocks (`split`, which takes the group-sum scratch and the tickets behind `a...`)
+template <class K1, class KS, class... A>
+void launch_fin(K1 one, KS split, int C, int S, void* scratch, hipStream_t s, A... a) {
+  if (S == 1)
+    hipLaunchKernelGGL(one, dim3((C + 3) / 4), dim3(4 * FIN_LANES), 0, s, a...);
+  else
+    hipLaunchKernelGGL(split, dim3(C / 4, S), dim3(4 * FIN_LANES / S), 0, s, a..., (double*)((char*)scratch + FIN_TICKET_BYTES),
+                       (unsigned*)scratch);
+}
 void launch_bn_finalize(const float* psum, const float* psq, int rows, int64_t M, int C, const float* gamma, const float* beta, float eps,
                         float momentum, float* running_mean, float* running_var, float* save_mean, float* save_invstd, float* scale,
                         float* shift, int S, void* scratch, hipStream_t s) {
-  if (S == 1) {
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(4 * FIN_LANES), 0, s, psum, psq, rows, M, C, gamma, beta, eps, momentum,
-                       running_mean, running_var, save_mean, save_invstd, scale, shift);
-  } else {
-    hipLaunchKernelGGL(bn_finalize_split_kernel, dim3(C / 4, S), dim3(4 * FIN_LANES / S), 0, s, psum, psq, rows, M, C, gamma, beta, eps,
-                       momentum, running_mean, running_var, save_mean, save_invstd, scale, shift,
-                       (double*)((char*)scratch + FIN_TICKET_BYTES), (unsigned*)scratch);
-  }
+  launch_fin(bn_finalize_kernel, bn_finalize_split_kernel, C, S, scratch, s, psum, psq, rows, M, C, gamma, beta, eps, momentum,
+             running_mean, running_var, save_mean, save_invstd, scale, shift);
 }
-
 void launch_bn_bwd_finalize(const float* q1, const float* q2, int rows, int64_t M, int C, const float* gamma, const float* invstd,
                             float* dgamma, float* dbeta, float beta_acc, float* coef, int S, void* scratch, hipStream_t s) {
-  if (S == 1) {
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(4 * FIN_LANES), 0, s, q1, q2, rows, M, C, gamma, invstd, dgamma,
-                       dbeta, beta_acc, coef);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_finalize_split_kernel, dim3(C / 4, S), dim3(4 * FIN_LANES / S), 0, s, q1, q2, rows, M, C, gamma, invstd,
-                       dgamma, dbeta, beta_acc, coef, (double*)((char*)scratch + FIN_TICKET_BYTES),
-                       (unsigned*)scratch);
+  launch_fin(bn_bwd_finalize_kernel, bn_bwd_finalize_split_kernel, C, S, scratch, s, q1, q2, rows, M, C, gamma, invstd, dgamma, dbeta,
+             beta_acc, coef);
+}
+
+// ---- what the entry points share ------------------------------------------------------------------------------------------
+// grid of an elementwise pass over n4 groups of 4 channels: one 16-byte unit per thread (ActU: fp32 BDV_F32_UNITS groups, bf16 2)
+dim3 act_grid(int64_t n4, int act_dtype) { return dim3(ew_grid(act_dtype == BDV_ACT_BF16 ? n4 / 2 : n4 / BDV_F32_UNITS)); }
+
+// The workspace of bdv_bn_workspace_bytes: two partial slabs, then the 3*C apply coefficients
+struct BnWs {
+  float *p1, *p2, *coef;
+};
+int bn_ws_carve(void* workspace, size_t workspace_bytes, int C, const char* who, BnWs* w) {
+  if (workspace_bytes < bdv_bn_workspace_bytes(0, C)) {
+    bdv_set_error("%s: workspace too small", who);
+    return BDV_EWORKSPACE;
   }
+  w->p1 = (float*)workspace;
+  w->p2 = w->p1 + MAX_RB_TIMES_C;
+  w->coef = w->p2 + MAX_RB_TIMES_C;
+  return BDV_OK;
+}
+
+// The two column sums a backward finalize reads: the caller's tile sums [2][stat_rows][C] (the producer of dout, a dgrad epilogue,
+// already reduced per 128-row tile: no statistics pass) or the slabs p1 / p2 of this call's own pass, RB rows
+struct BnSums {
+  const float *q1, *q2;
+  int rows;
+  bool given;
+};
+BnSums bn_sums(const float* stat_partial, int stat_rows, int C, const float* p1, const float* p2, int RB) {
+  if (stat_partial != nullptr) return {stat_partial, stat_partial + (size_t)stat_rows * C, stat_rows, true};
+  return {p1, p2, RB, false};
+}
+
+// ---- template arguments from tables: the rows are the instantiations that exist, a launch looks its row up -----------------------
+template <class Row, int N, class P>
+int find_row(const Row (&table)[N], P&& match) {
+  for (int i = 0; i < N; ++i)
+    if (match(table[i])) return i;
+  return -1;
+}
+// bn_apply_kernel<RELU, RES, NT, NTR>: non-temporal loads only in the ReLU forms (BDVCIL_BN_NT: 1 = y, 2 = also the residual)
+struct BnApplyRow {
+  bool relu, res, nt, ntr;
+};
+constexpr BnApplyRow kBnApplyRows[] = {{true, true, true, true},    {true, true, true, false},   {true, false, true, false},
+                                       {true, true, false, false},  {true, false, false, false}, {false, true, false, false},
+                                       {false, false, false, false}};
+constexpr int kNumBnApplyRows = sizeof(kBnApplyRows) / sizeof(kBnApplyRows[0]);
+// bn_bwd_apply_kernel<RELU, NT>: RELU 0 = none, 1 = mask, 2 = sign derived from y; no non-temporal form without ReLU
+struct BnBwdApplyRow {
+  int relu;
+  bool nt;
+};
+constexpr BnBwdApplyRow kBnBwdApplyRows[] = {{2, true}, {2, false}, {1, true}, {1, false}, {0, false}};
+constexpr int kNumBnBwdApplyRows = sizeof(kBnBwdApplyRows) / sizeof(kBnBwdApplyRows[0]);
+// bn_eval_bwd_kernel / bn_eval_bwd_stats_kernel<SIGN, DZ, NT>: all 12 combinations exist; row I = (SIGN * 2 + DZ) * 2 + NT
+constexpr int kNumBnEvalRows = 12;
+
+template <int ES>
+void launch_bn_bwd_partial(int relu_mode, const BnGrid& b, hipStream_t s, const void* dout, const uint32_t* relu_mask, const void* y,
+                           const float* mean, const float* invstd, float* p1, float* p2, int64_t M, int C, const float* relu_scale,
+                           const float* relu_shift) {
+  static_index<3>(relu_mode, [&](auto mode) {
+    hipLaunchKernelGGL((bn_bwd_partial_kernel<decltype(mode)::value, ES>), dim3(b.RB, b.CC), dim3(256), 0, s, dout, relu_mask, y, mean,
+                       invstd, p1, p2, M, C, b.CVB, b.RL, b.rows_per_block, relu_scale, relu_shift);
+  });
 }
 
 }  // namespace
@@ -899,18 +935,14 @@ extern "C" int bdv_bn_train_stats(const float* y, int64_t M, int C, const float*
   BDV_REQUIRE(M > 0 && bn_c_ok(C), "bdv_bn_train_stats: unsupported M=%lld C=%d", (long long)M, C);
   BDV_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bdv_bn_train_stats: running stats must come in pairs");
   BDV_REQUIRE(bdv_aligned16(y) && bdv_aligned16(workspace), "bdv_bn_train_stats: alignment");
-  if (workspace_bytes < bdv_bn_workspace_bytes(M, C)) {
-    bdv_set_error("bdv_bn_train_stats: workspace too small");
-    return BDV_EWORKSPACE;
-  }
+  BnWs w;   // psum = p1, psq = p2; the coefficients are not used
+  if (int e = bn_ws_carve(workspace, workspace_bytes, C, "bdv_bn_train_stats", &w)) return e;
   const BnGrid b = bn_grid(M, C);
-  float* psum = (float*)workspace;
-  float* psq = psum + MAX_RB_TIMES_C;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_partial_kernel, dim3(b.RB, b.CC), dim3(256), 0, s, y, psum, psq, M, C, b.CVB, b.RL, b.rows_per_block);
+  hipLaunchKernelGGL(bn_partial_kernel, dim3(b.RB, b.CC), dim3(256), 0, s, y, w.p1, w.p2, M, C, b.CVB, b.RL, b.rows_per_block);
   BDV_LAUNCH_CHECK("bdv_bn_train_stats(partial)");
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(4 * FIN_LANES), 0, s, (const float*)psum, (const float*)psq, b.RB,
-                     M, C, gamma, beta, eps, momentum, running_mean, running_var, save_mean, save_invstd, scale, shift);
+  launch_bn_finalize(w.p1, w.p2, b.RB, M, C, gamma, beta, eps, momentum, running_mean, running_var, save_mean, save_invstd, scale, shift,
+                     1, nullptr, s);
   BDV_LAUNCH_CHECK("bdv_bn_train_stats(finalize)");
   return BDV_OK;
 }
@@ -966,20 +998,19 @@ extern "C" int bdv_bn_apply(const void* y, const float* scale, const float* shif
   const int64_t n4 = M * C / 4;
   const int CV = C / 4;
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(ew_grid(act_dtype == BDV_ACT_BF16 ? n4 / 2 : n4 / BDV_F32_UNITS)), blk(256);
+  const dim3 grid = act_grid(n4, act_dtype), blk(256);
   const float4 *sc = (const float4*)scale, *sh = (const float4*)shift;
   const float4 *rs = (const float4*)res_scale, *rb = (const float4*)res_shift;
-#define BDV_APPLY(...) hipLaunchKernelGGL((bn_apply_kernel<__VA_ARGS__, ES>), grid, blk, 0, s, y, sc, sh, res, rs, rb, out, relu_mask, n4, CV)
-  BDV_ACT_SWITCH(act_dtype, ES, {
-    if (relu && res && bn_nt_level() >= 2) BDV_APPLY(true, true, true, true);
-    else if (relu && res && bn_nt_enabled()) BDV_APPLY(true, true, true, false);
-    else if (relu && bn_nt_enabled()) BDV_APPLY(true, false, true, false);
-    else if (relu && res) BDV_APPLY(true, true, false, false);
-    else if (relu) BDV_APPLY(true, false, false, false);
-    else if (res) BDV_APPLY(false, true, false, false);
-    else BDV_APPLY(false, false, false, false);
+  const BnApplyRow want = {relu != 0, res != nullptr, relu && bn_nt_enabled(), relu && res && bn_nt_level() >= 2};
+  const int row = find_row(kBnApplyRows, [&](const BnApplyRow& r) {
+    return r.relu == want.relu && r.res == want.res && r.nt == want.nt && r.ntr == want.ntr;
   });
-#undef BDV_APPLY
+  BDV_REQUIRE(row >= 0, "bdv_bn_apply: no kernel is compiled for relu %d, residual %d, non-temporal %d / %d", want.relu, want.res, want.nt,
+              want.ntr);
+  BDV_ACT_SWITCH(act_dtype, ES, static_index<kNumBnApplyRows>(row, [&](auto ri) {
+    constexpr BnApplyRow r = kBnApplyRows[decltype(ri)::value];
+    hipLaunchKernelGGL((bn_apply_kernel<r.relu, r.res, r.nt, r.ntr, ES>), grid, blk, 0, s, y, sc, sh, res, rs, rb, out, relu_mask, n4, CV);
+  }));
   BDV_LAUNCH_CHECK("bdv_bn_apply");
   return BDV_OK;
 }
@@ -997,53 +1028,35 @@ extern "C" int bdv_bn_backward_split(const void* dout, const uint32_t* relu_mask
   BDV_REQUIRE(!relu || derive || (relu_mask && C % 32 == 0), "bdv_bn_backward: relu needs the forward ReLU mask (C %% 32 == 0) or relu_scale / relu_shift");
   BDV_REQUIRE(!derive || (relu_shift != nullptr && bdv_aligned16(relu_scale) && bdv_aligned16(relu_shift)), "bdv_bn_backward: relu_scale / relu_shift");
   BDV_REQUIRE(M > 0 && bn_c_ok(C), "bdv_bn_backward: unsupported M=%lld C=%d", (long long)M, C);
+  BDV_REQUIRE(act_dtype == BDV_ACT_F32 || C % 8 == 0, "bdv_bn_backward: bf16 tensors need C %% 8 == 0 (16-byte units)");
   BDV_REQUIRE(bdv_aligned16(dout) && bdv_aligned16(y) && bdv_aligned16(dy) && bdv_aligned16(workspace) &&
                   bdv_aligned16(save_mean) && bdv_aligned16(save_invstd), "bdv_bn_backward: alignment");
-  if (workspace_bytes < bdv_bn_workspace_bytes(M, C)) {
-    bdv_set_error("bdv_bn_backward: workspace too small");
-    return BDV_EWORKSPACE;
-  }
+  BnWs w;
+  if (int e = bn_ws_carve(workspace, workspace_bytes, C, "bdv_bn_backward", &w)) return e;
   const BnGrid b = bn_grid(M, C);
-  const int S = bn_fin_resolve(splits, stat_partial != nullptr ? stat_rows : b.RB, C, fin_scratch, fin_scratch_bytes, "bdv_bn_backward");
+  const BnSums sums = bn_sums(stat_partial, stat_rows, C, w.p1, w.p2, b.RB);
+  const int S = bn_fin_resolve(splits, sums.rows, C, fin_scratch, fin_scratch_bytes, "bdv_bn_backward");
   if (S < 0) return BDV_EINVAL;
-  float* p1 = (float*)workspace;
-  float* p2 = p1 + MAX_RB_TIMES_C;
-  float* coef = p2 + MAX_RB_TIMES_C;
   hipStream_t s = (hipStream_t)stream;
-  const float *q1 = p1, *q2 = p2;
-  int rows = b.RB;
-  if (stat_partial != nullptr) {  // the producer of dout (a dgrad epilogue) already reduced per 128-row tile
-    q1 = stat_partial;
-    q2 = stat_partial + (size_t)stat_rows * C;
-    rows = stat_rows;
-  } else {
-#define BDV_BWD_PARTIAL(RELU_)                                                                                                  \
-  hipLaunchKernelGGL((bn_bwd_partial_kernel<RELU_, ES>), dim3(b.RB, b.CC), dim3(256), 0, s, dout, relu_mask, y, save_mean,     \
-                     save_invstd, p1, p2, M, C, b.CVB, b.RL, b.rows_per_block, relu_scale, relu_shift)
-    BDV_ACT_SWITCH(act_dtype, ES, {
-      if (derive) BDV_BWD_PARTIAL(2);
-      else if (relu) BDV_BWD_PARTIAL(1);
-      else BDV_BWD_PARTIAL(0);
-    });
-#undef BDV_BWD_PARTIAL
+  const int relu_mode = derive ? 2 : relu ? 1 : 0;   // the kernels' RELU
+  const bool nt = relu_mode != 0 && bn_nt_enabled();
+  const int row = find_row(kBnBwdApplyRows, [&](const BnBwdApplyRow& r) { return r.relu == relu_mode && r.nt == nt; });
+  BDV_REQUIRE(row >= 0, "bdv_bn_backward: no apply kernel is compiled for relu mode %d, non-temporal %d", relu_mode, (int)nt);
+  if (!sums.given) {
+    BDV_ACT_SWITCH(act_dtype, ES, launch_bn_bwd_partial<ES>(relu_mode, b, s, dout, relu_mask, y, save_mean, save_invstd, w.p1, w.p2, M, C,
+                                                            relu_scale, relu_shift));
     BDV_LAUNCH_CHECK("bdv_bn_backward(partial)");
   }
-  launch_bn_bwd_finalize(q1, q2, rows, M, C, gamma, save_invstd, dgamma, dbeta, beta_acc, coef, S, fin_scratch, s);
+  launch_bn_bwd_finalize(sums.q1, sums.q2, sums.rows, M, C, gamma, save_invstd, dgamma, dbeta, beta_acc, w.coef, S, fin_scratch, s);
   BDV_LAUNCH_CHECK("bdv_bn_backward(finalize)");
-  BDV_REQUIRE(act_dtype == BDV_ACT_F32 || C % 8 == 0, "bdv_bn_backward: bf16 tensors need C %% 8 == 0 (16-byte units)");
   const int64_t n4 = M * C / 4;
-  const dim3 grid(ew_grid(act_dtype == BDV_ACT_BF16 ? n4 / 2 : n4 / BDV_F32_UNITS)), blk(256);
+  const dim3 grid = act_grid(n4, act_dtype), blk(256);
   const float4 *rs4 = (const float4*)relu_scale, *rh4 = (const float4*)relu_shift;
-#define BDV_BWD_APPLY(RELU_, NT_)                                                                                              \
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<RELU_, NT_, ES>), grid, blk, 0, s, dout, relu_mask, y,                               \
-                     (const float4*)save_mean, (const float4*)save_invstd, (const float4*)coef, dy, n4, C / 4, rs4, rh4)
-  const bool nt = bn_nt_enabled();
-  BDV_ACT_SWITCH(act_dtype, ES, {
-    if (derive) { if (nt) BDV_BWD_APPLY(2, true); else BDV_BWD_APPLY(2, false); }
-    else if (relu) { if (nt) BDV_BWD_APPLY(1, true); else BDV_BWD_APPLY(1, false); }
-    else BDV_BWD_APPLY(0, false);
-  });
-#undef BDV_BWD_APPLY
+  BDV_ACT_SWITCH(act_dtype, ES, static_index<kNumBnBwdApplyRows>(row, [&](auto ri) {
+    constexpr BnBwdApplyRow r = kBnBwdApplyRows[decltype(ri)::value];
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<r.relu, r.nt, ES>), grid, blk, 0, s, dout, relu_mask, y, (const float4*)save_mean,
+                       (const float4*)save_invstd, (const float4*)w.coef, dy, n4, C / 4, rs4, rh4);
+  }));
   BDV_LAUNCH_CHECK("bdv_bn_backward(apply)");
   return BDV_OK;
 }
@@ -1084,65 +1097,52 @@ extern "C" int bdv_bn_backward_pair(const void* dout, const uint32_t* relu_mask,
     return BDV_EWORKSPACE;
   }
   const BnGrid b = bn_grid(M, C);
-  const int Sa = bn_fin_resolve(splits, stat_partial_a != nullptr ? stat_rows_a : b.RB, C, fin_scratch, fin_scratch_bytes, "bdv_bn_backward_pair");
-  const int Sb = bn_fin_resolve(splits, b.RB, C, fin_scratch, fin_scratch_bytes, "bdv_bn_backward_pair");
-  if (Sa < 0 || Sb < 0) return BDV_EINVAL;
-  float* p1 = (float*)workspace;
+  float* p1 = (float*)workspace;   // three slabs: sum g (one for both BatchNorms), sum g * xhat_a, sum g * xhat_b; then the coefficients
   float* pa2 = p1 + MAX_RB_TIMES_C;
   float* pb2 = pa2 + MAX_RB_TIMES_C;
   float* coef_a = pb2 + MAX_RB_TIMES_C;
   float* coef_b = coef_a + 3 * (size_t)C;
+  const BnSums sa = bn_sums(stat_partial_a, stat_rows_a, C, p1, pa2, b.RB);
+  const int Sa = bn_fin_resolve(splits, sa.rows, C, fin_scratch, fin_scratch_bytes, "bdv_bn_backward_pair");
+  const int Sb = bn_fin_resolve(splits, b.RB, C, fin_scratch, fin_scratch_bytes, "bdv_bn_backward_pair");
+  if (Sa < 0 || Sb < 0) return BDV_EINVAL;
+  const int64_t n4 = M * C / 4;
+  // the apply pass: four units per thread where the unit stride can be a multiple of the block (256) and of the channel period
+  // (tools/bench_bn.py --pair, whole pair call against two bdv_bn_backward calls at the four R50 downsample blocks: one unit per
+  // thread -8.7 / -7.9 / -8.7 / -4.9 %, four units per thread -9.8 / -12.5 / -20.9 / -16.2 %; the wider C, the more the ten
+  // per-channel vectors per unit cost)
+  const int U_ = act_dtype == BDV_ACT_BF16 ? 2 : BDV_F32_UNITS;
+  const int CVU = (C / 4) / U_;
+  const int L = CVU > 256 ? CVU : 256;
+  const bool rows4 = (C / 4) % U_ == 0 && L % CVU == 0 && L % 256 == 0;
+  const int64_t nu = n4 / U_;
+  const int64_t nblk = ((nu + (int64_t)4 * L - 1) / ((int64_t)4 * L)) * (L / 256);
+  BDV_REQUIRE(!rows4 || nblk < (1ll << 31), "bdv_bn_backward_pair: tensor too large");
   hipStream_t s = (hipStream_t)stream;
-  const float *qa1 = p1, *qa2 = pa2;
-  int rows_a = b.RB;
-  if (stat_partial_a != nullptr) {  // the last main unit's sums came out of a dgrad epilogue: the downsample BatchNorm's alone
-    qa1 = stat_partial_a;
-    qa2 = stat_partial_a + (size_t)stat_rows_a * C;
-    rows_a = stat_rows_a;
-    BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((bn_bwd_partial_kernel<1, ES>), dim3(b.RB, b.CC), dim3(256), 0, s, dout, relu_mask, yb,
-                       mean_b, invstd_b, p1, pb2, M, C, b.CVB, b.RL, b.rows_per_block, (const float*)nullptr, (const float*)nullptr));
+  if (sa.given) {  // the last main unit's sums came out of a dgrad epilogue: the downsample BatchNorm's alone
+    BDV_ACT_SWITCH(act_dtype, ES, launch_bn_bwd_partial<ES>(1, b, s, dout, relu_mask, yb, mean_b, invstd_b, p1, pb2, M, C, nullptr, nullptr));
   } else {
     BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((bn_bwd_partial_pair_kernel<ES>), dim3(b.RB, b.CC), dim3(256), 0, s, dout, relu_mask, ya,
                        mean_a, invstd_a, yb, mean_b, invstd_b, p1, pa2, pb2, M, C, b.CVB, b.RL, b.rows_per_block));
   }
   BDV_LAUNCH_CHECK("bdv_bn_backward_pair(partial)");
   // the two finalizes run one after the other on the stream: they may share the scratch and the tickets
-  launch_bn_bwd_finalize(qa1, qa2, rows_a, M, C, gamma_a, invstd_a, dgamma_a, dbeta_a, 0.f, coef_a, Sa, fin_scratch, s);
+  launch_bn_bwd_finalize(sa.q1, sa.q2, sa.rows, M, C, gamma_a, invstd_a, dgamma_a, dbeta_a, 0.f, coef_a, Sa, fin_scratch, s);
   BDV_LAUNCH_CHECK("bdv_bn_backward_pair(finalize a)");
   launch_bn_bwd_finalize(p1, pb2, b.RB, M, C, gamma_b, invstd_b, dgamma_b, dbeta_b, 0.f, coef_b, Sb, fin_scratch, s);
   BDV_LAUNCH_CHECK("bdv_bn_backward_pair(finalize b)");
-  const int64_t n4 = M * C / 4;
-  const dim3 grid(ew_grid(act_dtype == BDV_ACT_BF16 ? n4 / 2 : n4 / BDV_F32_UNITS)), blk(256);
-#define BDV_BWD_APPLY_PAIR(NT_)                                                                                                  \
-  hipLaunchKernelGGL((bn_bwd_apply_pair_kernel<NT_, ES>), grid, blk, 0, s, dout, relu_mask, ya, (const float4*)mean_a,            \
-                     (const float4*)invstd_a, (const float4*)coef_a, dya, yb, (const float4*)mean_b, (const float4*)invstd_b,     \
-                     (const float4*)coef_b, dyb, n4, C / 4)
-  const bool nt = bn_nt_enabled();
-  // four units per thread where the unit stride can be a multiple of the block (256) and of the channel period
-  const int U_ = act_dtype == BDV_ACT_BF16 ? 2 : BDV_F32_UNITS;
-  const int CVU = (C / 4) / U_;
-  const int L = CVU > 256 ? CVU : 256;
-  // (tools/bench_bn.py --pair, whole pair call against two bdv_bn_backward calls at the four R50 downsample blocks: one unit per
-  // thread -8.7 / -7.9 / -8.7 / -4.9 %, four units per thread -9.8 / -12.5 / -20.9 / -16.2 %; the wider C, the more the ten
-  // per-channel vectors per unit cost)
-  if ((C / 4) % U_ == 0 && L % CVU == 0 && L % 256 == 0) {
-    const int64_t nu = n4 / U_;
-    const int64_t nblk = ((nu + (int64_t)4 * L - 1) / ((int64_t)4 * L)) * (L / 256);
-    BDV_REQUIRE(nblk < (1ll << 31), "bdv_bn_backward_pair: tensor too large");
-#define BDV_BWD_APPLY_PAIR_ROWS(NT_)                                                                                             \
-  hipLaunchKernelGGL((bn_bwd_apply_pair_rows_kernel<NT_, ES, 4>), dim3((unsigned)nblk), blk, 0, s, dout, relu_mask, ya,           \
-                     (const float4*)mean_a, (const float4*)invstd_a, (const float4*)coef_a, dya, yb, (const float4*)mean_b,      \
-                     (const float4*)invstd_b, (const float4*)coef_b, dyb, nu, C / 4, L)
-    BDV_ACT_SWITCH(act_dtype, ES, {
-      if (nt) BDV_BWD_APPLY_PAIR_ROWS(true); else BDV_BWD_APPLY_PAIR_ROWS(false);
-    });
-#undef BDV_BWD_APPLY_PAIR_ROWS
-  } else {
-    BDV_ACT_SWITCH(act_dtype, ES, {
-      if (nt) BDV_BWD_APPLY_PAIR(true); else BDV_BWD_APPLY_PAIR(false);
-    });
-  }
-#undef BDV_BWD_APPLY_PAIR
+  const dim3 blk(256);
+  const float4 *mua = (const float4*)mean_a, *isa = (const float4*)invstd_a, *ca = (const float4*)coef_a;
+  const float4 *mub = (const float4*)mean_b, *isb = (const float4*)invstd_b, *cb = (const float4*)coef_b;
+  BDV_ACT_SWITCH(act_dtype, ES, static_index<2>(bn_nt_enabled(), [&](auto nt) {
+    constexpr bool NT = decltype(nt)::value != 0;
+    if (rows4)
+      hipLaunchKernelGGL((bn_bwd_apply_pair_rows_kernel<NT, ES, 4>), dim3((unsigned)nblk), blk, 0, s, dout, relu_mask, ya, mua, isa, ca, dya,
+                         yb, mub, isb, cb, dyb, nu, C / 4, L);
+    else
+      hipLaunchKernelGGL((bn_bwd_apply_pair_kernel<NT, ES>), act_grid(n4, act_dtype), blk, 0, s, dout, relu_mask, ya, mua, isa, ca, dya, yb,
+                         mub, isb, cb, dyb, n4, C / 4);
+  }));
   BDV_LAUNCH_CHECK("bdv_bn_backward_pair(apply)");
   return BDV_OK;
 }
@@ -1166,49 +1166,35 @@ extern "C" int bdv_bn_eval_backward(const void* dout, const uint32_t* relu_mask,
   const int sign = relu_mask != nullptr ? 1 : relu_act != nullptr ? 2 : 0;
   const bool nt = bn_nt_enabled();
   hipStream_t s = (hipStream_t)stream;
-#define BDV_EVAL_DISPATCH(LAUNCH)                                                       \
-  do {                                                                                  \
-    if (sign == 1) { if (dz) { if (nt) LAUNCH(1, true, true); else LAUNCH(1, true, false); }   \
-                     else    { if (nt) LAUNCH(1, false, true); else LAUNCH(1, false, false); } } \
-    else if (sign == 2) { if (dz) { if (nt) LAUNCH(2, true, true); else LAUNCH(2, true, false); }   \
-                          else    { if (nt) LAUNCH(2, false, true); else LAUNCH(2, false, false); } } \
-    else { if (dz) { if (nt) LAUNCH(0, true, true); else LAUNCH(0, true, false); }      \
-           else    { if (nt) LAUNCH(0, false, true); else LAUNCH(0, false, false); } }  \
-  } while (0)
+  const int row = (sign * 2 + (dz != nullptr)) * 2 + nt;   // kNumBnEvalRows
   if (!stats) {   // dy = dz * scale alone: no y, no workspace, no reduction
     const int64_t n4 = M * C / 4;
-    const dim3 grid(ew_grid(act_dtype == BDV_ACT_BF16 ? n4 / 2 : n4 / BDV_F32_UNITS)), blk(256);
-#define BDV_EVAL_BWD(SIGN_, DZ_, NT_)                                                                                          \
-  hipLaunchKernelGGL((bn_eval_bwd_kernel<SIGN_, DZ_, NT_, ES>), grid, blk, 0, s, dout, relu_mask, relu_act, (const float4*)scale, dy, \
-                     dz, n4, C / 4)
-    BDV_ACT_SWITCH(act_dtype, ES, BDV_EVAL_DISPATCH(BDV_EVAL_BWD));
-#undef BDV_EVAL_BWD
+    const dim3 grid = act_grid(n4, act_dtype), blk(256);
+    BDV_ACT_SWITCH(act_dtype, ES, static_index<kNumBnEvalRows>(row, [&](auto ri) {
+      constexpr int I = decltype(ri)::value;
+      hipLaunchKernelGGL((bn_eval_bwd_kernel<I / 4, (I / 2) % 2 != 0, I % 2 != 0, ES>), grid, blk, 0, s, dout, relu_mask, relu_act,
+                         (const float4*)scale, dy, dz, n4, C / 4);
+    }));
     BDV_LAUNCH_CHECK("bdv_bn_eval_backward");
     return BDV_OK;
   }
   BDV_REQUIRE(y && running_mean && invstd && workspace, "bdv_bn_eval_backward: dgamma / dbeta need y, running_mean, invstd and a workspace");
   BDV_REQUIRE(bdv_aligned16(running_mean) && bdv_aligned16(invstd) && bdv_aligned16(workspace), "bdv_bn_eval_backward: alignment");
   BDV_REQUIRE((const void*)dy != y && (dz == nullptr || (const void*)dz != y), "bdv_bn_eval_backward: dy / dz must not alias y");
-  if (workspace_bytes < bdv_bn_workspace_bytes(M, C)) {
-    bdv_set_error("bdv_bn_eval_backward: workspace too small");
-    return BDV_EWORKSPACE;
-  }
+  BnWs w;
+  if (int e = bn_ws_carve(workspace, workspace_bytes, C, "bdv_bn_eval_backward", &w)) return e;
   const BnGrid b = bn_grid(M, C);
   const int S = bn_fin_resolve(splits, b.RB, C, fin_scratch, fin_scratch_bytes, "bdv_bn_eval_backward");
   if (S < 0) return BDV_EINVAL;
-  float* p1 = (float*)workspace;
-  float* p2 = p1 + MAX_RB_TIMES_C;
-  float* coef = p2 + MAX_RB_TIMES_C;
-#define BDV_EVAL_BWD_STATS(SIGN_, DZ_, NT_)                                                                                    \
-  hipLaunchKernelGGL((bn_eval_bwd_stats_kernel<SIGN_, DZ_, NT_, ES>), dim3(b.RB, b.CC), dim3(256), 0, s, dout, relu_mask, relu_act, y, \
-                     scale, running_mean, invstd, dy, dz, p1, p2, M, C, b.CVB, b.RL, b.rows_per_block)
-  BDV_ACT_SWITCH(act_dtype, ES, BDV_EVAL_DISPATCH(BDV_EVAL_BWD_STATS));
-#undef BDV_EVAL_BWD_STATS
-#undef BDV_EVAL_DISPATCH
+  BDV_ACT_SWITCH(act_dtype, ES, static_index<kNumBnEvalRows>(row, [&](auto ri) {
+    constexpr int I = decltype(ri)::value;
+    hipLaunchKernelGGL((bn_eval_bwd_stats_kernel<I / 4, (I / 2) % 2 != 0, I % 2 != 0, ES>), dim3(b.RB, b.CC), dim3(256), 0, s, dout,
+                       relu_mask, relu_act, y, scale, running_mean, invstd, dy, dz, w.p1, w.p2, M, C, b.CVB, b.RL, b.rows_per_block);
+  }));
   BDV_LAUNCH_CHECK("bdv_bn_eval_backward(pass)");
   // the train-mode finalize: fixed-order fp64 column sums -> dgamma / dbeta (beta_acc as bdv_bn_backward).  Its apply coefficients
   // go to the workspace unread; `scale` stands in for the gamma they are formed from.
-  launch_bn_bwd_finalize(p1, p2, b.RB, M, C, scale, invstd, dgamma, dbeta, beta_acc, coef, S, fin_scratch, s);
+  launch_bn_bwd_finalize(w.p1, w.p2, b.RB, M, C, scale, invstd, dgamma, dbeta, beta_acc, w.coef, S, fin_scratch, s);
   BDV_LAUNCH_CHECK("bdv_bn_eval_backward(finalize)");
   return BDV_OK;
 }
@@ -1228,10 +1214,8 @@ extern "C" int bdv_bn_backward_maxpool_split(const void* dpool, const uint8_t* p
               "bdv_bn_backward_maxpool: alignment");
   const int64_t M = (int64_t)N * H * W;
   BDV_REQUIRE(M * (C / 4) < (1ll << 31), "bdv_bn_backward_maxpool: tensor too large");
-  if (workspace_bytes < bdv_bn_workspace_bytes(M, C)) {
-    bdv_set_error("bdv_bn_backward_maxpool: workspace too small");
-    return BDV_EWORKSPACE;
-  }
+  BnWs w;
+  if (int e = bn_ws_carve(workspace, workspace_bytes, C, "bdv_bn_backward_maxpool", &w)) return e;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1, CV = C / 4;
   const int gx = (Wo * CV + 255) / 256;
   int gy = N * Ho;
@@ -1241,20 +1225,20 @@ extern "C" int bdv_bn_backward_maxpool_split(const void* dpool, const uint8_t* p
   BDV_REQUIRE(gy >= 1, "bdv_bn_backward_maxpool: row too wide for the partial slab");
   const int S = bn_fin_resolve(splits, gx * gy, C, fin_scratch, fin_scratch_bytes, "bdv_bn_backward_maxpool");
   if (S < 0) return BDV_EINVAL;
-  float* p1 = (float*)workspace;
-  float* p2 = p1 + MAX_RB_TIMES_C;
-  float* coef = p2 + MAX_RB_TIMES_C;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(gx, gy), blk(256);
-  BDV_ACT_SWITCH(dpool_dtype, ES, hipLaunchKernelGGL((bn_bwd_pool_kernel<false, ES>), grid, blk, 0, s, dpool, (const uchar4*)pool_idx, relu_mask,
-                     (const float4*)y, (const float4*)save_mean, (const float4*)save_invstd, (const float4*)nullptr,
-                     (float4*)nullptr, p1, p2, N, H, W, CV, Ho, Wo));
+  auto pass = [&](auto apply) {   // statistics (coef and dy unused) or apply (p1 and p2 unused)
+    constexpr bool APPLY = decltype(apply)::value;
+    BDV_ACT_SWITCH(dpool_dtype, ES, hipLaunchKernelGGL((bn_bwd_pool_kernel<APPLY, ES>), grid, blk, 0, s, dpool, (const uchar4*)pool_idx,
+                       relu_mask, (const float4*)y, (const float4*)save_mean, (const float4*)save_invstd,
+                       APPLY ? (const float4*)w.coef : nullptr, APPLY ? (float4*)dy : nullptr, APPLY ? nullptr : w.p1,
+                       APPLY ? nullptr : w.p2, N, H, W, CV, Ho, Wo));
+  };
+  pass(std::false_type{});
   BDV_LAUNCH_CHECK("bdv_bn_backward_maxpool(partial)");
-  launch_bn_bwd_finalize(p1, p2, gx * gy, M, C, gamma, save_invstd, dgamma, dbeta, beta_acc, coef, S, fin_scratch, s);
+  launch_bn_bwd_finalize(w.p1, w.p2, gx * gy, M, C, gamma, save_invstd, dgamma, dbeta, beta_acc, w.coef, S, fin_scratch, s);
   BDV_LAUNCH_CHECK("bdv_bn_backward_maxpool(finalize)");
-  BDV_ACT_SWITCH(dpool_dtype, ES, hipLaunchKernelGGL((bn_bwd_pool_kernel<true, ES>), grid, blk, 0, s, dpool, (const uchar4*)pool_idx, relu_mask,
-                     (const float4*)y, (const float4*)save_mean, (const float4*)save_invstd, (const float4*)coef, (float4*)dy,
-                     (float*)nullptr, (float*)nullptr, N, H, W, CV, Ho, Wo));
+  pass(std::true_type{});
   BDV_LAUNCH_CHECK("bdv_bn_backward_maxpool(apply)");
   return BDV_OK;
 }

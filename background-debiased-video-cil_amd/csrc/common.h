@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <utility>
 #include "bdvcil_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -132,6 +133,17 @@ __device__ __forceinline__ void act_st16(void* __restrict__ base, int64_t iu, co
     }                                \
   } while (0)
 #define BDV_REQUIRE_ACT(dt, name) BDV_REQUIRE((dt) == BDV_ACT_F32 || (dt) == BDV_ACT_BF16, "%s: act_dtype %d (BDV_ACT_F32 = 0 | BDV_ACT_BF16 = 1)", name, (int)(dt))
+
+// Host only.  f(std::integral_constant<int, i>{}) for the runtime index i in [0, N): the launches turn a row of a constexpr table
+// into template arguments with it (conv_mfma.hip: kPlTiles, kPlAriths; bn.hip: kBnApplyRows, ...)
+template <class F, int... I>
+void static_index(int i, F&& f, std::integer_sequence<int, I...>) {
+  ((i == I ? (void)f(std::integral_constant<int, I>{}) : (void)0), ...);
+}
+template <int N, class F>
+void static_index(int i, F&& f) {
+  static_index(i, f, std::make_integer_sequence<int, N>{});
+}
 
 // ---- MaxPool2d(3, 2, 1) backward as a gather (shared by maxpool_bwd and the fused stem BatchNorm backward) ----------
 // The 2x2 input block (2i..2i+1, 2j..2j+1) of channels c4 is covered by exactly the windows (i,j), (i,j+1), (i+1,j),

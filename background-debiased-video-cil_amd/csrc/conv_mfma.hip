@@ -2980,16 +2980,6 @@ constexpr PlTile kPlTiles[] = {
 };
 constexpr int kNumPlTiles = sizeof(kPlTiles) / sizeof(kPlTiles[0]);
 
-// f(std::integral_constant<int, i>{}) for the runtime index i in [0, N): the launches turn a table row into template arguments with it
-template <class F, int... I>
-void static_index(int i, F&& f, std::integer_sequence<int, I...>) {
-  ((i == I ? (void)f(std::integral_constant<int, I>{}) : (void)0), ...);
-}
-template <int N, class F>
-void static_index(int i, F&& f) {
-  static_index(i, f, std::make_integer_sequence<int, N>{});
-}
-
 struct PlPlan {
   int cfg;  // -1: shape not covered by the P kernels
   int MT, NT, nk;

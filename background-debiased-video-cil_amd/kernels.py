@@ -606,6 +606,27 @@ def _bn_fin_scratch(C, device):
     return cur
 
 
+def _bn_fin_args(splits, C, device):
+    """(pointer, byte count) of the finalize scratch for a call with ``splits`` blocks per channel group: none for one block."""
+    fs = _bn_fin_scratch(C, device) if splits != 1 else None
+    return _p(fs), fs.numel() if fs is not None else 0
+
+
+def _bn_stat_rows(stat_partial, C, who, name='stat_partial'):
+    """Checks the ``(2, rows, C)`` tile sums of a ``conv_dgrad(bn_stats=...)`` call -> rows (0 without them)."""
+    if stat_partial is None:
+        return 0
+    _chk(stat_partial, name=name)
+    if stat_partial.dim() != 3 or stat_partial.shape[0] != 2 or stat_partial.shape[2] != C:
+        raise ValueError(f'{who}: {name} {tuple(stat_partial.shape)} is not (2, rows, {C})')
+    return stat_partial.shape[1]
+
+
+def _bn_param_grads(C, device):
+    """Fresh (dgamma, dbeta)."""
+    return torch.empty(C, dtype=torch.float32, device=device), torch.empty(C, dtype=torch.float32, device=device)
+
+
 def bn_train_stats(y, gamma, beta, eps, momentum, running_mean, running_var):
     """y (..., C) -> (save_mean, save_invstd, scale, shift); running stats updated in place."""
     C = y.shape[-1]
@@ -635,10 +656,9 @@ def bn_train_finalize(partial, M, gamma, beta, eps, momentum, running_mean, runn
         _chk(running_mean, (C,), name='running_mean')
         _chk(running_var, (C,), name='running_var')
     stats = torch.empty((4, C), dtype=torch.float32, device=partial.device)
-    fs = _bn_fin_scratch(C, partial.device) if splits != 1 else None
     check(lib().bdv_bn_train_finalize_split(_p(partial), rows, int(M), C, _p(gamma), _p(beta), float(eps), float(momentum),
                                             _p(running_mean), _p(running_var), _p(stats[0]), _p(stats[1]), _p(stats[2]),
-                                            _p(stats[3]), int(splits), _p(fs), fs.numel() if fs is not None else 0, _stream()),
+                                            _p(stats[3]), int(splits), *_bn_fin_args(splits, C, partial.device), _stream()),
           'bdv_bn_train_finalize_split')
     return stats[0], stats[1], stats[2], stats[3]
 
@@ -703,27 +723,20 @@ def bn_backward(dout, relu_mask, y, gamma, save_mean, save_invstd, relu, dgamma=
     for t, n in ((gamma, 'gamma'), (save_mean, 'save_mean'), (save_invstd, 'save_invstd')):
         _chk(t, (C,), name=n)
     if dgamma is None:
-        dgamma = torch.empty(C, dtype=torch.float32, device=y.device)
-        dbeta = torch.empty(C, dtype=torch.float32, device=y.device)
+        dgamma, dbeta = _bn_param_grads(C, y.device)
         beta_acc = 0.0
     _chk(dgamma, (C,), name='dgamma')
     _chk(dbeta, (C,), name='dbeta')
     d = dy if dy is not None else torch.empty_like(y)
     _chk_act(d, tuple(y.shape), name='dy', like=y)
     amax_forget(dy)
-    srows = 0
-    if stat_partial is not None:
-        _chk(stat_partial, name='stat_partial')
-        if stat_partial.dim() != 3 or stat_partial.shape[0] != 2 or stat_partial.shape[2] != C:
-            raise ValueError(f'bn_backward: stat_partial {tuple(stat_partial.shape)} is not (2, rows, {C})')
-        srows = stat_partial.shape[1]
+    srows = _bn_stat_rows(stat_partial, C, 'bn_backward')
     ws = _bn_ws(M, C, y.device)
-    fs = _bn_fin_scratch(C, y.device) if splits != 1 else None
     check(lib().bdv_bn_backward_split(_p(dout), _p(relu_mask if relu else None), _p(y), _p(gamma), _p(save_mean), _p(save_invstd),
                                       _p(d), _p(dgamma), _p(dbeta), float(beta_acc), M, C, int(bool(relu)), _p(stat_partial), srows,
                                       _p(relu_affine[0] if relu_affine is not None else None),
                                       _p(relu_affine[1] if relu_affine is not None else None), _p(ws), ws.numel(), _act_code(y),
-                                      int(splits), _p(fs), fs.numel() if fs is not None else 0, _stream()), 'bdv_bn_backward_split')
+                                      int(splits), *_bn_fin_args(splits, C, y.device), _stream()), 'bdv_bn_backward_split')
     return d, dgamma, dbeta
 
 
@@ -743,20 +756,14 @@ def bn_backward_pair(dout, relu_mask, ya, gamma_a, mean_a, invstd_a, yb, gamma_b
     for t, n in ((gamma_a, 'gamma_a'), (mean_a, 'mean_a'), (invstd_a, 'invstd_a'), (gamma_b, 'gamma_b'), (mean_b, 'mean_b'),
                  (invstd_b, 'invstd_b')):
         _chk(t, (C,), name=n)
-    srows = 0
-    if stat_partial_a is not None:
-        _chk(stat_partial_a, name='stat_partial_a')
-        if stat_partial_a.dim() != 3 or stat_partial_a.shape[0] != 2 or stat_partial_a.shape[2] != C:
-            raise ValueError(f'bn_backward_pair: stat_partial_a {tuple(stat_partial_a.shape)} is not (2, rows, {C})')
-        srows = stat_partial_a.shape[1]
+    srows = _bn_stat_rows(stat_partial_a, C, 'bn_backward_pair', 'stat_partial_a')
     dya, dyb = torch.empty_like(ya), torch.empty_like(yb)
-    pg = [torch.empty(C, dtype=torch.float32, device=ya.device) for _ in range(4)]      # dgamma_a, dbeta_a, dgamma_b, dbeta_b
+    pg = _bn_param_grads(C, ya.device) + _bn_param_grads(C, ya.device)      # dgamma_a, dbeta_a, dgamma_b, dbeta_b
     ws = workspace(lib().bdv_bn_pair_workspace_bytes(M, C), ya.device, 'bn')
-    fs = _bn_fin_scratch(C, ya.device) if splits != 1 else None
     check(lib().bdv_bn_backward_pair(_p(dout), _p(relu_mask), _p(ya), _p(gamma_a), _p(mean_a), _p(invstd_a), _p(stat_partial_a), srows,
                                      _p(dya), _p(pg[0]), _p(pg[1]), _p(yb), _p(gamma_b), _p(mean_b), _p(invstd_b), _p(dyb), _p(pg[2]),
-                                     _p(pg[3]), M, C, _p(ws), ws.numel(), _act_code(ya), int(splits), _p(fs),
-                                     fs.numel() if fs is not None else 0, _stream()), 'bdv_bn_backward_pair')
+                                     _p(pg[3]), M, C, _p(ws), ws.numel(), _act_code(ya), int(splits), *_bn_fin_args(splits, C, ya.device),
+                                     _stream()), 'bdv_bn_backward_pair')
     return (dya, pg[0], pg[1]), (dyb, pg[2], pg[3])
 
 
@@ -798,7 +805,7 @@ def bn_eval_backward(dout, scale, relu_mask=None, relu_act=None, y=None, running
     if relu_act is not None:
         _chk_act(relu_act, tuple(dout.shape), name='relu_act', like=dout)
     params = want_params or dgamma is not None or dbeta is not None
-    ws = fs = None
+    ws = None
     if params:
         if y is None or running_mean is None or invstd is None:
             raise ValueError('bn_eval_backward: parameter gradients need y, running_mean and invstd')
@@ -808,13 +815,11 @@ def bn_eval_backward(dout, scale, relu_mask=None, relu_act=None, y=None, running
         if (dgamma is None) != (dbeta is None):
             raise ValueError('bn_eval_backward: give dgamma and dbeta together (to accumulate into) or neither')
         if dgamma is None:
-            dgamma = torch.empty(C, dtype=torch.float32, device=dout.device)
-            dbeta = torch.empty(C, dtype=torch.float32, device=dout.device)
+            dgamma, dbeta = _bn_param_grads(C, dout.device)
             beta_acc = 0.0
         _chk(dgamma, (C,), name='dgamma')
         _chk(dbeta, (C,), name='dbeta')
         ws = _bn_ws(M, C, dout.device)
-        fs = _bn_fin_scratch(C, dout.device) if splits != 1 else None
     else:
         y = running_mean = invstd = None
     d = dy if dy is not None else torch.empty_like(dout)
@@ -822,8 +827,8 @@ def bn_eval_backward(dout, scale, relu_mask=None, relu_act=None, y=None, running
     dz = torch.empty_like(dout) if want_dz else None
     check(lib().bdv_bn_eval_backward(_p(dout), _p(relu_mask), _p(relu_act), _p(y), _p(scale), _p(running_mean), _p(invstd), _p(d),
                                      _p(dz), _p(dgamma), _p(dbeta), float(beta_acc), M, C, _p(ws), ws.numel() if ws is not None else 0,
-                                     _act_code(dout), int(splits), _p(fs), fs.numel() if fs is not None else 0, _stream()),
-          'bdv_bn_eval_backward')
+                                     _act_code(dout), int(splits), *(_bn_fin_args(splits, C, dout.device) if params else (None, 0)),
+                                     _stream()), 'bdv_bn_eval_backward')
     return d, dz, dgamma, dbeta
 
 
@@ -839,13 +844,11 @@ def bn_backward_maxpool(dpool, pool_idx, relu_mask, y, gamma, save_mean, save_in
     for t, n in ((gamma, 'gamma'), (save_mean, 'save_mean'), (save_invstd, 'save_invstd')):
         _chk(t, (C,), name=n)
     dy = torch.empty_like(y)
-    dgamma = torch.empty(C, dtype=torch.float32, device=y.device)
-    dbeta = torch.empty(C, dtype=torch.float32, device=y.device)
+    dgamma, dbeta = _bn_param_grads(C, y.device)
     ws = _bn_ws(N * H * W, C, y.device)
-    fs = _bn_fin_scratch(C, y.device) if splits != 1 else None
     check(lib().bdv_bn_backward_maxpool_split(_p(dpool), _p(pool_idx), _p(relu_mask), _p(y), _p(gamma), _p(save_mean), _p(save_invstd),
                                               _p(dy), _p(dgamma), _p(dbeta), 0.0, N, H, W, C, _p(ws), ws.numel(), _act_code(dpool),
-                                              int(splits), _p(fs), fs.numel() if fs is not None else 0, _stream()),
+                                              int(splits), *_bn_fin_args(splits, C, y.device), _stream()),
           'bdv_bn_backward_maxpool_split')
     return dy, dgamma, dbeta
 
