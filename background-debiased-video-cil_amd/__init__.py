@@ -62,8 +62,9 @@ from .frontend import BackgroundCropFrontEnd, BackgroundMixFrontEnd, CropFrontEn
 from .decode import Draws, JpegDecoder, PrefetchLoader, RawFrameClipLoader, sample_frames  # noqa: F401
 from .actor_cut_mix import ActorCutMixClipLoader  # noqa: F401
 from .augment import RandAugment  # noqa: F401
-from .background import (encode_jpeg, extract_background, extract_backgrounds, random_resized_crop_boxes, resized_crop,  # noqa: F401
-                         resolve_bg_files, sim_cam_frame_files, temporal_median, temporal_nanreduce)
+from .background import (encode_jpeg, extract_background, extract_backgrounds, person_box_table, random_resized_crop_boxes,  # noqa: F401
+                         resized_crop, resolve_bg_files, sim_cam_frame_files, temporal_masked_median, temporal_median,
+                         temporal_nanreduce)
 from .cil_step import (TrainEngine, base_training_step, icarl_training_step, icarl_video_mix_training_step,  # noqa: F401
                        tubemix_draw)
 from .ddp import GradAllReducer, broadcast_parameters  # noqa: F401

@@ -125,6 +125,7 @@ SIGNATURES = {
     'bdv_jpeg_workspace_bytes': (c_size_t, [POINTER(JpegInfo), c_int]),
     'bdv_jpeg_reconstruct_u8': (c_int, [P, P, POINTER(JpegInfo), c_int, P, c_size_t, P, P]),
     'bdv_temporal_median_u8': (c_int, [P, c_int64, P, P, P, P, c_int, c_int, c_int, P, P]),
+    'bdv_temporal_masked_median_u8': (c_int, [P, c_int64, P, P, P, P, c_int, c_int, c_int, P, P, P, P, c_int64, c_int, P, P, P]),
     'bdv_resized_crop_f32': (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, c_int, P, P]),
     'bdv_temporal_nanreduce_f32': (c_int, [P, c_int64, P, P, P, P, c_int, c_int64, c_int, c_int, P, P]),
     'bdv_jpeg_encode_info': (c_int, [c_int, c_int, c_int, POINTER(JpegInfo)]),

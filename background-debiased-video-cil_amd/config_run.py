@@ -188,6 +188,38 @@ _DATASET_COMMON = dict(with_offset=False, multi_class=False, num_classes=None, m
                        dynamic_length=False)
 
 
+_BG_METHODS = ('tmf', 'sim_cam', 'person_masked')          # background.METHODS
+_BG_EXTRACTION_KEYS = ('method', 'det_file', 'det_thres', 'dilate', 'min_visible', 'max_hole_fraction', 'filename_tmpl')
+
+
+def bg_extraction_spec(train) -> Optional[dict]:
+    """``data.train.bg_extraction`` checked and as ``resolve_bg_files`` takes it, or None when the config has none (missing backgrounds
+    are then made as the reference makes them, by the temporal median).  The key is this package's own: ``dict(method='person_masked',
+    det_file=..., det_thres=..., dilate=..., min_visible=..., max_hole_fraction=...)`` extracts person-free backgrounds from the
+    ActorCutMix detection file; ``filename_tmpl`` defaults to the dataset's."""
+    ext = train.get('bg_extraction')
+    if ext is None:
+        return None
+    where = 'data.train bg_extraction'
+    if not hasattr(ext, 'items'):
+        _fail(where, f'{ext!r} is not a dict')
+    ext = dict(ext)
+    for key in ext:
+        if key not in _BG_EXTRACTION_KEYS:
+            _fail(f'{where} {key}', f'unknown key (the keys are {", ".join(_BG_EXTRACTION_KEYS)})')
+    method = ext.setdefault('method', 'tmf')               # extract_backgrounds' default
+    if method not in _BG_METHODS:
+        _fail(f'{where} method', f'{method!r} is not one of {_BG_METHODS}')
+    if method != 'person_masked':
+        if len(ext) > 1:
+            _fail(f'{where} {[k for k in ext if k != "method"][0]}', f"belongs to method 'person_masked', not {method!r}")
+        return ext
+    if not ext.get('det_file'):
+        _fail(f'{where} det_file', "missing: method 'person_masked' reads the ActorCutMix detection file")
+    ext.setdefault('filename_tmpl', train.get('filename_tmpl', 'img_{:05}.jpg'))
+    return ext
+
+
 def clip_loader_spec(config) -> dict:
     """``{'loader': class name, 'kwargs': constructor arguments, 'dataset': what the loop reads from data.train}`` for a config (see the
     module docstring).  ``kwargs['randAug']`` is the ``dict(n, m, prob)`` of the RandAugment stage, which the loaders accept in place of
@@ -262,6 +294,11 @@ def clip_loader_spec(config) -> dict:
         dataset.update(bg_dir=train.get('bg_dir'), extract_bg_if_not_found=train.get('extract_bg_if_not_found', True),
                        back_ground_from_bg_dir=train.get('back_ground_from_bg_dir', True), map_bg_to_video=train.get('map_bg_to_video', True),
                        merge_bg_files=train.get('merge_bg_files', True), bg_image_extension=train.get('bg_image_extension', '.jpg'))
+        ext = bg_extraction_spec(train)
+        if ext is not None:
+            dataset.update(bg_extraction=ext)
+    elif train.get('bg_extraction') is not None:
+        _fail(f'data.train ({kind}) bg_extraction', 'only BackgroundMixDataset reads a bg_dir')
     return dict(loader=loader, kwargs=kw, dataset=dataset)
 
 

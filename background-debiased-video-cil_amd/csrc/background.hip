@@ -24,6 +24,14 @@ namespace {
 // only touches its own 32 dwords, which all sit in bank (lane % 64) -- no conflicts, no barriers.  For an even count whose two
 // middle values have different high nibbles (15 / 16, 127 / 128), the upper one is the smallest value above the lower one's
 // nibble bucket, kept as a running minimum in pass 2.
+//
+// The person-masked median (bdv_temporal_masked_median_u8) is the same scheme with a sample count per byte position: a frame's
+// sample is left out of both passes where one of the frame's boxes contains the pixel.  A lane's 4 bytes span pixels a = p0 / 3 and
+// a + 1 (the first 3 - p0 % 3 bytes are a's), so a frame costs two containment tests per box; the box rows of a frame are the same
+// for the whole wave and come through scalar loads.  Hole fallback: the lanes that own a byte with fewer than min_visible samples
+// run the unmasked two passes as well, in the same launch and in the same LDS column, and take those bytes from them -- the
+// select against bdv_temporal_median_u8's statistic, narrowed to the waves that hold a hole (no second histogram set, so LDS
+// stays at 32 KB per block; no second launch over the whole batch, no flag read back on the host).
 constexpr int kMedThreads = 256;
 
 template <bool kAligned>
@@ -37,27 +45,47 @@ __device__ __forceinline__ unsigned load4(const unsigned char* __restrict__ p, u
   }
 }
 
-template <bool kAligned>
-__global__ __launch_bounds__(kMedThreads) void temporal_median_kernel(const unsigned char* __restrict__ frames,
-                                                                      const long long* __restrict__ first,
-                                                                      const int* __restrict__ counts, unsigned P,
-                                                                      unsigned char* __restrict__ out) {
-  __shared__ unsigned hist[32 * kMedThreads];
-  const unsigned tid = threadIdx.x;
-  const unsigned p0 = (blockIdx.x * kMedThreads + tid) * 4u;
-  if (p0 >= P) return;
-  const unsigned nb = P - p0 < 4u ? P - p0 : 4u;
-  const int v = blockIdx.y;
-  const int F = counts[v];
-  const unsigned char* src = frames + (size_t)first[v] * P + p0;
-  unsigned* h = hist + tid;
+// What a lane needs to tell which of its bytes a frame's boxes cover.  box_first is indexed by the frame's number in the batch.
+struct LaneMask {
+  const int* __restrict__ box_first;
+  const int4* __restrict__ boxes;
+  int xa, ya, xb, yb;            // pixels a and a + 1
+  unsigned bytes_a;              // bit k set: byte k belongs to pixel a
+};
+
+// bit k set: byte k of the lane is visible (outside every box) in batch frame fg
+__device__ __forceinline__ unsigned visible_bytes(const LaneMask& m, long long fg) {
+  const int b0 = __builtin_amdgcn_readfirstlane(m.box_first[fg]), b1 = __builtin_amdgcn_readfirstlane(m.box_first[fg + 1]);
+  bool in_a = false, in_b = false;
+  for (int b = b0; b < b1; ++b) {
+    const int4 r = m.boxes[b];
+    in_a |= m.xa >= r.x && m.xa < r.z && m.ya >= r.y && m.ya < r.w;
+    in_b |= m.xb >= r.x && m.xb < r.z && m.yb >= r.y && m.yb < r.w;
+  }
+  return (in_a ? 0u : m.bytes_a) | (in_b ? 0u : ~m.bytes_a & 15u);
+}
+
+// The median of each of the lane's 4 byte positions over frames src, src + P, ... (F of them), packed into a dword.  kMasked: only
+// over the samples visible_bytes() keeps; n[k] returns their number per byte, and a byte with none gives an arbitrary value.
+// h: the lane's LDS column (32 dwords, stride kMedThreads).
+template <bool kAligned, bool kMasked>
+__device__ __forceinline__ unsigned median4(const unsigned char* __restrict__ src, unsigned P, unsigned nb, int F, unsigned* h,
+                                            const LaneMask& m, long long f0, int (&n)[4]) {
 #pragma unroll
   for (int s = 0; s < 32; ++s) h[s * kMedThreads] = 0u;
 
   // pass 1: high nibbles.  Four frames' loads are issued before their counts, to keep several loads in flight per lane.
-  auto count_hi = [&](unsigned w) {
+  int na = 0, nb2 = 0;             // masked: visible samples of pixel a (byte 0 is always its) and of pixel a + 1 (byte 3)
+  auto count_hi = [&](unsigned w, int f) {
+    unsigned vis = 15u;
+    if constexpr (kMasked) {
+      vis = visible_bytes(m, f0 + f);
+      na += (int)(vis & 1u);
+      nb2 += (int)(vis >> 3);
+    }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) atomicAdd(h + ((k >> 1) * 16 + ((w >> (8 * k + 4)) & 15u)) * kMedThreads, 1u << (16 * (k & 1)));
+    for (int k = 0; k < 4; ++k)
+      atomicAdd(h + ((k >> 1) * 16 + ((w >> (8 * k + 4)) & 15u)) * kMedThreads, ((vis >> k) & 1u) << (16 * (k & 1)));
   };
   int f = 0;
   for (; f + 4 <= F; f += 4) {
@@ -65,14 +93,14 @@ __global__ __launch_bounds__(kMedThreads) void temporal_median_kernel(const unsi
 #pragma unroll
     for (int j = 0; j < 4; ++j) w[j] = load4<kAligned>(src + (size_t)(f + j) * P, nb);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) count_hi(w[j]);
+    for (int j = 0; j < 4; ++j) count_hi(w[j], f + j);
   }
-  for (; f < F; ++f) count_hi(load4<kAligned>(src + (size_t)f * P, nb));
-  const int k1 = (F - 1) >> 1;            // rank of the lower middle value (the middle one for odd F)
-  const bool even = (F & 1) == 0;
+  for (; f < F; ++f) count_hi(load4<kAligned>(src + (size_t)f * P, nb), f);
   unsigned bucket[4], rank[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
+    n[k] = kMasked ? ((m.bytes_a >> k) & 1u ? na : nb2) : F;
+    const int k1 = (n[k] - 1) >> 1;        // rank of the lower middle value (the middle one for an odd count)
     int below = 0, b = 0;
     for (; b < 15; ++b) {
       const int c = (int)((h[((k >> 1) * 16 + b) * kMedThreads] >> (16 * (k & 1))) & 0xffffu);
@@ -87,12 +115,14 @@ __global__ __launch_bounds__(kMedThreads) void temporal_median_kernel(const unsi
 
   // pass 2: low nibbles inside the chosen bucket, and the smallest value above it
   unsigned above[4] = {256u, 256u, 256u, 256u};
-  auto count_lo = [&](unsigned w) {
+  auto count_lo = [&](unsigned w, int f) {
+    unsigned vis = 15u;
+    if constexpr (kMasked) vis = visible_bytes(m, f0 + f);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const unsigned x = (w >> (8 * k)) & 255u, hi = x >> 4;
-      if (hi > bucket[k]) above[k] = x < above[k] ? x : above[k];
-      atomicAdd(h + ((k >> 1) * 16 + (x & 15u)) * kMedThreads, hi == bucket[k] ? 1u << (16 * (k & 1)) : 0u);
+      const unsigned x = (w >> (8 * k)) & 255u, hi = x >> 4, on = (vis >> k) & 1u;
+      if (hi > bucket[k] && on) above[k] = x < above[k] ? x : above[k];
+      atomicAdd(h + ((k >> 1) * 16 + (x & 15u)) * kMedThreads, hi == bucket[k] ? on << (16 * (k & 1)) : 0u);
     }
   };
   for (f = 0; f + 4 <= F; f += 4) {
@@ -100,9 +130,9 @@ __global__ __launch_bounds__(kMedThreads) void temporal_median_kernel(const unsi
 #pragma unroll
     for (int j = 0; j < 4; ++j) w[j] = load4<kAligned>(src + (size_t)(f + j) * P, nb);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) count_lo(w[j]);
+    for (int j = 0; j < 4; ++j) count_lo(w[j], f + j);
   }
-  for (; f < F; ++f) count_lo(load4<kAligned>(src + (size_t)f * P, nb));
+  for (; f < F; ++f) count_lo(load4<kAligned>(src + (size_t)f * P, nb), f);
   unsigned res = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -114,8 +144,8 @@ __global__ __launch_bounds__(kMedThreads) void temporal_median_kernel(const unsi
     }
     if (lo == 15) c = (h[((k >> 1) * 16 + 15) * kMedThreads] >> (16 * (k & 1))) & 0xffffu;
     const unsigned a = (bucket[k] << 4) | lo;
-    unsigned m = a;
-    if (even) {
+    unsigned med = a;
+    if ((n[k] & 1) == 0) {
       unsigned b;
       if (below + c > rank[k] + 1) {           // the upper middle value has the same low nibble
         b = a;
@@ -127,16 +157,75 @@ __global__ __launch_bounds__(kMedThreads) void temporal_median_kernel(const unsi
             break;
           }
       }
-      m = (a + b) >> 1;                        // numpy: the float64 mean of the two, truncated by astype(uint8)
+      med = (a + b) >> 1;                      // numpy: the float64 mean of the two, truncated by astype(uint8)
     }
-    res |= m << (8 * k);
+    res |= (med & 255u) << (8 * k);
   }
-  unsigned char* dst = out + (size_t)v * P + p0;
-  if (kAligned) {
+  return res;
+}
+
+template <bool kAligned>
+__device__ __forceinline__ void store4(unsigned char* __restrict__ dst, unsigned res, unsigned nb) {
+  if constexpr (kAligned) {
     *reinterpret_cast<unsigned*>(dst) = res;
   } else {
     for (unsigned k = 0; k < nb; ++k) dst[k] = (unsigned char)(res >> (8 * k));
   }
+}
+
+template <bool kAligned>
+__global__ __launch_bounds__(kMedThreads) void temporal_median_kernel(const unsigned char* __restrict__ frames,
+                                                                      const long long* __restrict__ first,
+                                                                      const int* __restrict__ counts, unsigned P,
+                                                                      unsigned char* __restrict__ out) {
+  __shared__ unsigned hist[32 * kMedThreads];
+  const unsigned tid = threadIdx.x;
+  const unsigned p0 = (blockIdx.x * kMedThreads + tid) * 4u;
+  if (p0 >= P) return;
+  const unsigned nb = P - p0 < 4u ? P - p0 : 4u;
+  const int v = blockIdx.y;
+  int n[4];
+  const unsigned res = median4<kAligned, false>(frames + (size_t)first[v] * P + p0, P, nb, counts[v], hist + tid, LaneMask{}, 0, n);
+  store4<kAligned>(out + (size_t)v * P + p0, res, nb);
+}
+
+template <bool kAligned>
+__global__ __launch_bounds__(kMedThreads) void temporal_masked_median_kernel(const unsigned char* __restrict__ frames,
+                                                                             const long long* __restrict__ first,
+                                                                             const int* __restrict__ counts, unsigned P, int W,
+                                                                             const int* __restrict__ box_first,
+                                                                             const int4* __restrict__ boxes, int min_visible,
+                                                                             unsigned char* __restrict__ out,
+                                                                             unsigned short* __restrict__ visible) {
+  __shared__ unsigned hist[32 * kMedThreads];
+  const unsigned tid = threadIdx.x;
+  const unsigned p0 = (blockIdx.x * kMedThreads + tid) * 4u;
+  if (p0 >= P) return;
+  const unsigned nb = P - p0 < 4u ? P - p0 : 4u;
+  const int v = blockIdx.y;
+  const int F = counts[v];
+  const long long f0 = first[v];
+  const unsigned char* src = frames + (size_t)f0 * P + p0;
+  const unsigned pa = p0 / 3u, na_bytes = 3u - (p0 - pa * 3u);      // pixel a holds the lane's first 1..3 bytes
+  LaneMask m;
+  m.box_first = box_first;
+  m.boxes = boxes;
+  m.ya = (int)(pa / (unsigned)W);
+  m.xa = (int)(pa - (unsigned)m.ya * (unsigned)W);
+  m.yb = (int)((pa + 1u) / (unsigned)W);                            // row H past the last pixel: inside no box
+  m.xb = (int)(pa + 1u - (unsigned)m.yb * (unsigned)W);
+  m.bytes_a = (1u << na_bytes) - 1u;
+  int n[4], nall[4];
+  unsigned res = median4<kAligned, true>(src, P, nb, F, hist + tid, m, f0, n);
+  unsigned holes = 0;                                                // 0xff in the bytes with fewer than min_visible samples
+#pragma unroll
+  for (int k = 0; k < 4; ++k) holes |= ((unsigned)k < nb && n[k] < min_visible ? 255u : 0u) << (8 * k);
+  if (holes) res = (res & ~holes) | (median4<kAligned, false>(src, P, nb, F, hist + tid, m, f0, nall) & holes);
+  store4<kAligned>(out + (size_t)v * P + p0, res, nb);
+  // a pixel's count is written by the lane that holds its first byte
+  const size_t npix = P / 3u;
+  if (na_bytes == 3u) visible[(size_t)v * npix + pa] = (unsigned short)n[0];
+  if (p0 + na_bytes < P) visible[(size_t)v * npix + pa + 1u] = (unsigned short)n[3];
 }
 
 // ---- JPEG forward stage ---------------------------------------------------------------------------------------------------------
@@ -555,6 +644,48 @@ extern "C" int bdv_temporal_median_u8(const uint8_t* frames, int64_t total_frame
   else
     hipLaunchKernelGGL(temporal_median_kernel<false>, grid, dim3(kMedThreads), 0, s, frames, (const long long*)first, counts, P, out);
   BDV_LAUNCH_CHECK("bdv_temporal_median_u8");
+  return BDV_OK;
+}
+
+extern "C" int bdv_temporal_masked_median_u8(const uint8_t* frames, int64_t total_frames, const int64_t* first, const int32_t* counts,
+                                             const int64_t* first_host, const int32_t* counts_host, int V, int H, int W,
+                                             const int32_t* box_first, const int32_t* boxes, const int32_t* box_first_host,
+                                             const int32_t* boxes_host, int64_t num_boxes, int min_visible, uint8_t* out,
+                                             uint16_t* visible, void* stream) {
+  const char* who = "bdv_temporal_masked_median_u8";
+  BDV_REQUIRE(frames && first && counts && first_host && counts_host && out && visible && box_first && box_first_host, "%s: null pointer", who);
+  BDV_REQUIRE(V > 0 && V <= 65535 && H > 0 && W > 0, "%s: bad batch (V=%d, %d x %d)", who, V, H, W);
+  BDV_REQUIRE((long long)H * W * 3 < (1ll << 31) - 1024, "%s: frame too large", who);
+  BDV_REQUIRE(min_visible >= 1, "%s: min_visible %d (at least 1)", who, min_visible);
+  BDV_REQUIRE(num_boxes >= 0 && num_boxes < (1ll << 31) && (num_boxes == 0 || (boxes && boxes_host)), "%s: bad box table (%lld rows)", who,
+              (long long)num_boxes);
+  BDV_REQUIRE(num_boxes == 0 || bdv_aligned16(boxes), "%s: boxes must be 16-byte aligned", who);
+  for (int v = 0; v < V; ++v)
+    BDV_REQUIRE(counts_host[v] >= 1 && counts_host[v] <= 65535 && first_host[v] >= 0 && first_host[v] + counts_host[v] <= total_frames,
+                "%s: video %d: frames %lld..%lld of %lld (1..65535 frames per video)", who, v, (long long)first_host[v],
+                (long long)first_host[v] + counts_host[v] - 1, (long long)total_frames);
+  BDV_REQUIRE(box_first_host[0] >= 0 && box_first_host[total_frames] <= num_boxes, "%s: box_first spans rows %d..%d of %lld", who,
+              box_first_host[0], box_first_host[total_frames], (long long)num_boxes);
+  for (int64_t f = 0; f < total_frames; ++f)
+    BDV_REQUIRE(box_first_host[f] <= box_first_host[f + 1], "%s: box_first decreases at frame %lld (%d > %d)", who, (long long)f,
+                box_first_host[f], box_first_host[f + 1]);
+  for (int64_t b = box_first_host[0]; b < box_first_host[total_frames]; ++b) {
+    const int32_t* r = boxes_host + 4 * b;
+    BDV_REQUIRE(0 <= r[0] && r[0] <= r[2] && r[2] <= W && 0 <= r[1] && r[1] <= r[3] && r[3] <= H,
+                "%s: box %lld (%d, %d, %d, %d) is not inside the %d x %d frame", who, (long long)b, r[0], r[1], r[2], r[3], W, H);
+  }
+  const unsigned P = (unsigned)H * (unsigned)W * 3u;
+  const bool aligned = (P & 3u) == 0 && (((uintptr_t)frames) & 3) == 0 && (((uintptr_t)out) & 3) == 0;
+  const unsigned groups = (P + 3u) / 4u;
+  dim3 grid((groups + kMedThreads - 1) / kMedThreads, (unsigned)V);
+  hipStream_t s = (hipStream_t)stream;
+  if (aligned)
+    hipLaunchKernelGGL(temporal_masked_median_kernel<true>, grid, dim3(kMedThreads), 0, s, frames, (const long long*)first, counts, P, W,
+                       box_first, (const int4*)boxes, min_visible, out, visible);
+  else
+    hipLaunchKernelGGL(temporal_masked_median_kernel<false>, grid, dim3(kMedThreads), 0, s, frames, (const long long*)first, counts, P, W,
+                       box_first, (const int4*)boxes, min_visible, out, visible);
+  BDV_LAUNCH_CHECK(who);
   return BDV_OK;
 }
 

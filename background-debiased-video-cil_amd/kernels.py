@@ -1056,6 +1056,35 @@ def temporal_nanreduce_f32(frames, counts, mode: int = 0, zero_is_missing: bool 
     return out
 
 
+def temporal_masked_median_u8(frames, counts, box_first, boxes, min_visible: int = 1):
+    """frames (sum(counts), H, W, 3) u8 on the device, the videos' frames back to back; counts: frames per video; box_first
+    (sum(counts) + 1,) / boxes (nb, 4) int32 host arrays or tensors: the CSR table of half-open person boxes ``x0, y0, x1, y1`` per
+    frame -> ``(out (V, H, W, 3) uint8, visible (V, H, W) uint16)``: the median over the frames in which no box covers the pixel, the
+    plain median where fewer than ``min_visible`` such frames exist, and their number (the detector-free stand-in for
+    cil_tools/type_b_and_c_bg.py:47-54)."""
+    _chk(frames, dtype=torch.uint8, name='frames')
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f'temporal_masked_median_u8: expected (F,H,W,3), got {tuple(frames.shape)}')
+    counts_h = torch.tensor([int(c) for c in counts], dtype=torch.int32)
+    V, H, W = int(counts_h.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    first_h = torch.zeros(V, dtype=torch.int64)
+    first_h[1:] = torch.cumsum(counts_h[:-1], 0)
+    bf_h = torch.as_tensor(box_first).to('cpu', torch.int32).reshape(-1).contiguous()
+    bx_h = torch.as_tensor(boxes).to('cpu', torch.int32).reshape(-1, 4).contiguous()
+    if bf_h.shape[0] != frames.shape[0] + 1:
+        raise ValueError(f'temporal_masked_median_u8: box_first has {bf_h.shape[0]} entries for {frames.shape[0]} frames')
+    dev = frames.device
+    out = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev)
+    visible = torch.empty((V, H, W), dtype=torch.uint16, device=dev)
+    first_d, counts_d, bf_d, bx_d = first_h.to(dev), counts_h.to(dev), bf_h.to(dev), bx_h.to(dev)
+    nb = int(bx_h.shape[0])
+    check(lib().bdv_temporal_masked_median_u8(_p(frames), int(frames.shape[0]), _p(first_d), _p(counts_d), first_h.data_ptr(),
+                                              counts_h.data_ptr(), V, H, W, _p(bf_d), _p(bx_d) if nb else None, bf_h.data_ptr(),
+                                              bx_h.data_ptr() if nb else None, nb, int(min_visible), _p(out), _p(visible), _stream()),
+          'bdv_temporal_masked_median_u8')
+    return out, visible
+
+
 def resize_linear_u8(frames, Hd: int, Wd: int, boxes=None):
     """``cv2.resize(..., INTER_LINEAR)`` of uint8 frames (.., Hs, Ws, 3) -> (.., Hd, Wd, 3).  ``boxes``: None, or for frames of shape
     (B, T, Hs, Ws, 3) a list / (B, 4) array of per-clip crops (x0, y0, w, h) that are cut out and resized in the same pass

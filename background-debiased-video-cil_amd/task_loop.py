@@ -510,6 +510,9 @@ class CILTaskLoop:
         if not bg.get('back_ground_from_bg_dir', True):
             return records
         kw = dict(map_bg_to_video=bg.get('map_bg_to_video', True), bg_image_extension=bg.get('bg_image_extension', '.jpg'))
+        if bg.get('bg_extraction') is not None:
+            from .config_run import bg_extraction_spec
+            kw.update(bg_extraction=bg_extraction_spec(bg))
         if self.rank == 0:
             records.bg_files = resolve_bg_files(records.video_infos, bg['bg_dir'],
                                                 extract_bg_if_not_found=bg.get('extract_bg_if_not_found', True), **kw)

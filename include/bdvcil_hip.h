@@ -604,6 +604,28 @@ int bdv_jpeg_reconstruct_u8(const short* coefs, const unsigned short* qts, const
  * of the mean of the two middle ones for an even count.  One launch; the frame stack is read twice. */
 int bdv_temporal_median_u8(const uint8_t* frames, int64_t total_frames, const int64_t* first, const int32_t* counts,
                            const int64_t* first_host, const int32_t* counts_host, int V, int H, int W, uint8_t* out, void* stream);
+/* Person-masked backgrounds: the reference filters extracted backgrounds with a Mask-RCNN person detector and keeps those in which
+ * no person is left (cil_tools/type_b_and_c_bg.py:47-54), because the temporal median of bg_extraction_tmf
+ * (libs/loader/comix_loader.py:148-164) keeps a person who covers a pixel in half or more of the frames.  The substitute here
+ * needs no detector: the median over the frames in which the pixel lies outside every person box of the ActorCutMix detection
+ * file, and the number of such frames per pixel.
+ *
+ * bdv_temporal_masked_median_u8 (device): frames / first / counts / V / H / W as for bdv_temporal_median_u8.  The boxes are a CSR
+ * table over the batch's frames: box_first (total_frames + 1) int32, boxes (num_boxes, 4) int32 rows x0, y0, x1, y1, half-open
+ * (pixel (x, y) is covered when x0 <= x < x1 and y0 <= y < y1, as mask[y0:y1, x0:x1] of BuildHumanMask); frame f of the batch owns
+ * rows box_first[f] .. box_first[f + 1] - 1.  Both are device arrays (boxes 16-byte aligned) with the same values on the host in
+ * box_first_host / boxes_host, checked before the launch: box_first monotone within 0..num_boxes, 0 <= x0 <= x1 <= W,
+ * 0 <= y0 <= y1 <= H.  num_boxes may be 0 (boxes then unused).  min_visible >= 1.
+ * visible (V, H, W) uint16 = the number of the video's frames none of whose boxes covers the pixel.  out (V, H, W, 3) uint8: where
+ * visible >= min_visible, np.median over those frames, .astype(uint8) (the middle value for an odd count, the floor of the mean of
+ * the two middle ones for an even count); elsewhere (a hole) np.median over ALL the video's frames, bdv_temporal_median_u8's value.
+ * With no boxes out is bdv_temporal_median_u8's, byte for byte, and visible the frame count.  One launch; the stack is read twice,
+ * and twice more by the waves that own a hole. */
+int bdv_temporal_masked_median_u8(const uint8_t* frames, int64_t total_frames, const int64_t* first, const int32_t* counts,
+                                  const int64_t* first_host, const int32_t* counts_host, int V, int H, int W,
+                                  const int32_t* box_first, const int32_t* boxes, const int32_t* box_first_host,
+                                  const int32_t* boxes_host, int64_t num_boxes, int min_visible, uint8_t* out, uint16_t* visible,
+                                  void* stream);
 /* Simulated-camera-motion backgrounds: sim_cam_motion_bg_extract (cil_tools/extract_background.py:78-99) passes every frame, as
  * a float image, through torchvision's RandomResizedCrop(size=100), sets exact zeros to NaN and takes np.nanmedian / np.nanmean
  * over time, .astype(np.uint8).

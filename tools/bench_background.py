@@ -7,6 +7,7 @@ job script can give each its own time limit:
     python tools/bench_background.py --phase gpu     --data DIR --out R  # resolve_bg_files end to end (decode, median, encode, write)
     rocprofv3 --kernel-trace --stats --output-format csv -d S -- python tools/bench_background.py --phase kernels --data DIR
     python tools/bench_background.py --phase report  --out R --stats S > profiles/r04_background.txt
+    python tools/bench_background.py --phase masked  > profiles/person_masked.txt   # person-masked median beside the plain one
 
 The CPU path decodes with Pillow (cv2 is not installed; both run libjpeg-turbo with the same defaults).
 
@@ -127,6 +128,81 @@ def _gpu_sim_cam(a):
     print(key, json.dumps(res))
 
 
+def _masked_phase(a):
+    """The person-masked median beside the plain one on one random stack (64 videos x 150 frames of 240 x 320), interleaved in one
+    process: per round one launch of each variant between device events; medians and minima over the rounds.  The C entry points are
+    called on tensors uploaded beforehand, so the events bracket the host-side table check and the kernel, not Python's part."""
+    import torch
+    from bdvcil_amd import background as BG
+    from bdvcil_amd._lib import check, lib
+    from bdvcil_amd.kernels import _p, _stream
+    videos, frames_per, rounds = 64, 150, 12
+    total = videos * frames_per
+    frames = torch.randint(0, 256, (total, H, W, 3), dtype=torch.uint8, device='cuda')
+    counts_h = torch.full((videos,), frames_per, dtype=torch.int32)
+    first_h = torch.arange(videos, dtype=torch.int64) * frames_per
+    counts_d, first_d = counts_h.cuda(), first_h.cuda()
+    out = torch.empty(videos, H, W, 3, dtype=torch.uint8, device='cuda')
+    visible = torch.empty(videos, H, W, dtype=torch.uint16, device='cuda')
+
+    def table(second):
+        """Per frame a person walking through (80 x 160, two pixels a frame); ``second``: 'walks' adds another one (40 x 100, three
+        pixels a frame), 'stays' one who never moves (40 x 100: every pixel of it is a hole)."""
+        rows = []
+        for v in range(videos):
+            for f in range(frames_per):
+                rows.append([(2 * f + 7 * v) % 240, 40, (2 * f + 7 * v) % 240 + 80, 200])
+                if second:
+                    x = (3 * f + 11 * v) % 280 if second == 'walks' else 260
+                    rows.append([x, 120, x + 40, 220])
+        per = 2 if second else 1
+        bf, bx = torch.arange(0, per * total + 1, per, dtype=torch.int32), torch.tensor(rows, dtype=torch.int32)
+        return bf, bx, bf.cuda(), bx.cuda()
+
+    def plain():
+        check(lib().bdv_temporal_median_u8(_p(frames), total, _p(first_d), _p(counts_d), first_h.data_ptr(), counts_h.data_ptr(), videos, H, W,
+                                           _p(out), _stream()), 'bdv_temporal_median_u8')
+
+    def masked(t):
+        bf, bx, bf_d, bx_d = t
+        nb = int(bx.shape[0])
+        check(lib().bdv_temporal_masked_median_u8(_p(frames), total, _p(first_d), _p(counts_d), first_h.data_ptr(), counts_h.data_ptr(), videos,
+                                                  H, W, _p(bf_d), _p(bx_d) if nb else None, bf.data_ptr(), bx.data_ptr() if nb else None, nb, 1,
+                                                  _p(out), _p(visible), _stream()), 'bdv_temporal_masked_median_u8')
+
+    none = (torch.zeros(total + 1, dtype=torch.int32), torch.zeros((0, 4), dtype=torch.int32))
+    none = none + (none[0].cuda(), none[1].cuda())
+    variants = [('bdv_temporal_median_u8', plain),
+                ('masked, empty box table', lambda: masked(none)),
+                ('masked, 1 box per frame, no holes', lambda t=table(None): masked(t)),
+                ('masked, 2 boxes per frame, no holes', lambda t=table('walks'): masked(t)),
+                ('masked, 2 boxes per frame, one never moves (holes)', lambda t=table('stays'): masked(t))]
+    shares = {}
+    for name, fn in variants:                   # code objects, and the hole share of each table
+        fn()
+        if fn is not plain:
+            shares[name] = sum(BG.hole_fractions(visible)) / videos
+    torch.cuda.synchronize()
+    ms = {name: [] for name, _ in variants}
+    for _ in range(rounds):
+        for name, fn in variants:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms[name].append(ev[0].elapsed_time(ev[1]))
+    stack = total * H * W * 3
+    print(f'# tools/bench_background.py --phase masked: {videos} videos x {frames_per} frames of {W} x {H} (random bytes, {stack / 2**30:.2f} GiB), '
+          f'one MI355X; {rounds} interleaved rounds, one launch of each per round, device events around the C call (tables uploaded beforehand)')
+    base = float(np.median(ms[variants[0][0]]))
+    for name, _ in variants:
+        t = np.asarray(ms[name])
+        holes = f', {shares[name] * 100:.2f} % of the pixels are holes' if name in shares else ''
+        print(f'{name}: median {np.median(t):.3f} ms, min {t.min():.3f} ms, {2 * stack / np.median(t) / 1e9:.2f} TB/s over two reads of the stack, '
+              f'{np.median(t) / base:.2f}x the plain median{holes}')
+
+
 def _videos(data):
     return sorted(glob.glob(os.path.join(data, 'frames', 'v_*')))
 
@@ -144,7 +220,7 @@ def _record(out, key, value):
 def main():
     global FRAMES
     ap = argparse.ArgumentParser()
-    ap.add_argument('--phase', required=True, choices=['make', 'cpu', 'gpu', 'kernels', 'report'])
+    ap.add_argument('--phase', required=True, choices=['make', 'cpu', 'gpu', 'kernels', 'report', 'masked'])
     ap.add_argument('--data', default='bench_out/background')
     ap.add_argument('--out', default='bench_out/background.json')
     ap.add_argument('--stats', default=None)
@@ -154,6 +230,8 @@ def main():
     ap.add_argument('--frames', type=int, default=FRAMES, help='files per video written by --phase make')
     a = ap.parse_args()
     FRAMES = a.frames
+    if a.phase == 'masked':
+        return _masked_phase(a)
     if a.method == 'sim_cam' and a.phase in ('cpu', 'gpu', 'report'):
         return _sim_cam_phase(a)
     frame_bytes, stack = H * W * 3, VIDEOS * FRAMES * H * W * 3
