@@ -56,6 +56,7 @@ from .recognizer import CILRecognizer2D, Recognizer2D  # noqa: F401
 from .blending import CutmixBlending, MixupBlending  # noqa: F401
 from .resnet3d import I3DHead, Recognizer3D, ResNet3d  # noqa: F401
 from .hooks import OutputHook, rgetattr  # noqa: F401
+from .functional import KDPodFlatFn, KDPodSpatialFn, kd_pod_flat, kd_pod_spatial  # noqa: F401
 from .optim import (CILTSMOptimizerConstructor, CILTSMOptimizerConstructorImprovised, FusedSGD, build_lr_scheduler,  # noqa: F401
                     build_optimizer)
 from .frontend import BackgroundCropFrontEnd, BackgroundMixFrontEnd, CropFrontEnd, MultiScaleCropResize, TrainClipFrontEnd, crop_offsets  # noqa: F401
@@ -65,7 +66,7 @@ from .augment import RandAugment  # noqa: F401
 from .background import (encode_jpeg, extract_background, extract_backgrounds, person_box_table, random_resized_crop_boxes,  # noqa: F401
                          resized_crop, resolve_bg_files, sim_cam_frame_files, temporal_masked_median, temporal_median,
                          temporal_nanreduce)
-from .cil_step import (TrainEngine, base_training_step, icarl_training_step, icarl_video_mix_training_step,  # noqa: F401
+from .cil_step import (KD_TYPES, TrainEngine, base_training_step, check_kd_type, icarl_training_step, icarl_video_mix_training_step,  # noqa: F401
                        tubemix_draw)
 from .ddp import GradAllReducer, broadcast_parameters  # noqa: F401
 from .representation import Herding, ReprPredictor, class_means_from_repr, nme_classify  # noqa: F401

@@ -17,13 +17,59 @@ from .losses import SoftTargetCrossEntropy
 from .resnet_tsm import Nhwc4Frames
 
 
+KD_TYPES = ('mse', 'pod', 'pod_spatial', 'pod_flat')
+
+
+def check_kd_type(kd_type, num_modules: int, key: str = 'kd_type') -> List[str]:
+    """``kd_type`` as one entry of ``KD_TYPES`` per KD module: a string stands for every module, a sequence needs one entry per
+    name in ``kd_modules_names``.  Raises ``ValueError`` naming ``key``; touches no tensor."""
+    if isinstance(kd_type, str):
+        kinds = [kd_type] * num_modules
+        given = [kd_type]
+    else:
+        try:
+            kinds = given = list(kd_type)
+        except TypeError:
+            raise ValueError(f'{key}={kd_type!r}: expected one of {KD_TYPES} or a sequence of them') from None
+        if len(kinds) != num_modules:
+            raise ValueError(f'{key} has {len(kinds)} entries for {num_modules} kd_modules_names; give one string or one entry per module')
+    for k in given:
+        if not isinstance(k, str) or k not in KD_TYPES:
+            raise ValueError(f'{key}={k!r}: expected one of {KD_TYPES}')
+    return kinds
+
+
+def _kd_term(kind: str, m_name: str, cur: torch.Tensor, prev: torch.Tensor):
+    """One module's distillation loss.  'pod' is resolved on the hooked output: POD-spatial for a map (H*W > 1), POD-flat for
+    pooled (N, D, 1, 1) / (N, D) features."""
+    if kind == 'mse':
+        return Fn.kd_mse(cur, prev)
+    is_map = cur.dim() == 4 and cur.shape[2] * cur.shape[3] > 1
+    if kind == 'pod':
+        kind = 'pod_spatial' if is_map else 'pod_flat'
+    if kind == 'pod_flat':
+        if is_map or cur.dim() not in (2, 4):
+            raise ValueError(f"kd_type='pod_flat' for module {m_name!r}: its output has shape {tuple(cur.shape)}; POD-flat takes "
+                             f"(N, D) or (N, D, 1, 1) features, use 'pod_spatial' (or 'pod') for a feature map")
+        return Fn.kd_pod_flat(cur, prev)
+    if cur.dim() != 4:
+        raise ValueError(f"kd_type='pod_spatial' for module {m_name!r}: its output has shape {tuple(cur.shape)}, not (N, C, H, W)")
+    return Fn.kd_pod_spatial(cur, prev)
+
+
 def base_training_step(current_model: nn.Module, batch_data: Dict[str, torch.Tensor], current_task: int = 0,
                        prev_model: Optional[nn.Module] = None, current_hooks: Optional[OutputHook] = None,
                        prev_hooks: Optional[OutputHook] = None, kd_modules_names: Sequence[str] = (),
                        kd_weight_by_module: Sequence[float] = (), adaptive_scale_factors: Sequence[float] = (),
-                       kd_exemplar_only: bool = False, previous_task_num_classes: int = 0) -> Dict[str, torch.Tensor]:
+                       kd_exemplar_only: bool = False, previous_task_num_classes: int = 0,
+                       kd_type='mse') -> Dict[str, torch.Tensor]:
     """libs/cil/cil.py:512-556.  Returns the ``losses`` dict with an extra ``'loss'`` entry (the value the
-    reference returns from ``training_step``)."""
+    reference returns from ``training_step``).
+
+    ``kd_type`` (one of ``KD_TYPES``, or one per entry of ``kd_modules_names``): the per-module distillation loss.  'mse' is the
+    reference's ``nn.MSELoss``; 'pod_spatial' / 'pod_flat' are PODNet's pooled-output losses (UPSTREAM, unpinned; csrc/pod_kd.hip),
+    'pod' picks between the two by the hooked output's shape.  Weights, scale factors and ``kd_exemplar_only`` apply alike."""
+    kd_kinds = check_kd_type(kd_type, len(kd_modules_names))
     imgs, labels = batch_data['imgs'], batch_data['label']
     losses = current_model(imgs, labels, batch_data=batch_data)
     use_kd = prev_model is not None and len(kd_modules_names) > 0
@@ -33,7 +79,7 @@ def base_training_step(current_model: nn.Module, batch_data: Dict[str, torch.Ten
         with torch.no_grad():
             prev_model.forward_test(imgs)
         scale_factor = adaptive_scale_factors[current_task]
-        for m_name, kd_weight in zip(kd_modules_names, kd_weight_by_module):
+        for m_name, kd_weight, kd_kind in zip(kd_modules_names, kd_weight_by_module, kd_kinds):
             cur = current_hooks.get_layer_output(m_name)
             prev = prev_hooks.get_layer_output(m_name).detach()
             if kd_exemplar_only:
@@ -42,11 +88,12 @@ def base_training_step(current_model: nn.Module, batch_data: Dict[str, torch.Ten
                 # sample positions all the same, and so does this.)
                 indices = (batch_data['label'].view(-1) < previous_task_num_classes).nonzero().reshape(-1)
                 if indices.nelement():
-                    kd_loss = Fn.kd_mse(cur.index_select(0, indices).contiguous(), prev.index_select(0, indices).contiguous())
+                    kd_loss = _kd_term(kd_kind, m_name, cur.index_select(0, indices).contiguous(),
+                                       prev.index_select(0, indices).contiguous())
                 else:
                     kd_loss = 0
             else:
-                kd_loss = Fn.kd_mse(cur, prev)
+                kd_loss = _kd_term(kd_kind, m_name, cur, prev)
             losses[m_name] = kd_loss
             total_kd_loss = total_kd_loss + scale_factor * kd_weight * kd_loss
         losses['kd_loss'] = total_kd_loss

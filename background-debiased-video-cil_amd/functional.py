@@ -991,3 +991,49 @@ class KDMSEFn(torch.autograd.Function):
 
 def kd_mse(cur: torch.Tensor, prev: torch.Tensor) -> torch.Tensor:
     return KDMSEFn.apply(cur, prev.detach())
+
+
+class KDPodSpatialFn(torch.autograd.Function):
+    """PODNet's POD-spatial loss between hooked feature maps, in place of the MSE of libs/cil/cil.py:519-541 (csrc/pod_kd.hip).
+    Saves ``cur`` and the profile gradient ``G`` only: the teacher's maps are free after the forward.  ``prev`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, cur, prev):
+        loss, G, cur_nhwc = K.pod_spatial_fwd(cur, prev)
+        keep = cur_nhwc.permute(0, 3, 1, 2)          # cur itself when it is channels-last, else the one converted copy
+        ctx.save_for_backward(cur if keep.stride() == cur.stride() else keep, G)
+        ctx.cur_strides = cur.stride()
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        cur, G = ctx.saved_tensors
+        d = K.pod_spatial_bwd(cur, G, g.reshape(1).to(torch.float32).contiguous())
+        if d.stride() != ctx.cur_strides:
+            d = torch.empty_strided(d.shape, ctx.cur_strides, dtype=d.dtype, device=d.device).copy_(d)
+        return d, None
+
+
+class KDPodFlatFn(torch.autograd.Function):
+    """PODNet's POD-flat loss (F.cosine_embedding_loss, target 1) between pooled features, in place of the MSE of
+    libs/cil/cil.py:519-541; the forward kernel also produces the gradient for an upstream gradient of 1."""
+
+    @staticmethod
+    def forward(ctx, cur, prev):
+        loss, dunit = K.pod_flat(cur, prev)
+        ctx.save_for_backward(dunit)
+        ctx.cur_shape, ctx.cur_dtype = cur.shape, cur.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dunit,) = ctx.saved_tensors
+        return _scale_by(g, dunit).to(ctx.cur_dtype).view(ctx.cur_shape), None
+
+
+def kd_pod_spatial(cur: torch.Tensor, prev: torch.Tensor) -> torch.Tensor:
+    return KDPodSpatialFn.apply(cur, prev.detach())
+
+
+def kd_pod_flat(cur: torch.Tensor, prev: torch.Tensor) -> torch.Tensor:
+    return KDPodFlatFn.apply(cur, prev.detach())

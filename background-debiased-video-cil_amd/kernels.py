@@ -1542,6 +1542,74 @@ def kd_mse_bwd(cur, prev, gscale_dev, gscale_host=1.0):
     return d
 
 
+def _pod_nhwc(t: torch.Tensor, name: str) -> torch.Tensor:
+    """The (N, H, W, C) storage of a logical (N, C, H, W) activation: the channels-last strides of the hooked stage outputs are
+    used in place, any other layout costs one copy."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f'{name}: expected a tensor, got {type(t)}')
+    if not t.is_cuda:
+        raise RuntimeError(f'{name}: the HIP path needs a GPU tensor (got device {t.device}); there is no CPU fallback')
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'{name}: dtype {t.dtype}, expected torch.float32 or torch.bfloat16')
+    if t.dim() != 4:
+        raise ValueError(f'{name}: expected a 4-D (N, C, H, W) tensor, got shape {tuple(t.shape)}')
+    p = t.permute(0, 2, 3, 1)
+    return p if p.is_contiguous() else p.contiguous()
+
+
+def pod_spatial_fwd(cur, prev):
+    """POD-spatial distillation loss (csrc/pod_kd.hip) of logical (N, C, H, W) maps.  Returns ``(loss, G, cur_nhwc)``: the scalar,
+    the profile gradient (N, H+W, C) fp32 and the (N, H, W, C) storage of ``cur`` that was read (``cur``'s own when it is
+    channels-last), which together are what ``pod_spatial_bwd`` needs."""
+    a, b = _pod_nhwc(cur, 'pod_spatial: cur'), _pod_nhwc(prev, 'pod_spatial: prev')
+    if cur.shape != prev.shape or cur.dtype != prev.dtype:
+        raise ValueError(f'pod_spatial: cur {tuple(cur.shape)} {cur.dtype} and prev {tuple(prev.shape)} {prev.dtype} differ')
+    N, H, W, C = a.shape
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    G = torch.empty((N, H + W, C), dtype=torch.float32, device=a.device)
+    ws = workspace(lib().bdv_pod_workspace_bytes(N, C, H, W), a.device, 'pod')
+    check(lib().bdv_pod_spatial_fwd(_p(a), _p(b), _p(loss), _p(G), N, C, H, W, _p(ws), ws.numel(), _act_code(a), _stream()),
+          'bdv_pod_spatial_fwd')
+    return loss[0], G, a
+
+
+def pod_spatial_bwd(cur, G, gscale_dev):
+    """``dcur = gscale * 2 * cur * (G[n,h,c] + G[n,H+w,c])`` for the logical (N, C, H, W) ``cur``, in ``cur``'s strides and dtype."""
+    a = _pod_nhwc(cur, 'pod_spatial_bwd: cur')
+    N, H, W, C = a.shape
+    _chk(G, (N, H + W, C), name='pod_spatial_bwd: G')
+    _chk(gscale_dev.reshape(1), (1,), name='pod_spatial_bwd: gscale')
+    d = torch.empty_like(a)
+    check(lib().bdv_pod_spatial_bwd(_p(a), _p(G), _p(gscale_dev), _p(d), N, C, H, W, _act_code(a), _stream()), 'bdv_pod_spatial_bwd')
+    d = d.permute(0, 3, 1, 2)
+    if d.stride() == cur.stride():
+        return d
+    out = torch.empty_like(cur)
+    out.copy_(d)
+    return out
+
+
+def pod_flat(cur, prev):
+    """POD-flat (cosine embedding) distillation loss of (N, D) or (N, D, 1, 1) features.  Returns ``(loss, dcur_unit)`` with
+    ``dcur_unit`` (N, D) fp32 the gradient for an upstream gradient of 1."""
+    for t, name in ((cur, 'cur'), (prev, 'prev')):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'pod_flat: {name}: expected a tensor, got {type(t)}')
+        if not t.is_cuda:
+            raise RuntimeError(f'pod_flat: {name}: the HIP path needs a GPU tensor (got device {t.device}); there is no CPU fallback')
+    if cur.shape != prev.shape or cur.dtype != prev.dtype:
+        raise ValueError(f'pod_flat: cur {tuple(cur.shape)} {cur.dtype} and prev {tuple(prev.shape)} {prev.dtype} differ')
+    if cur.dim() not in (2, 4) or (cur.dim() == 4 and cur.shape[2] * cur.shape[3] != 1):
+        raise ValueError(f'pod_flat: expected (N, D) or (N, D, 1, 1) features, got shape {tuple(cur.shape)}')
+    N, D = cur.shape[0], cur.shape[1]
+    a, b = _chk_act(cur.reshape(N, D).contiguous(), name='pod_flat: cur'), _chk_act(prev.reshape(N, D).contiguous(), name='pod_flat: prev')
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    d = torch.empty((N, D), dtype=torch.float32, device=a.device)
+    ws = workspace(lib().bdv_pod_workspace_bytes(N, D, 1, 1), a.device, 'pod')
+    check(lib().bdv_pod_flat(_p(a), _p(b), _p(loss), _p(d), N, D, _p(ws), ws.numel(), _act_code(a), _stream()), 'bdv_pod_flat')
+    return loss[0], d
+
+
 def _dense_storage(t: torch.Tensor) -> torch.Tensor:
     """Flat view over the storage of a dense (possibly permuted) tensor."""
     if not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16):

@@ -26,7 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import kernels as K
-from .cil_step import base_training_step, icarl_training_step, icarl_video_mix_training_step
+from .cil_step import check_kd_type, base_training_step, icarl_training_step, icarl_video_mix_training_step
 from .ddp import GradAllReducer, broadcast_parameters
 from .hooks import OutputHook
 from .optim import build_lr_scheduler, build_optimizer
@@ -358,6 +358,22 @@ def check_loop_conv_arith(config) -> Optional[str]:
     return mode
 
 
+def check_loop_kd_type(config):
+    """The ``kd_type`` key of a loop config (absent = 'mse'), validated without touching the GPU: one of ``cil_step.KD_TYPES`` or one
+    per entry of ``kd_modules_names``.  Only ``methods='base'`` distils hooked features, so any other method with a ``kd_type`` that
+    is not 'mse' is refused: the key would be silently unused."""
+    kd_type = config.get('kd_type', 'mse')
+    names = list(config.get('kd_modules_names') or ())
+    kinds = check_kd_type(kd_type, len(names), key='kd_type')
+    default = kd_type == 'mse' if isinstance(kd_type, str) else all(k == 'mse' for k in kinds)
+    method = config.get('methods', 'base')
+    if not default and method != 'base':
+        raise ValueError(f"kd_type={kd_type!r} has no effect with methods={method!r}: only methods='base' distils hooked features")
+    if not default and not names:
+        raise ValueError(f'kd_type={kd_type!r} has no effect without kd_modules_names')
+    return kd_type if isinstance(kd_type, str) else kinds
+
+
 def _in_arith(fn):
     """A public entry point of the loop runs under the loop's ``conv_arith`` (nothing to do without one); the process's own
     arithmetic is back when it returns or raises.  Entry points call each other: the blocks nest."""
@@ -376,7 +392,7 @@ class CILTaskLoop:
     ``config`` carries the reference's top-level config keys (work_dir, task_splits, starting_task, ending_task,
     methods, num_epochs_per_task, videos_per_gpu, testing_videos_per_gpu, accumulate_grad_batches, optimizer,
     lr_scheduler, cbf_*, use_cbf, budget_size, storing_methods, budget_type, save_best, kd_modules_names,
-    kd_weight_by_module, adaptive_scale_factors, repr_hook, data_root, train_ann_file, val_ann_file,
+    kd_type, kd_weight_by_module, adaptive_scale_factors, repr_hook, data_root, train_ann_file, val_ann_file,
     cil_ann_file_template, model).  ``clip_loader(video_infos, phase) -> batch_data`` supplies the frames.
 
     ``prefetch``: 0 = the loader is called inline, batch by batch.  n > 0 = every epoch of ``fit`` and every ``predict`` (validation,
@@ -391,12 +407,18 @@ class CILTaskLoop:
     feature extraction, class means, testing.  Every public entry point enters ``kernels.conv_arith(mode)`` and leaves the process's
     arithmetic as it found it; None / absent changes nothing.  Parameters and BatchNorm buffers are fp32 in every mode, so the files of
     a work_dir do not depend on it.  Unknown modes, and 'bf16' with ``norm_eval`` / ``partial_bn``, raise ``ValueError`` here.
+
+    Config key ``kd_type`` (absent = 'mse'): the distillation loss of ``methods='base'`` per hooked module, one of 'mse' (the
+    reference's ``nn.MSELoss``), 'pod_spatial', 'pod_flat', 'pod' (POD-spatial on feature maps, POD-flat on pooled features), or a
+    list with one entry per ``kd_modules_names``.  Unknown values, a list of the wrong length, and a non-default value with another
+    method raise ``ValueError`` here.
     """
 
     def __init__(self, config, clip_loader: Callable[[List[dict], str], Dict], device='cuda', seed: int = 0, log: Callable = print,
                  prefetch: Optional[int] = None):
         self.config = config = config if isinstance(config, AttrDict) else AttrDict(config)
         self.conv_arith = check_loop_conv_arith(config)         # before any file or GPU work
+        self.kd_type = check_loop_kd_type(config)
         self.device = torch.device(device)
         self.clip_loader = clip_loader
         self.prefetch = int(config.get('prefetch_batches', 0) if prefetch is None else prefetch)
@@ -424,6 +446,7 @@ class CILTaskLoop:
         self.optimizer_mode = 'default'
         self.current_best = 0 if config.get('save_best', False) else None
         self.history: List[Dict] = []
+        self.kd_log: List[Dict] = []                   # per epoch with a teacher: {'task', 'phase', 'epoch', 'losses': {module: mean}}
         self._all_bg_files: Dict[str, None] = {}       # keep_all_backgrounds (libs/cil/cil.py:62), an ordered set
 
         # models (libs/cil/cil.py:429-452): current + frozen previous copy, hooks for KD / representation
@@ -606,7 +629,8 @@ class CILTaskLoop:
                                   kd_weight_by_module=list(cfg.kd_weight_by_module) if self.use_kd else (),
                                   adaptive_scale_factors=list(cfg.adaptive_scale_factors) if self.use_kd else (),
                                   kd_exemplar_only=cfg.get('kd_exemplar_only', False),
-                                  previous_task_num_classes=self.num_classes(t - 1))
+                                  previous_task_num_classes=self.num_classes(t - 1),
+                                  kd_type=self.kd_type if self.use_kd else 'mse')
 
     @_in_arith
     def fit(self, records: RawframeRecords, max_epochs: int, validate: bool = False) -> List[float]:
@@ -656,9 +680,13 @@ class CILTaskLoop:
             self.current_model.train()
             batches = epoch_batches(len(records), cfg.videos_per_gpu, True, self._shuffle_gen, self.rank, self.world)
             total, pending = 0.0, 0
+            kd_sums = {n: 0.0 for n in cfg.kd_modules_names} if getattr(self, 'use_kd', False) and self._current_task > 0 else {}
             optimizer.zero_grad(set_to_none=True)
             for bi, batch_data in enumerate(self._load(records, batches)):
                 losses = self._training_step(batch_data)
+                for n in kd_sums:
+                    if torch.is_tensor(losses.get(n)):
+                        kd_sums[n] = kd_sums[n] + losses[n].detach()
                 pending += 1
                 boundary = pending == accum or bi == len(batches) - 1
                 if reducer is not None:
@@ -678,6 +706,10 @@ class CILTaskLoop:
             if scheduler is not None:
                 scheduler.step()
             epoch_losses.append(float(total) / max(len(batches), 1))
+            if kd_sums:        # the epoch's mean of every module's distillation loss, unweighted (one read-back per epoch, as above)
+                entry = {n: float(v) / max(len(batches), 1) for n, v in kd_sums.items()}
+                self.kd_log.append(dict(task=self._current_task, phase=self.training_phase, epoch=epoch, losses=entry))
+                self.log('Task {} epoch {} KD losses (kd_type={}): {}'.format(self._current_task, epoch, self.kd_type, entry))
             if validate:
                 self._validation_epoch()
 

@@ -488,6 +488,27 @@ int bdv_kd_mse_fwd(const void* cur, const void* prev, float* mse, int64_t numel,
 int bdv_kd_mse_bwd(const void* cur, const void* prev, const float* gscale_dev, float gscale_host,
                    void* dcur, int64_t numel, int act_dtype, void* stream);
 
+/* ---- pooled-output distillation (csrc/pod_kd.hip) ---------------------------------------------
+ * UPSTREAM, unpinned: PODNet (Douillard et al., "PODNet: Pooled Outputs Distillation for Small-Tasks Incremental Learning",
+ * ECCV 2020), its pod(collapse_channels='spatial', normalize=True) and embeddings_similarity restated from the paper; the
+ * reference has no such loss.  Each entry point stands in for the nn.MSELoss of libs/cil/cil.py:519-541, per hooked module.
+ * Tensors are NHWC (N, H, W, C) in the activation storage type act_dtype; C % 4 == 0, H <= 64, W <= 64, N <= 65535. */
+/* libs/cil/cil.py:519-541 (site), PODNet POD-spatial: bytes of workspace for bdv_pod_spatial_fwd(N, C, H, W); bdv_pod_flat(N, D)
+ * takes bdv_pod_workspace_bytes(N, D, 1, 1).  0 for a non-positive size. */
+size_t bdv_pod_workspace_bytes(int N, int C, int H, int W);
+/* libs/cil/cil.py:519-541 (site), PODNet POD-spatial: p_n = concat(sum_w cur^2 (H, C), sum_h cur^2 (W, C)), q_n from
+ * prev, loss = mean_n | p_n / max(|p_n|, 1e-12) - q_n / max(|q_n|, 1e-12) |.  Writes loss[0] and the profile gradient
+ * G (N, H+W, C) fp32 = d loss / d p, which is all bdv_pod_spatial_bwd needs besides cur. */
+int bdv_pod_spatial_fwd(const void* cur, const void* prev, float* loss, float* G, int N, int C, int H, int W, void* workspace,
+                        size_t workspace_bytes, int act_dtype, void* stream);
+/* libs/cil/cil.py:519-541 (site), PODNet POD-spatial: dcur[n,h,w,c] = gscale_dev[0] * 2 * cur * (G[n,h,c] + G[n,H+w,c]); prev is not read. */
+int bdv_pod_spatial_bwd(const void* cur, const float* G, const float* gscale_dev, void* dcur, int N, int C, int H, int W,
+                        int act_dtype, void* stream);
+/* libs/cil/cil.py:519-541 (site), PODNet POD-flat, F.cosine_embedding_loss with target 1 on (N, D) rows:
+ * loss = mean_n (1 - cur.prev / sqrt((|cur|^2 + 1e-12)(|prev|^2 + 1e-12))); dcur_unit (N, D) fp32 = d loss / d cur. */
+int bdv_pod_flat(const void* cur, const void* prev, float* loss, float* dcur_unit, int N, int D, void* workspace,
+                 size_t workspace_bytes, int act_dtype, void* stream);
+
 /* ---- representation path: clip representations, NME classifier, class means, herding --------- */
 /* libs/cil/cil.py:501-506 (_extract_repr) + :564-571 (predict_step, extract_repr): feat = the hooked
  * cls_head.avg_pool output flattened to (B*crops*T, D); repr (B*crops, D) = F.normalize(mean over the T segments);

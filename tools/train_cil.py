@@ -1,7 +1,7 @@
 """Run a CIL config file end to end: train every task of the config, or re-test the checkpoints of a finished run.
 
     VIDEO_CIL_ROOT=/data/ucf101 python tools/train_cil.py CONFIG [--test] [--test-nme] [--prefetch N] [--seed S] [--device D]
-        [--conv-arith {bf16x3,f32mfma,bf16x2,f16x2,bf16x1,bf16}]
+        [--conv-arith {bf16x3,f32mfma,bf16x2,f16x2,bf16x1,bf16}] [--kd-type {mse,pod,pod_spatial,pod_flat}]
 
 CONFIG is a config file of the reference (configs/ucf101/..., self-contained Python that reads VIDEO_CIL_ROOT).  The clip loader is
 built from the config's ``data.train`` and its four pipelines (``bdvcil_amd.clip_loader_spec``; a stage the loaders cannot honour is an
@@ -11,6 +11,8 @@ the shuffle and the process-global generators the training step draws from, whic
 ``--conv-arith`` sets the config's ``conv_arith`` key (the conv arithmetic of everything the loop computes; it wins over the config
 file, and without either the default arithmetic runs); the files of the work_dir are fp32 in every mode, so a run trained under one
 mode re-tests under any other.
+``--kd-type`` sets the config's ``kd_type`` key: the feature-distillation loss of ``methods='base'``, the reference's MSE or PODNet's
+pooled-output losses ('pod' = POD-spatial on feature maps, POD-flat on pooled features); it wins over the config file.
 Several GPUs: start one process per GPU with torchrun; the process group is picked up from the environment."""
 import argparse
 import os
@@ -19,6 +21,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+KD_TYPES = ('mse', 'pod', 'pod_spatial', 'pod_flat')                               # bdvcil_amd.KD_TYPES (checked in main)
 CONV_ARITH_MODES = ('bf16x3', 'f32mfma', 'bf16x2', 'f16x2', 'bf16x1', 'bf16')      # bdvcil_amd.CONV_ARITH_MODES (checked in main)
 
 
@@ -33,6 +36,8 @@ def build_parser():
     ap.add_argument('--threads', type=int, default=8, help='host threads of the JPEG entropy stage')
     ap.add_argument('--conv-arith', choices=CONV_ARITH_MODES, default=None,
                     help="conv arithmetic of the run (the config's conv_arith key; default: the config's, else bf16x3)")
+    ap.add_argument('--kd-type', choices=KD_TYPES, default=None,
+                    help="feature-distillation loss of methods='base' (the config's kd_type key; default: the config's, else mse)")
     return ap
 
 
@@ -40,7 +45,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
 
     import bdvcil_amd as bd           # before the first torch.cuda call (GPU_MAX_HW_QUEUES)
-    assert tuple(bd.CONV_ARITH_MODES) == CONV_ARITH_MODES
+    assert tuple(bd.CONV_ARITH_MODES) == CONV_ARITH_MODES and tuple(bd.KD_TYPES) == KD_TYPES
     import torch
     import torch.distributed as dist
     local = int(os.environ.get('LOCAL_RANK', 0))
@@ -57,6 +62,8 @@ def main(argv=None):
     cfg = bd.load_config(args.config)
     if args.conv_arith is not None:
         cfg['conv_arith'] = args.conv_arith
+    if args.kd_type is not None:
+        cfg['kd_type'] = args.kd_type
     rank = dist.get_rank() if dist.is_initialized() else 0
     # each rank loads its own share of an epoch: its loader draws from its own stream
     loader = bd.build_clip_loader(cfg, device=device, seed=None if args.seed is None else args.seed + rank, threads=args.threads)
