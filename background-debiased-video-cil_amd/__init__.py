@@ -13,7 +13,8 @@ Import as ``bdvcil_amd`` (see ``bdvcil_amd.py`` at the repo root).  Layout:
 * ``background``   background extraction: temporal median + JPEG encode of the frames of a video (bg_extraction_tmf); resized crop +
                    NaN-aware median / mean for moving-camera videos (sim_cam_motion_bg_extract)
 * ``augment``      RandAugment for batches of uint8 clips (draws + device tables; pixels in csrc/augment.hip)
-* ``blending``     ``train_cfg.blending``: MixupBlending / CutmixBlending on the clip-blend kernels (csrc/blend.hip)
+* ``blending``     ``train_cfg.blending``: MixupBlending / CutmixBlending on the clip-blend kernels (csrc/blend.hip); foreground merging
+                   (ForegroundMergeBlending, ``foreground_mask``: motion masks + in-place merge, csrc/fg_merge.hip)
 * ``cil_step``     training-step arithmetic of BaseCIL / ICARLModel + a step engine
 * ``ddp``          bucketed gradient all-reduce over RCCL
 * ``representation``  predict_step / NME classifier / class means / herding
@@ -53,7 +54,7 @@ from .resnet_tsm import Nhwc4Frames, ResNetTSM, TemporalShift  # noqa: F401
 from .heads import LSC, AvgConsensus, IncrementalNet, IncrementalTSMHead, TSMHead  # noqa: F401
 from .losses import ACMSmoothCE, CrossEntropyLoss, LSCLoss, SoftTargetCrossEntropy  # noqa: F401
 from .recognizer import CILRecognizer2D, Recognizer2D  # noqa: F401
-from .blending import CutmixBlending, MixupBlending  # noqa: F401
+from .blending import CutmixBlending, ForegroundMergeBlending, MixupBlending, foreground_mask  # noqa: F401
 from .resnet3d import I3DHead, Recognizer3D, ResNet3d  # noqa: F401
 from .hooks import OutputHook, rgetattr  # noqa: F401
 from .functional import KDPodFlatFn, KDPodSpatialFn, kd_pod_flat, kd_pod_spatial  # noqa: F401

@@ -170,6 +170,10 @@ SIGNATURES = {
     'bdv_blend_mix_f32': (c_int, [P, P, c_float, P, c_int, c_int64, P]),
     'bdv_blend_box_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'bdv_blend_box_f32': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    'bdv_fg_motion_q': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P]),
+    'bdv_fg_hist_refine': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
+    'bdv_fg_select': (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
+    'bdv_fg_merge': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'bdv_gradcam_map': (c_int, [P, P, P, c_int, c_int, c_int, P]),
     'bdv_gradcam_minmax': (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     'bdv_gradcam_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
@@ -183,7 +187,7 @@ class HipExtensionError(RuntimeError):
 
 
 HASHED_SOURCES = ('conv_mfma.hip', 'bn.hip', 'pool_frontend.hip', 'head_loss.hip', 'repr.hip', 'augment.hip', 'optim.hip', 'jpeg.hip',
-                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'ragged.hip', 'gradcam.hip', 'blend.hip', 'pod_kd.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'conv_row_run.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
+                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'ragged.hip', 'gradcam.hip', 'blend.hip', 'pod_kd.hip', 'fg_merge.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'conv_row_run.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
 
 
 def source_hash():

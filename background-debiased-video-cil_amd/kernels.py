@@ -1779,3 +1779,156 @@ def blend_box_(x, perm, box, outer: int, H: int, W: int, inner: int = 1, perm_de
     ws = workspace(lib().bdv_blend_box_scratch_bytes(B, outer, inner, r1, c1, r2, c2), x.device, 'blend')
     check(lib().bdv_blend_box_f32(_p(x), _p(dev), B, outer, H, W, inner, r1, c1, r2, c2, _p(ws), ws.numel(), _stream()), 'bdv_blend_box_f32')
     return x
+
+
+# ---- foreground merging (FAME-style; beyond the reference): csrc/fg_merge.hip -------------------------------------------------------
+
+FG_LAYOUTS = {'tchw': 0, 'thwc4': 1, 'cthw': 2}      # BDV_FG_*: (B,T,3,H,W) | NHWC4 frames (B*T,H,W,4) | (B,3,T,H,W)
+
+
+def fg_blur_taps(H: int, W: int) -> torch.Tensor:
+    """The Gaussian of stage 2 as host fp32 taps: ``k = 2 * (int(0.1 * min(H, W)) // 2) + 1`` of them (23 at 224, 1 = the identity under
+    a short side of 20), sigma = k / 3, computed and normalised in fp64."""
+    k = 2 * (int(0.1 * min(int(H), int(W))) // 2) + 1
+    sigma = k / 3
+    j = torch.arange(k, dtype=torch.float64) - (k // 2)
+    w = torch.exp(-(j * j) / (2 * sigma * sigma))
+    return (w / w.sum()).to(torch.float32)
+
+
+def fg_colour_params(bins: int, mean, std):
+    """Stage 4's six floats: ``lo_c = -mean_c / std_c`` (pixel value 0 after normalisation) and ``s_c = bins * std_c / 256`` (bins per
+    normalised unit), formed in fp64 and rounded to fp32.  -> (lo fp32 (3,), scale fp32 (3,)), host tensors."""
+    bins = fg_check_bins(bins)
+    mean = torch.as_tensor(mean, dtype=torch.float64).reshape(-1)
+    std = torch.as_tensor(std, dtype=torch.float64).reshape(-1)
+    if mean.numel() != 3 or std.numel() != 3 or not bool((std > 0).all()):
+        raise ValueError(f'fg_merge: mean and std must be three numbers each, std positive (got {mean.tolist()}, {std.tolist()})')
+    return (-mean / std).to(torch.float32), (bins * std / 256).to(torch.float32)
+
+
+def fg_check_bins(bins) -> int:
+    if isinstance(bins, bool) or int(bins) != bins or not 2 <= int(bins) <= 16:
+        raise ValueError(f'fg_merge: bins must be an integer in 2..16, got {bins!r}')
+    return int(bins)
+
+
+def fg_k_fg(beta, H: int, W: int) -> int:
+    """``max(1, int(beta * H * W))`` for beta in (0, 1]."""
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0 < beta <= 1:
+        raise ValueError(f'fg_merge: beta must be a number in (0, 1], got {beta!r}')
+    return max(1, int(beta * int(H) * int(W)))
+
+
+def _fg_dims(B, T, H, W, layout, who):
+    B, T, H, W = int(B), int(T), int(H), int(W)
+    if layout not in FG_LAYOUTS:
+        raise ValueError(f'{who}: layout {layout!r}, expected one of {sorted(FG_LAYOUTS)}')
+    if B <= 0 or T <= 0 or H <= 0 or W <= 0 or B > 65535 or H * W > 1 << 24 or T * H * W > 1 << 28:
+        raise ValueError(f'{who}: B {B}, T {T}, H {H}, W {W} (B <= 65535, H * W <= 2^24, T * H * W <= 2^28)')
+    return B, T, H, W, FG_LAYOUTS[layout], (4 if layout == 'thwc4' else 3)
+
+
+def _fg_clip(x, B, T, H, W, lanes, who):
+    if not isinstance(x, torch.Tensor) or x.numel() != B * T * H * W * lanes:
+        raise ValueError(f'{who}: x {tuple(getattr(x, "shape", ()))} is not a batch of {B} clips of {T} x {H} x {W} x {lanes} floats')
+    return _chk(x, name=f'{who}: x')
+
+
+def fg_motion_q(x, B, T, H, W, layout='tchw'):
+    """Stages 1-3 (``bdv_fg_motion_q``): -> ``(q uint8, g, d)``, each (B, H, W): the quantised map, the blurred map and the raw motion
+    map of every clip of ``x`` (contiguous fp32 in ``layout``)."""
+    B, T, H, W, code, lanes = _fg_dims(B, T, H, W, layout, 'fg_motion_q')
+    if T < 2:
+        raise ValueError(f'fg_motion_q: T {T}: a motion map needs two frames')
+    _fg_clip(x, B, T, H, W, lanes, 'fg_motion_q')
+    taps = fg_blur_taps(H, W)
+    dev = x.device
+    d, tmp, g = (torch.empty((B, H, W), dtype=torch.float32, device=dev) for _ in range(3))
+    mm = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    part = workspace(B * ((H * W + 255) // 256) * 8, dev, 'fg_minmax')
+    q = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    check(lib().bdv_fg_motion_q(_p(x), B, T, H, W, code, ctypes.c_void_p(taps.data_ptr()), taps.numel(), _p(d), _p(tmp), _p(g), _p(part), _p(mm),
+                                _p(q), _stream()), 'bdv_fg_motion_q')
+    return q, g, d
+
+
+def fg_hist_refine(x, q, B, T, H, W, layout='tchw', bins=8, lo=None, scale=None):
+    """Stages 4-5 (``bdv_fg_hist_refine``): -> ``(s (B, H, W) fp32, F, N)`` with F, N (B, bins^3) int32 tensors holding the uint32 sums of
+    ``q`` and the counts per colour bin.  ``lo`` / ``scale``: host triples of ``fg_colour_params``."""
+    B, T, H, W, code, lanes = _fg_dims(B, T, H, W, layout, 'fg_hist_refine')
+    bins = fg_check_bins(bins)
+    if 255 * T * H * W >= 1 << 32:
+        raise ValueError(f'fg_hist_refine: 255 * T * H * W = 255 * {T} * {H} * {W} does not fit the uint32 histograms')
+    if not isinstance(q, torch.Tensor) or q.numel() != B * H * W:
+        raise ValueError(f'fg_hist_refine: q {tuple(getattr(q, "shape", ()))} is not ({B}, {H}, {W})')
+    _fg_clip(x, B, T, H, W, lanes, 'fg_hist_refine')
+    _chk(q, dtype=torch.uint8, name='fg_hist_refine: q')
+    lo = torch.as_tensor(lo, dtype=torch.float32).reshape(-1).contiguous()
+    scale = torch.as_tensor(scale, dtype=torch.float32).reshape(-1).contiguous()
+    if lo.is_cuda or scale.is_cuda or lo.numel() != 3 or scale.numel() != 3:
+        raise ValueError('fg_hist_refine: lo and scale are host triples (fg_colour_params)')
+    dev = x.device
+    nb = bins ** 3
+    F = torch.empty((B, nb), dtype=torch.int32, device=dev)
+    N = torch.empty((B, nb), dtype=torch.int32, device=dev)
+    s = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    idx = workspace(B * T * ((H * W + 3) // 4 * 4) * 2, dev, 'fg_idx')
+    check(lib().bdv_fg_hist_refine(_p(x), _p(q), B, T, H, W, code, bins, ctypes.c_void_p(lo.data_ptr()), ctypes.c_void_p(scale.data_ptr()),
+                                   _p(idx), _p(F), _p(N), _p(s), _stream()), 'bdv_fg_hist_refine')
+    return s, F, N
+
+
+def fg_select(s, k_fg: int):
+    """Stage 6 (``bdv_fg_select``): ``s`` (B, H, W) or (B, HW) non-negative fp32 -> ``(v (B,), mask uint8 like s, count int32 (B,))``."""
+    if not isinstance(s, torch.Tensor) or s.dim() not in (2, 3) or s.numel() == 0:
+        raise ValueError(f'fg_select: expected a non-empty (B, H, W) or (B, HW) map, got {tuple(getattr(s, "shape", ()))}')
+    B, HW = int(s.shape[0]), s.numel() // int(s.shape[0])
+    k_fg = int(k_fg)
+    if not 1 <= k_fg <= HW or HW > 1 << 24:
+        raise ValueError(f'fg_select: k_fg {k_fg} outside 1..{HW} (H * W <= 2^24)')
+    _chk(s, name='fg_select: s')
+    v = torch.empty((B,), dtype=torch.float32, device=s.device)
+    mask = torch.empty(s.shape, dtype=torch.uint8, device=s.device)
+    count = torch.empty((B,), dtype=torch.int32, device=s.device)
+    check(lib().bdv_fg_select(_p(s), B, HW, k_fg, _p(v), _p(mask), _p(count), _stream()), 'bdv_fg_select')
+    return v, mask, count
+
+
+def fg_merge_slots(perm, apply):
+    """Host side of stage 7: a scratch slot for every clip whose source may itself be merged.  -> (slot int32 (B,) host, nslots)."""
+    perm, apply = perm.tolist(), [bool(a) for a in apply.tolist()]
+    on = [apply[b] and perm[b] != b for b in range(len(perm))]
+    slot, n = [], 0
+    for b in range(len(perm)):
+        if on[b] and on[perm[b]]:
+            slot.append(n)
+            n += 1
+        else:
+            slot.append(-1)
+    return torch.tensor(slot, dtype=torch.int32), n
+
+
+def fg_merge_(x, mask, count, perm, apply, B, T, H, W, layout='tchw'):
+    """Stage 7 (``bdv_fg_merge``), in place: the background (``mask == 0``) of every clip b with ``apply[b]``, ``perm[b] != b`` and
+    ``count[b] > 0`` takes the pixels clip ``perm[b]`` had before the call.  ``perm``: host int64 (B,), ``apply``: host bool (B,).
+    Returns ``x``."""
+    B, T, H, W, code, lanes = _fg_dims(B, T, H, W, layout, 'fg_merge_')
+    if not isinstance(mask, torch.Tensor) or mask.numel() != B * H * W:
+        raise ValueError(f'fg_merge_: mask {tuple(getattr(mask, "shape", ()))} does not fit {B} clips of {H} x {W} pixels')
+    _fg_clip(x, B, T, H, W, lanes, 'fg_merge_')
+    _chk(mask, dtype=torch.uint8, name='fg_merge_: mask')
+    _chk(count, (B,), torch.int32, 'fg_merge_: count')
+    perm_dev = _blend_perm(perm, B, x.device, 'fg_merge_')
+    host_perm = torch.as_tensor(perm, dtype=torch.int64).reshape(-1)
+    apply = torch.as_tensor(apply).reshape(-1)
+    if apply.is_cuda or apply.numel() != B:
+        raise ValueError(f'fg_merge_: apply must be a host vector of {B} flags')
+    apply = apply.to(torch.bool)
+    slot, nslots = fg_merge_slots(host_perm, apply)
+    S = T * H * W * lanes
+    ws = workspace(nslots * S * 4, x.device, 'fg_merge') if nslots else None
+    apply_dev, slot_dev = apply.to(torch.uint8).to(x.device), slot.to(x.device)      # both alive until the launches are queued
+    check(lib().bdv_fg_merge(_p(x), _p(mask), _p(count), _p(perm_dev), _p(apply_dev), _p(slot_dev), nslots,
+                             B, T, H, W, code, _p(ws), 0 if ws is None else ws.numel(), _stream()), 'bdv_fg_merge')
+    return x

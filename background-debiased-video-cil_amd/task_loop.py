@@ -374,6 +374,29 @@ def check_loop_kd_type(config):
     return kd_type if isinstance(kd_type, str) else kinds
 
 
+def check_loop_fg_merge(config):
+    """The ``fg_merge`` key of a loop config (absent or None = off), validated without touching the GPU: a dict with any of ``beta`` in
+    (0, 1], ``prob`` in [0, 1] and ``bins`` in 2..16 (the defaults of ``ForegroundMergeBlending`` otherwise).  Returns the dict of the
+    three values, or None."""
+    spec = config.get('fg_merge')
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError(f'fg_merge must be a dict(beta=, prob=, bins=), got {spec!r}')
+    unknown = sorted(set(spec) - {'beta', 'prob', 'bins'})
+    if unknown:
+        raise ValueError(f'fg_merge: unknown keys {unknown} (known: beta, prob, bins)')
+    out = dict(beta=spec.get('beta', 0.5), prob=spec.get('prob', 0.5), bins=spec.get('bins', 8))
+    for key, ok, rule in (('beta', lambda v: 0 < v <= 1, 'in (0, 1]'), ('prob', lambda v: 0 <= v <= 1, 'in [0, 1]')):
+        v = out[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(v):
+            raise ValueError(f'fg_merge: {key} must be a number {rule}, got {v!r}')
+    b = out['bins']
+    if isinstance(b, bool) or not isinstance(b, int) or not 2 <= b <= 16:
+        raise ValueError(f'fg_merge: bins must be an integer in 2..16, got {b!r}')
+    return out
+
+
 def _in_arith(fn):
     """A public entry point of the loop runs under the loop's ``conv_arith`` (nothing to do without one); the process's own
     arithmetic is back when it returns or raises.  Entry points call each other: the blocks nest."""
@@ -412,6 +435,11 @@ class CILTaskLoop:
     reference's ``nn.MSELoss``), 'pod_spatial', 'pod_flat', 'pod' (POD-spatial on feature maps, POD-flat on pooled features), or a
     list with one entry per ``kd_modules_names``.  Unknown values, a list of the wrong length, and a non-default value with another
     method raise ``ValueError`` here.
+
+    Config key ``fg_merge=dict(beta, prob, bins)`` (absent = off): foreground merging (``blending.ForegroundMergeBlending``, beyond the
+    reference) of ``batch_data['imgs']``, in place, at the top of every training step -- all three ``methods``, CBF fits included, so
+    the KD teacher sees the merged clips too; never in validation, feature extraction or test.  Labels are untouched.  Validated here
+    by ``check_loop_fg_merge``.
     """
 
     def __init__(self, config, clip_loader: Callable[[List[dict], str], Dict], device='cuda', seed: int = 0, log: Callable = print,
@@ -419,6 +447,11 @@ class CILTaskLoop:
         self.config = config = config if isinstance(config, AttrDict) else AttrDict(config)
         self.conv_arith = check_loop_conv_arith(config)         # before any file or GPU work
         self.kd_type = check_loop_kd_type(config)
+        fg = check_loop_fg_merge(config)
+        self.fg_merge = None
+        if fg is not None:
+            from .blending import ForegroundMergeBlending
+            self.fg_merge = ForegroundMergeBlending(**fg)
         self.device = torch.device(device)
         self.clip_loader = clip_loader
         self.prefetch = int(config.get('prefetch_batches', 0) if prefetch is None else prefetch)
@@ -612,6 +645,9 @@ class CILTaskLoop:
     # -- one fit ---------------------------------------------------------------------------------------------------------
     def _training_step(self, batch_data: Dict) -> Dict:
         t = self._current_task
+        fg = getattr(self, 'fg_merge', None)
+        if fg is not None:                   # in place: the teacher of any method reads the merged clips
+            batch_data['imgs'], _ = fg(batch_data['imgs'], batch_data.get('label'))
         if self.method == 'icarl_video_mix':
             loss = icarl_video_mix_training_step(self.current_model, batch_data, self.num_classes(t), self.config.video_mix_prob,
                                                  self.config.video_mix_alpha, current_task=t, prev_model=self.prev_model,

@@ -744,6 +744,41 @@ size_t bdv_blend_box_scratch_bytes(int B, int outer, int inner, int r1, int c1, 
 int bdv_blend_box_f32(float* x, const int64_t* perm, int B, int outer, int H, int W, int inner, int r1, int c1, int r2, int c2,
                       void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- foreground merging (FAME-style): motion masks + in-place merge ---------------------------------------------------------------
+ * BEYOND THE REFERENCE: the reference has no such augmentation.  UPSTREAM, unpinned: FAME (Ding et al., "Motion-aware Contrastive
+ * Video Representation Learning via Foreground-background Merging", CVPR 2022), restated from memory and fixed in DESIGN.md 4.11.
+ * A clip batch is fp32 in one of three layouts: BDV_FG_TCHW (B, T, 3, H, W), BDV_FG_THWC4 the NHWC4 frames (B * T, H, W, 4) whose
+ * fourth lane takes no part in the mask and moves with its pixel, BDV_FG_CTHW (B, 3, T, H, W).  All arithmetic is fp32, sums in the
+ * stated order, no fused multiply-add.  B <= 65535, H * W <= 2^24, T * H * W <= 2^28.  Bases need 4-byte alignment only. */
+#define BDV_FG_TCHW 0
+#define BDV_FG_THWC4 1
+#define BDV_FG_CTHW 2
+/* beyond the reference (FAME stages 1-3): d[b,p] = (sum_{t<T-1} sum_c |x[b,t+1,c,p] - x[b,t,c,p]|) / (T - 1); tmp = d blurred along W,
+ * g = tmp blurred along H with the k taps taps_host (HOST floats, k odd, 1 <= k <= 129, k / 2 < min(H, W); reflect border, edge not
+ * repeated, taps added in ascending order); minmax[b] = {bits of min g[b], bits of max g[b]}; q = (uint8)floor(255 * (g - lo) /
+ * (hi - lo + 1e-8f) + 0.5), 0 everywhere when hi == lo.  d, tmp, g: (B, H*W) fp32; partials: workspace of B * ceil(H*W / 256) * 2
+ * uint32 (the per-workgroup min / max: no atomics); minmax: (B, 2) uint32; q: (B, H*W).  T >= 2. */
+int bdv_fg_motion_q(const float* x, int B, int T, int H, int W, int layout, const float* taps_host, int k, float* d, float* tmp,
+                    float* g, uint32_t* partials, uint32_t* minmax, uint8_t* q, void* stream);
+/* beyond the reference (FAME stages 4-5): bin_c = clamp((int)floor((x_c - lo_host[c]) * scale_host[c]), 0, bins - 1) (a NaN: 0),
+ * i = (bin_0 * bins + bin_1) * bins + bin_2; F[b,i] = sum of q over the (t,p) in bin i, N[b,i] their count, both uint32 by integer
+ * atomics (cleared here); idx (B, T, HWp) uint16 with HWp = H*W rounded up to 4, 8-byte aligned, holds i; s[b,p] = (sum_t
+ * float(F[b,i_t]) / (255.0f * float(N[b,i_t]))) / T.  bins 2..16; refuses 255 * T * H * W >= 2^32. */
+int bdv_fg_hist_refine(const float* x, const uint8_t* q, int B, int T, int H, int W, int layout, int bins, const float lo_host[3],
+                       const float scale_host[3], uint16_t* idx, uint32_t* F, uint32_t* N, float* s, void* stream);
+/* beyond the reference (FAME stage 6): v[b] = the k_fg-th largest value of the non-negative map s[b] (B, HW), exactly (radix select
+ * on the float bits, one workgroup per clip); mask[b,p] = (s >= v[b] and s > 0), so ties at the threshold are all foreground;
+ * count[b] = its size.  1 <= k_fg <= HW. */
+int bdv_fg_select(const float* s, int B, int HW, int k_fg, float* v, uint8_t* mask, int32_t* count, void* stream);
+/* beyond the reference (FAME stage 7), in place: for every b with apply[b] != 0, perm[b] != b and count[b] > 0, every pixel with
+ * mask[b,p] == 0 takes, in every frame and channel, the value it had in clip perm[b] BEFORE the call (gather-then-assign for any
+ * index vector, as bdv_blend_box_f32); all other clips are neither read nor written.  perm: device int64 (B) in [0, B) (checked by
+ * the caller on its host copy); apply: device uint8 (B); slot: device int32 (B), a distinct index in [0, nslots) for every b whose
+ * source may itself be merged (apply[b], perm[b] != b, apply[perm[b]], perm[perm[b]] != perm[b]), else -1; scratch: 16-byte aligned,
+ * nslots samples (T * H * W * 3 or 4 floats each). */
+int bdv_fg_merge(float* x, const uint8_t* mask, const int32_t* count, const int64_t* perm, const uint8_t* apply, const int32_t* slot,
+                 int nslots, int B, int T, int H, int W, int layout, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- optimizer: multi-tensor global-norm clip + SGD(momentum, wd) ---------------------------
  * torch.optim.SGD built at libs/cil/cil.py:467 with the groups of libs/models/cil_heads/tsm.py:273-303
  * and PL gradient_clip_val (cil.py:743).  Tables are device arrays, one entry per tensor. */

@@ -2,6 +2,7 @@
 
     VIDEO_CIL_ROOT=/data/ucf101 python tools/train_cil.py CONFIG [--test] [--test-nme] [--prefetch N] [--seed S] [--device D]
         [--conv-arith {bf16x3,f32mfma,bf16x2,f16x2,bf16x1,bf16}] [--kd-type {mse,pod,pod_spatial,pod_flat}]
+        [--fg-merge-prob P [--fg-merge-beta B]]
 
 CONFIG is a config file of the reference (configs/ucf101/..., self-contained Python that reads VIDEO_CIL_ROOT).  The clip loader is
 built from the config's ``data.train`` and its four pipelines (``bdvcil_amd.clip_loader_spec``; a stage the loaders cannot honour is an
@@ -13,6 +14,9 @@ file, and without either the default arithmetic runs); the files of the work_dir
 mode re-tests under any other.
 ``--kd-type`` sets the config's ``kd_type`` key: the feature-distillation loss of ``methods='base'``, the reference's MSE or PODNet's
 pooled-output losses ('pod' = POD-spatial on feature maps, POD-flat on pooled features); it wins over the config file.
+``--fg-merge-prob P`` sets the config's ``fg_merge`` key: foreground merging of the training batches (a clip keeps its motion
+foreground and takes the rest from another clip of the batch, with probability P; labels untouched), ``--fg-merge-beta B`` the share
+of pixels kept as foreground (default 0.5); both win over the config file, whose other ``fg_merge`` entries stay.
 Several GPUs: start one process per GPU with torchrun; the process group is picked up from the environment."""
 import argparse
 import os
@@ -38,7 +42,26 @@ def build_parser():
                     help="conv arithmetic of the run (the config's conv_arith key; default: the config's, else bf16x3)")
     ap.add_argument('--kd-type', choices=KD_TYPES, default=None,
                     help="feature-distillation loss of methods='base' (the config's kd_type key; default: the config's, else mse)")
+    ap.add_argument('--fg-merge-prob', type=float, default=None,
+                    help="foreground merging of the training batches with this probability per clip (the config's fg_merge key)")
+    ap.add_argument('--fg-merge-beta', type=float, default=None,
+                    help='share of the pixels kept as foreground (with --fg-merge-prob or an fg_merge key of the config; default 0.5)')
     return ap
+
+
+def set_fg_merge(cfg, prob=None, beta=None):
+    """--fg-merge-prob / --fg-merge-beta -> the config's ``fg_merge`` key; entries of the config file that no flag names stay."""
+    if prob is None and beta is None:
+        return cfg
+    if prob is None and not cfg.get('fg_merge'):
+        raise SystemExit('--fg-merge-beta needs --fg-merge-prob (the config has no fg_merge key)')
+    spec = dict(cfg.get('fg_merge') or {})
+    if prob is not None:
+        spec['prob'] = prob
+    if beta is not None:
+        spec['beta'] = beta
+    cfg['fg_merge'] = spec
+    return cfg
 
 
 def main(argv=None):
@@ -64,6 +87,8 @@ def main(argv=None):
         cfg['conv_arith'] = args.conv_arith
     if args.kd_type is not None:
         cfg['kd_type'] = args.kd_type
+    set_fg_merge(cfg, args.fg_merge_prob, args.fg_merge_beta)
+    bd.task_loop.check_loop_fg_merge(cfg)
     rank = dist.get_rank() if dist.is_initialized() else 0
     # each rank loads its own share of an epoch: its loader draws from its own stream
     loader = bd.build_clip_loader(cfg, device=device, seed=None if args.seed is None else args.seed + rank, threads=args.threads)
