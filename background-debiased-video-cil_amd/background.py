@@ -112,7 +112,7 @@ def encode_jpeg(images_u8, quality: int = DEFAULT_QUALITY, device=None, threads:
 def temporal_median(frames_u8, counts: Sequence[int], device=None) -> torch.Tensor:
     """``np.median(frames_v, axis=0).astype(np.uint8)`` for every video v of a ragged batch: ``frames_u8`` ``(sum(counts), H, W, 3)``
     uint8 (tensor or array; the videos' frames back to back), ``counts`` the frames per video -> ``(V, H, W, 3)`` uint8 on the device."""
-    from .kernels import _p, _stream
+    from .kernels import _p, _stream, _video_runs
     counts = [int(c) for c in counts]
     frames = torch.as_tensor(frames_u8)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
@@ -122,12 +122,9 @@ def temporal_median(frames_u8, counts: Sequence[int], device=None) -> torch.Tens
     dev = frames.device if frames.is_cuda else _device(device)
     frames = frames.to(dev).contiguous()
     V, H, W = len(counts), int(frames.shape[1]), int(frames.shape[2])
-    first_h = np.zeros(V, dtype=np.int64)
-    first_h[1:] = np.cumsum(counts[:-1])
-    counts_h = np.asarray(counts, dtype=np.int32)
-    first_d, counts_d = torch.from_numpy(first_h).to(dev), torch.from_numpy(counts_h).to(dev)
+    first_h, counts_h, first_d, counts_d = _video_runs(counts, dev)
     out = torch.empty(V, H, W, 3, dtype=torch.uint8, device=dev)
-    check(lib().bdv_temporal_median_u8(_p(frames), int(frames.shape[0]), _p(first_d), _p(counts_d), first_h.ctypes.data, counts_h.ctypes.data,
+    check(lib().bdv_temporal_median_u8(_p(frames), int(frames.shape[0]), _p(first_d), _p(counts_d), first_h.data_ptr(), counts_h.data_ptr(),
                                        V, H, W, _p(out), _stream()), 'bdv_temporal_median_u8')
     return out
 

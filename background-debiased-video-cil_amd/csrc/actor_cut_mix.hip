@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "loader_pieces.h"
 #include "resize_linear.h"
 
 namespace {
@@ -36,7 +37,7 @@ struct AcmArgs {
   float* out;                      // (B_out, T, 3, Hd, Wd)
   int32_t* counts;                 // (nclips) mask pixels, zeroed by the launcher
   int T, Ha, Wa, Hs, Ws, Hd, Wd;
-  float mean[3], inv_std[3];
+  ClipNorm norm;
 };
 
 // numpy slice semantics img[y0:y1, x0:x1] for 0 <= coordinates <= the frame size (validated on the host): an inverted box is empty
@@ -50,15 +51,7 @@ __device__ __forceinline__ bool in_any_box(const int32_t* box, int b0, int b1, i
 }
 
 __device__ __forceinline__ ResizeBox frame_box(const uint8_t* src, int frame, int Hs, int Ws, int Hd, int Wd) {
-  ResizeBox b;
-  b.bw = Ws;
-  b.bh = Hs;
-  b.pitch = (size_t)Ws * 3;
-  b.base = src + (size_t)frame * Hs * b.pitch;
-  b.mode = (Ws == Wd && Hs == Hd) ? 1 : (Ws == 2 * Wd && Hs == 2 * Hd) ? 2 : 0;   // as resize_linear_u8_kernel
-  b.scale_x = 1.0 / ((double)Wd / Ws);
-  b.scale_y = 1.0 / ((double)Hd / Hs);
-  return b;
+  return resize_box(src + (size_t)frame * Hs * Ws * 3, (size_t)Ws * 3, Ws, Hs, Hd, Wd);
 }
 
 // grid (pixel groups of one frame, nclips*T), 256 threads; four consecutive output pixels per thread
@@ -75,28 +68,24 @@ __global__ __launch_bounds__(256) void actor_cut_mix_kernel(const AcmArgs a) {
     const ResizeBox ra = frame_box(a.actor, actor_row * a.T + t, a.Ha, a.Wa, a.Hd, a.Wd);
     // scene_row < 0 only for a clip without actor boxes (checked on the host): every pixel is then the actor's
     const ResizeBox rs = frame_box(a.scene, (scene_row < 0 ? 0 : scene_row) * a.T + t, a.Hs, a.Ws, a.Hd, a.Wd);
-    const int cnt4 = npix - p0 < 4u ? (int)(npix - p0) : 4;
-    int dy = (int)(p0 / (unsigned)a.Wd), dx = (int)(p0 - (unsigned)dy * (unsigned)a.Wd);
+    ResizeGroup g = resize_group(p0, npix, a.Wd);
+    const int cnt4 = g.cnt;
     float v[3][4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < 4; ++k, g.next(a.Wd)) {
       unsigned px = 0;
       if (k < cnt4) {
-        const bool m = whole || in_any_box(a.abox, ab0, ab1, dx, dy);
+        const bool m = whole || in_any_box(a.abox, ab0, ab1, g.dx, g.dy);
         if (m)
-          px = actor_flip ? resize_pixel<true>(ra, dx, dy) : resize_pixel<false>(ra, dx, dy);
-        else if (in_any_box(a.sbox, sb0, sb1, dx, dy))
+          px = actor_flip ? resize_pixel<true>(ra, g.dx, g.dy) : resize_pixel<false>(ra, g.dx, g.dy);
+        else if (in_any_box(a.sbox, sb0, sb1, g.dx, g.dy))
           px = 0x7F7F7Fu;                                                       // ActorCutOut(fill_color=127)
         else
-          px = scene_flip ? resize_pixel<true>(rs, dx, dy) : resize_pixel<false>(rs, dx, dy);
+          px = scene_flip ? resize_pixel<true>(rs, g.dx, g.dy) : resize_pixel<false>(rs, g.dx, g.dy);
         cnt += m;
       }
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[c][k] = ((float)((px >> (8 * c)) & 255u) - a.mean[c]) * a.inv_std[c];
-      if (++dx == a.Wd) {
-        dx = 0;
-        ++dy;
-      }
+      for (int c = 0; c < 3; ++c) v[c][k] = normalize_u8((uint8_t)(px >> (8 * c)), a.norm.mean[c], a.norm.inv_std[c]);
     }
     float* o = a.out + ((size_t)out_row * a.T + t) * 3 * npix + p0;
     if (cnt4 == 4 && (npix & 3u) == 0u) {
@@ -184,10 +173,7 @@ extern "C" int bdv_actor_cut_mix_u8(const uint8_t* actor, int n_actor, int Ha, i
   a.Ws = n_scene > 0 ? Ws : Wa;
   a.Hd = Hd;
   a.Wd = Wd;
-  for (int c = 0; c < 3; ++c) {
-    a.mean[c] = mean[c];
-    a.inv_std[c] = inv_std[c];
-  }
+  a.norm = clip_norm(mean, inv_std);
   const unsigned groups = ((unsigned)Hd * (unsigned)Wd + 3u) / 4u;
   hipLaunchKernelGGL(actor_cut_mix_kernel, dim3((groups + 255u) / 256u, (unsigned)F), dim3(256), 0, st, a);
   BDV_LAUNCH_CHECK("bdv_actor_cut_mix_u8");

@@ -358,46 +358,21 @@ __global__ __launch_bounds__(256) void resize_linear_u8_kernel(const uint8_t* __
   const unsigned p0 = (blockIdx.x * 256u + threadIdx.x) * 4u;
   if (p0 >= npix) return;
   const unsigned n = blockIdx.y;
-  int x0 = 0, y0 = 0;
-  ResizeBox b;
-  b.bw = Ws;
-  b.bh = Hs;
+  int x0 = 0, y0 = 0, bw = Ws, bh = Hs;
   if (boxes != nullptr) {
     const int32_t* q = boxes + 4 * (n / (unsigned)T);
     x0 = q[0];
     y0 = q[1];
-    b.bw = q[2];
-    b.bh = q[3];
+    bw = q[2];
+    bh = q[3];
   }
-  b.pitch = (size_t)Ws * 3;
-  b.base = src + ((size_t)n * Hs + y0) * b.pitch + (size_t)x0 * 3;
-  b.mode = (b.bw == Wd && b.bh == Hd) ? 1 : (b.bw == 2 * Wd && b.bh == 2 * Hd) ? 2 : 0;
-  b.scale_x = 1.0 / ((double)Wd / b.bw);
-  b.scale_y = 1.0 / ((double)Hd / b.bh);
-  int dy = (int)(p0 / (unsigned)Wd), dx = (int)(p0 - (unsigned)dy * (unsigned)Wd);
+  const size_t pitch = (size_t)Ws * 3;
+  const ResizeBox b = resize_box(src + ((size_t)n * Hs + y0) * pitch + (size_t)x0 * 3, pitch, bw, bh, Hd, Wd);
+  ResizeGroup g = resize_group(p0, npix, Wd);
   unsigned px[4];
-  const int cnt = npix - p0 < 4u ? (int)(npix - p0) : 4;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    px[k] = k < cnt ? resize_pixel(b, dx, dy) : 0u;
-    if (++dx == Wd) {
-      dx = 0;
-      ++dy;
-    }
-  }
-  uint8_t* out = dst + ((size_t)n * npix + p0) * 3;
-  if (cnt == 4 && (npix & 3u) == 0u) {
-    unsigned* o = reinterpret_cast<unsigned*>(out);
-    o[0] = px[0] | (px[1] << 24);
-    o[1] = (px[1] >> 8) | (px[2] << 16);
-    o[2] = (px[2] >> 16) | (px[3] << 8);
-  } else {
-    for (int k = 0; k < cnt; ++k) {
-      out[3 * k] = (uint8_t)px[k];
-      out[3 * k + 1] = (uint8_t)(px[k] >> 8);
-      out[3 * k + 2] = (uint8_t)(px[k] >> 16);
-    }
-  }
+  for (int k = 0; k < 4; ++k, g.next(Wd)) px[k] = k < g.cnt ? resize_pixel(b, g.dx, g.dy) : 0u;
+  resize_store4(dst + ((size_t)n * npix + p0) * 3, px, g.cnt, (npix & 3u) == 0u);
 }
 
 }  // namespace

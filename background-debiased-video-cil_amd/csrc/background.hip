@@ -630,10 +630,7 @@ extern "C" int bdv_temporal_median_u8(const uint8_t* frames, int64_t total_frame
   BDV_REQUIRE(frames && first && counts && first_host && counts_host && out, "bdv_temporal_median_u8: null pointer");
   BDV_REQUIRE(V > 0 && V <= 65535 && H > 0 && W > 0, "bdv_temporal_median_u8: bad batch (V=%d, %d x %d)", V, H, W);
   BDV_REQUIRE((long long)H * W * 3 < (1ll << 31) - 1024, "bdv_temporal_median_u8: frame too large");
-  for (int v = 0; v < V; ++v)
-    BDV_REQUIRE(counts_host[v] >= 1 && counts_host[v] <= 65535 && first_host[v] >= 0 && first_host[v] + counts_host[v] <= total_frames,
-                "bdv_temporal_median_u8: video %d: frames %lld..%lld of %lld (1..65535 frames per video)", v, (long long)first_host[v],
-                (long long)first_host[v] + counts_host[v] - 1, (long long)total_frames);
+  if (int rc = bdv_check_video_runs("bdv_temporal_median_u8", first_host, counts_host, V, total_frames)) return rc;
   const unsigned P = (unsigned)H * (unsigned)W * 3u;
   const bool aligned = (P & 3u) == 0 && (((uintptr_t)frames) & 3) == 0 && (((uintptr_t)out) & 3) == 0;
   const unsigned groups = (P + 3u) / 4u;
@@ -660,10 +657,7 @@ extern "C" int bdv_temporal_masked_median_u8(const uint8_t* frames, int64_t tota
   BDV_REQUIRE(num_boxes >= 0 && num_boxes < (1ll << 31) && (num_boxes == 0 || (boxes && boxes_host)), "%s: bad box table (%lld rows)", who,
               (long long)num_boxes);
   BDV_REQUIRE(num_boxes == 0 || bdv_aligned16(boxes), "%s: boxes must be 16-byte aligned", who);
-  for (int v = 0; v < V; ++v)
-    BDV_REQUIRE(counts_host[v] >= 1 && counts_host[v] <= 65535 && first_host[v] >= 0 && first_host[v] + counts_host[v] <= total_frames,
-                "%s: video %d: frames %lld..%lld of %lld (1..65535 frames per video)", who, v, (long long)first_host[v],
-                (long long)first_host[v] + counts_host[v] - 1, (long long)total_frames);
+  if (int rc = bdv_check_video_runs(who, first_host, counts_host, V, total_frames)) return rc;
   BDV_REQUIRE(box_first_host[0] >= 0 && box_first_host[total_frames] <= num_boxes, "%s: box_first spans rows %d..%d of %lld", who,
               box_first_host[0], box_first_host[total_frames], (long long)num_boxes);
   for (int64_t f = 0; f < total_frames; ++f)

@@ -11,34 +11,15 @@
 // sample, a scratch row): ld4_any reads it as one 16-byte, two 8-byte or four 4-byte loads, whichever its address allows.  That
 // choice is the same for every unit of a run, so a wave does not diverge on it.
 #include "common.h"
+#include "loader_pieces.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int64_t kMaxBlocks = 1 << 20;      // as the elementwise passes of bn.hip: one unit per thread up to 2^20 blocks, a stride beyond
-
-__device__ __forceinline__ int phase4(const float* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3); }
-
-__device__ __forceinline__ float4 ld4_any(const float* p) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  if ((a & 15) == 0) return *reinterpret_cast<const float4*>(p);
-  if ((a & 7) == 0) {
-    const float2 lo = *reinterpret_cast<const float2*>(p), hi = *reinterpret_cast<const float2*>(p + 2);
-    return make_float4(lo.x, lo.y, hi.x, hi.y);
-  }
-  return make_float4(p[0], p[1], p[2], p[3]);
-}
 
 __device__ __forceinline__ float mix1(float lam, float om, float a, float b) {
   const float u = lam * a, v = om * b;       // no contraction in this file
   return u + v;
-}
-
-// perm entries are validated by the caller before the upload; an entry outside [0, B) is treated as b itself here, so that no
-// address outside the batch is ever formed
-__device__ __forceinline__ int64_t source_of(const int64_t* __restrict__ perm, int b, int B) {
-  const int64_t p = perm[b];
-  return (p < 0 || p >= B) ? (int64_t)b : p;
 }
 
 __global__ __launch_bounds__(kThreads) void blend_mix_kernel(const float* __restrict__ x, const int64_t* __restrict__ perm, float lam,
@@ -113,12 +94,8 @@ __global__ __launch_bounds__(kThreads) void blend_box_kernel(float* x, const int
 }
 
 dim3 blend_grid(int64_t units_per_sample, int B) {
-  const int64_t gy = B < 65535 ? B : 65535;
-  int64_t gx = (units_per_sample + kThreads - 1) / kThreads;
-  const int64_t cap = kMaxBlocks / gy > 0 ? kMaxBlocks / gy : 1;
-  if (gx > cap) gx = cap;
-  if (gx < 1) gx = 1;
-  return dim3((unsigned)gx, (unsigned)gy);
+  const int gy = B < 65535 ? B : 65535;
+  return dim3((unsigned)bdv_ew_grid(units_per_sample, gy), (unsigned)gy);      // kThreads is the helper's 256
 }
 
 inline int64_t box_units(int64_t L) { return (L + 6) / 4; }

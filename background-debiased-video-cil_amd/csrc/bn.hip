@@ -785,18 +785,6 @@ __global__ __launch_bounds__(256) void add_kernel(const void* __restrict__ a, co
   }
 }
 
-int ew_grid(int64_t n4) {
-  int64_t b = (n4 + 255) / 256;
-  // Blocks per launch of the grid-stride passes.  A cap of 4096 blocks (16 MB between a thread's successive accesses) cost the
-  // passes over the large tensors a quarter of their bandwidth: the 822 MB layer-1 apply pass with a residual 548 us (4.5 TB/s)
-  // capped at 4096, 454 us at 65536, 416 us (5.9 TB/s) with one unit per thread; all apply passes of a step 6.00 -> 5.05 ms,
-  // backward 11.93 -> 11.21 ms (tools/bench_bn.py), 589.4 -> 601.9 clips/s in the step (two alternating pairs, one box).
-  // (round 2's BDVCIL_EW_BLOCKS switch is gone: the A/B is recorded in profiles/r02_ab_streams.txt)
-  if (b > (1 << 20)) b = 1 << 20;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 // ---- finalize launches ------------------------------------------------------------------------------------------------
 // Blocks per channel group of the two finalize kernels.  One block streams rows * 32 bytes of 16-byte pieces through one CU; S
 // blocks spread the same lanes over S CUs and pay a ticket and the last arriver's serial read of 1 KB (slab_colsum2_split):
@@ -855,7 +843,7 @@ void launch_bn_bwd_finalize(const float* q1, const float* q2, int rows, int64_t 
 
 // ---- what the entry points share ------------------------------------------------------------------------------------------
 // grid of an elementwise pass over n4 groups of 4 channels: one 16-byte unit per thread (ActU: fp32 BDV_F32_UNITS groups, bf16 2)
-dim3 act_grid(int64_t n4, int act_dtype) { return dim3(ew_grid(act_dtype == BDV_ACT_BF16 ? n4 / 2 : n4 / BDV_F32_UNITS)); }
+dim3 act_grid(int64_t n4, int act_dtype) { return dim3(bdv_ew_grid(act_dtype == BDV_ACT_BF16 ? n4 / 2 : n4 / BDV_F32_UNITS)); }
 
 // The workspace of bdv_bn_workspace_bytes: two partial slabs, then the 3*C apply coefficients
 struct BnWs {
@@ -1257,7 +1245,7 @@ extern "C" int bdv_relu_bwd(const void* dout, const uint32_t* relu_mask, const v
   BDV_REQUIRE_ACT(act_dtype, "bdv_relu_bwd");
   BDV_REQUIRE(bdv_aligned16(dout) && bdv_aligned16(g) && (!add || bdv_aligned16(add)), "bdv_relu_bwd: alignment");
   const int64_t n4 = numel / 4;
-  BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((relu_bwd_kernel<ES>), dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, dout,
+  BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((relu_bwd_kernel<ES>), dim3(bdv_ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, dout,
                      relu_mask, add, g, n4));
   BDV_LAUNCH_CHECK("bdv_relu_bwd");
   return BDV_OK;
@@ -1268,7 +1256,7 @@ extern "C" int bdv_add(const void* a, const void* b, void* out, int64_t numel, i
   BDV_REQUIRE_ACT(act_dtype, "bdv_add");
   BDV_REQUIRE(bdv_aligned16(a) && bdv_aligned16(b) && bdv_aligned16(out), "bdv_add: alignment");
   const int64_t n4 = numel / 4;
-  BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((add_kernel<ES>), dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, a, b, out, n4));
+  BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((add_kernel<ES>), dim3(bdv_ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, a, b, out, n4));
   BDV_LAUNCH_CHECK("bdv_add");
   return BDV_OK;
 }

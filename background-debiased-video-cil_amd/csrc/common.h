@@ -29,6 +29,31 @@ void bdv_set_error(const char* fmt, ...);
 
 static inline bool bdv_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+// Host only.  Blocks of 256 threads for a grid-stride pass over n units: one unit per thread up to 2^20 blocks, a stride beyond, at
+// least one block.  rows (>= 1): the grid's other dimension, when there is one -- the cap then holds for the whole grid.
+// A cap of 4096 blocks (16 MB between a thread's successive accesses) cost the passes over the large tensors a quarter of their
+// bandwidth: the 822 MB layer-1 BatchNorm apply pass with a residual 548 us (4.5 TB/s) capped at 4096, 454 us at 65536, 416 us
+// (5.9 TB/s) with one unit per thread; all apply passes of a step 6.00 -> 5.05 ms, backward 11.93 -> 11.21 ms (tools/bench_bn.py),
+// 589.4 -> 601.9 clips/s in the step (two alternating pairs, one box).
+// (round 2's BDVCIL_EW_BLOCKS switch is gone: the A/B is recorded in profiles/r02_ab_streams.txt)
+static inline int bdv_ew_grid(int64_t n, int64_t rows = 1) {
+  const int64_t cap = (1 << 20) / rows;
+  int64_t b = (n + 255) / 256;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+// Host only.  The per-video frame runs of a ragged batch, (first, counts) of V videos inside total_frames frames, as the temporal
+// reductions take them: an out-of-range run would read outside the tensor.  who: the entry point, for the message.
+static inline int bdv_check_video_runs(const char* who, const int64_t* first_host, const int32_t* counts_host, int V, int64_t total_frames) {
+  for (int v = 0; v < V; ++v)
+    BDV_REQUIRE(counts_host[v] >= 1 && counts_host[v] <= 65535 && first_host[v] >= 0 && first_host[v] + counts_host[v] <= total_frames,
+                "%s: video %d: frames %lld..%lld of %lld (1..65535 frames per video)", who, v, (long long)first_host[v],
+                (long long)first_host[v] + counts_host[v] - 1, (long long)total_frames);
+  return BDV_OK;
+}
+
 // wave-level and block-level sum (wave = 64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

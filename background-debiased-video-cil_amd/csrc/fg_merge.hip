@@ -18,6 +18,7 @@
 // planes at every 4-byte phase), four pixels 256 apart in NHWC4 (one 16-byte load each, consecutive lanes on consecutive pixels).
 // The merge lays 16-byte units on the grid of the DESTINATION address, as blend.hip does, so every wide store is aligned.
 #include "common.h"
+#include "loader_pieces.h"
 
 namespace {
 
@@ -40,24 +41,6 @@ struct Taps {
 struct Colour {
   float lo[3], s[3];
 };
-
-__device__ __forceinline__ int phase4(const float* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3); }
-
-__device__ __forceinline__ float4 ld4_any(const float* p) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  if ((a & 15) == 0) return *reinterpret_cast<const float4*>(p);
-  if ((a & 7) == 0) {
-    const float2 lo = *reinterpret_cast<const float2*>(p), hi = *reinterpret_cast<const float2*>(p + 2);
-    return make_float4(lo.x, lo.y, hi.x, hi.y);
-  }
-  return make_float4(p[0], p[1], p[2], p[3]);
-}
-
-// as blend.hip: an entry outside [0, B) is treated as b itself, so that no address outside the batch is ever formed
-__device__ __forceinline__ int64_t source_of(const int64_t* __restrict__ perm, int b, int B) {
-  const int64_t p = perm[b];
-  return (p < 0 || p >= B) ? (int64_t)b : p;
-}
 
 // pixel j (0..3) of this thread inside its workgroup's run of kBlockPix pixels
 template <int INNER>

@@ -1,6 +1,7 @@
 // HBM-bound helpers around the conv stack: layout change at the boundary, max/avg pooling, and
 // the fused background-mix + normalize front-end (uint8 in, NHWC4 fp32 out).
 #include "common.h"
+#include "loader_pieces.h"
 
 namespace {
 
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(256) void bgmix_normalize_kernel(const uint8_t* __r
       float v[3];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        float xn = ((float)q[c] - np.mean[c]) * np.inv_std[c];
+        float xn = normalize_u8(q[c], np.mean[c], np.inv_std[c]);
         if (do_mix) xn = xn * one_m_alpha + bgn[c] * np.alpha;
         v[c] = xn;
       }
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(256) void crop_normalize_kernel(const uint8_t* __re
       const uint8_t* q = frames + ((((int64_t)b * T + t) * H + sy) * W + sx) * 3;
       float v[3];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = ((float)q[c] - np.mean[c]) * np.inv_std[c];
+      for (int c = 0; c < 3; ++c) v[c] = normalize_u8(q[c], np.mean[c], np.inv_std[c]);
       const int64_t f = ((int64_t)b * ct.n + k) * T + t;
       if (out_nhwc4 != nullptr) out_nhwc4[f * chw + p] = make_float4(v[0], v[1], v[2], 0.f);
       if (out_nchw != nullptr) {
@@ -256,13 +257,6 @@ __global__ __launch_bounds__(256) void crop_normalize_kernel(const uint8_t* __re
       }
     }
   }
-}
-
-int ew_grid(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > (1 << 20)) b = 1 << 20;   // (one unit per thread: see ew_grid in bn.hip)
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 }  // namespace
@@ -330,8 +324,7 @@ template <int ES>
 inline void pool_t2_units(int64_t frames_out, int64_t frame_elems, int64_t* frame_u, int64_t* n_u, int* blocks) {
   *frame_u = frame_elems / (4 * ActU<ES>::value);
   *n_u = frames_out * *frame_u;
-  const int64_t b = (*n_u + 255) / 256;
-  *blocks = (int)(b > (1 << 20) ? (1 << 20) : b);
+  *blocks = bdv_ew_grid(*n_u);
 }
 }  // namespace
 
@@ -419,7 +412,7 @@ extern "C" int bdv_bg_resize_crop_u8(const uint8_t* src, int B, int Hs, int Ws, 
   BDV_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Hr > 0 && Wr > 0 && crop_h > 0 && crop_w > 0 && crop_h <= Hr && crop_w <= Wr,
               "bdv_bg_resize_crop_u8: bad shape (%dx%d -> %dx%d, crop %dx%d)", Hs, Ws, Hr, Wr, crop_h, crop_w);
   const int64_t total = (int64_t)B * crop_h * crop_w;
-  hipLaunchKernelGGL(bg_resize_crop_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, src, top, left, out, B, Hs, Ws,
+  hipLaunchKernelGGL(bg_resize_crop_kernel, dim3(bdv_ew_grid(total)), dim3(256), 0, (hipStream_t)stream, src, top, left, out, B, Hs, Ws,
                      Hr, Wr, crop_h, crop_w);
   BDV_LAUNCH_CHECK("bdv_bg_resize_crop_u8");
   return BDV_OK;
@@ -429,7 +422,7 @@ extern "C" int bdv_nchw3_to_nhwc4(const float* x, float* out, int N, int H, int 
   BDV_REQUIRE(x && out && N > 0 && H > 0 && W > 0, "bdv_nchw3_to_nhwc4: bad argument");
   BDV_REQUIRE(bdv_aligned16(out), "bdv_nchw3_to_nhwc4: alignment");
   const int64_t npix = (int64_t)N * H * W;
-  hipLaunchKernelGGL(nchw3_to_nhwc4_kernel, dim3(ew_grid(npix)), dim3(256), 0, (hipStream_t)stream, x, (float4*)out, npix, H * W);
+  hipLaunchKernelGGL(nchw3_to_nhwc4_kernel, dim3(bdv_ew_grid(npix)), dim3(256), 0, (hipStream_t)stream, x, (float4*)out, npix, H * W);
   BDV_LAUNCH_CHECK("bdv_nchw3_to_nhwc4");
   return BDV_OK;
 }
@@ -482,7 +475,7 @@ extern "C" int bdv_avgpool_fwd(const void* x, float* out, int N, int HW, int C, 
   BDV_REQUIRE(x && out && N > 0 && HW > 0 && C > 0 && C % 4 == 0, "bdv_avgpool_fwd: bad argument");
   BDV_REQUIRE(bdv_aligned16(x) && bdv_aligned16(out), "bdv_avgpool_fwd: alignment");
   const int64_t total = (int64_t)N * (C / 4);
-  BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((avgpool_fwd_kernel<ES>), dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, (float4*)out, N,
+  BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((avgpool_fwd_kernel<ES>), dim3(bdv_ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, (float4*)out, N,
                      HW, C / 4));
   BDV_LAUNCH_CHECK("bdv_avgpool_fwd");
   return BDV_OK;
@@ -493,7 +486,7 @@ extern "C" int bdv_avgpool_bwd(const float* dout, void* dx, int N, int HW, int C
   BDV_REQUIRE(dout && dx && N > 0 && HW > 0 && C > 0 && C % 4 == 0, "bdv_avgpool_bwd: bad argument");
   BDV_REQUIRE(bdv_aligned16(dout) && bdv_aligned16(dx), "bdv_avgpool_bwd: alignment");
   const int64_t total = (int64_t)N * HW * (C / 4);
-  BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((avgpool_bwd_kernel<ES>), dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, (const float4*)dout, dx,
+  BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((avgpool_bwd_kernel<ES>), dim3(bdv_ew_grid(total)), dim3(256), 0, (hipStream_t)stream, (const float4*)dout, dx,
                      N, HW, C / 4));
   BDV_LAUNCH_CHECK("bdv_avgpool_bwd");
   return BDV_OK;
@@ -517,7 +510,7 @@ extern "C" int bdv_crop_normalize_u8(const uint8_t* frames, const int32_t* crops
     BDV_REQUIRE(ct.x[k] >= 0 && ct.y[k] >= 0 && ct.x[k] + crop_w <= W && ct.y[k] + crop_h <= H,
                 "bdv_crop_normalize_u8: crop %d at (%d, %d) leaves the %dx%d frame", k, ct.x[k], ct.y[k], H, W);
   }
-  NormParams np;
+  NormParams np;      // the kernel's argument layout is bgmix_normalize_kernel's: std and alpha are not read
   for (int c = 0; c < 3; ++c) {
     np.mean[c] = mean[c];
     np.std[c] = 0.f;
@@ -525,7 +518,7 @@ extern "C" int bdv_crop_normalize_u8(const uint8_t* frames, const int32_t* crops
   }
   np.alpha = 0.f;
   const int64_t total = (int64_t)B * ncrops * crop_h * crop_w;
-  hipLaunchKernelGGL(crop_normalize_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, frames, ct, np,
+  hipLaunchKernelGGL(crop_normalize_kernel, dim3(bdv_ew_grid(total)), dim3(256), 0, (hipStream_t)stream, frames, ct, np,
                      (float4*)out_nhwc4, out_nchw, B, T, H, W, crop_h, crop_w);
   BDV_LAUNCH_CHECK("bdv_crop_normalize_u8");
   return BDV_OK;
@@ -548,10 +541,10 @@ extern "C" int bdv_bgmix_normalize_u8(const uint8_t* frames, const void* bg, int
   np.alpha = alpha;
   const int64_t total = (int64_t)B * H * W;
   if (bg_f32)
-    hipLaunchKernelGGL((bgmix_normalize_kernel<true>), dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, frames, bg, mix, np,
+    hipLaunchKernelGGL((bgmix_normalize_kernel<true>), dim3(bdv_ew_grid(total)), dim3(256), 0, (hipStream_t)stream, frames, bg, mix, np,
                        (float4*)out_nhwc4, out_nchw, B, T, H * W);
   else
-    hipLaunchKernelGGL((bgmix_normalize_kernel<false>), dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, frames, bg, mix, np,
+    hipLaunchKernelGGL((bgmix_normalize_kernel<false>), dim3(bdv_ew_grid(total)), dim3(256), 0, (hipStream_t)stream, frames, bg, mix, np,
                        (float4*)out_nhwc4, out_nchw, B, T, H * W);
   BDV_LAUNCH_CHECK("bdv_bgmix_normalize_u8");
   return BDV_OK;

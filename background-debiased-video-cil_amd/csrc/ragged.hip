@@ -13,6 +13,7 @@
 
 #include "bdvcil_hip.h"
 #include "common.h"
+#include "loader_pieces.h"
 #include "resize_linear.h"
 
 namespace {
@@ -31,49 +32,21 @@ __global__ __launch_bounds__(256) void resize_linear_ragged_u8_kernel(const uint
   const unsigned npix = (unsigned)Hd * (unsigned)Wd;
   const unsigned p0 = (blockIdx.x * 256u + threadIdx.x) * 4u;
   if (p0 >= npix) return;
-  ResizeBox b;
-  b.bw = (int)q[RG_BW];
-  b.bh = (int)q[RG_BH];
-  b.pitch = (size_t)Ws * 3;
-  b.base = src + q[RG_SRC] + ((size_t)t * Hs + (size_t)q[RG_Y0]) * b.pitch + (size_t)q[RG_X0] * 3;
-  b.mode = (b.bw == Wd && b.bh == Hd) ? 1 : (b.bw == 2 * Wd && b.bh == 2 * Hd) ? 2 : 0;
-  b.scale_x = 1.0 / ((double)Wd / b.bw);
-  b.scale_y = 1.0 / ((double)Hd / b.bh);
-  int dy = (int)(p0 / (unsigned)Wd), dx = (int)(p0 - (unsigned)dy * (unsigned)Wd);
+  const size_t pitch = (size_t)Ws * 3;
+  const ResizeBox b = resize_box(src + q[RG_SRC] + ((size_t)t * Hs + (size_t)q[RG_Y0]) * pitch + (size_t)q[RG_X0] * 3, pitch, (int)q[RG_BW],
+                                 (int)q[RG_BH], Hd, Wd);
+  ResizeGroup g = resize_group(p0, npix, Wd);
   unsigned px[4];
-  const int cnt = npix - p0 < 4u ? (int)(npix - p0) : 4;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    px[k] = k < cnt ? resize_pixel(b, dx, dy) : 0u;
-    if (++dx == Wd) {
-      dx = 0;
-      ++dy;
-    }
-  }
+  for (int k = 0; k < 4; ++k, g.next(Wd)) px[k] = k < g.cnt ? resize_pixel(b, g.dx, g.dy) : 0u;
   // a clip starts 16-byte aligned; with npix a multiple of 4 every frame of it is a whole number of dwords
-  uint8_t* out = dst + q[RG_DST] + ((size_t)t * npix + p0) * 3;
-  if (cnt == 4 && (npix & 3u) == 0u) {
-    unsigned* o = reinterpret_cast<unsigned*>(out);
-    o[0] = px[0] | (px[1] << 24);
-    o[1] = (px[1] >> 8) | (px[2] << 16);
-    o[2] = (px[2] >> 16) | (px[3] << 8);
-  } else {
-    for (int k = 0; k < cnt; ++k) {
-      out[3 * k] = (uint8_t)px[k];
-      out[3 * k + 1] = (uint8_t)(px[k] >> 8);
-      out[3 * k + 2] = (uint8_t)(px[k] >> 16);
-    }
-  }
+  resize_store4(dst + q[RG_DST] + ((size_t)t * npix + p0) * 3, px, g.cnt, (npix & 3u) == 0u);
 }
-
-struct RaggedNorm {
-  float mean[3], inv_std[3];
-};
 
 // crop_normalize_kernel (pool_frontend.hip) with the clip's (byte offset, H, W) and its crop table read from memory: one thread =
 // one output pixel of one (b, crop), looping over T
 __global__ __launch_bounds__(256) void crop_normalize_ragged_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ clips,
-                                                                     const int32_t* __restrict__ crops, int ncrops, RaggedNorm np,
+                                                                     const int32_t* __restrict__ crops, int ncrops, ClipNorm np,
                                                                      float4* __restrict__ out_nhwc4, float* __restrict__ out_nchw,
                                                                      int B, int T, int ch, int cw) {
 #pragma clang fp contract(off)
@@ -93,7 +66,7 @@ __global__ __launch_bounds__(256) void crop_normalize_ragged_kernel(const uint8_
       const uint8_t* q = src + d[0] + (((int64_t)t * H + sy) * W + sx) * 3;
       float v[3];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = ((float)q[c] - np.mean[c]) * np.inv_std[c];
+      for (int c = 0; c < 3; ++c) v[c] = normalize_u8(q[c], np.mean[c], np.inv_std[c]);
       const int64_t f = ((int64_t)b * ncrops + k) * T + t;
       if (out_nhwc4 != nullptr) out_nhwc4[f * chw + p] = make_float4(v[0], v[1], v[2], 0.f);
       if (out_nchw != nullptr) {
@@ -181,15 +154,8 @@ extern "C" int bdv_crop_normalize_ragged_u8(const uint8_t* src, int64_t src_byte
                   "%s: clip %d: crop %d at (%d, %d) leaves the %lldx%lld frame", me, b, k, c[0], c[1], (long long)d[1], (long long)d[2]);
     }
   }
-  RaggedNorm np;
-  for (int c = 0; c < 3; ++c) {
-    np.mean[c] = mean[c];
-    np.inv_std[c] = inv_std[c];
-  }
-  int64_t blocks = ((int64_t)B * ncrops * crop_h * crop_w + 255) / 256;   // one output pixel per thread, grid-stride beyond 2^20 blocks
-  blocks = std::min<int64_t>(std::max<int64_t>(blocks, 1), 1 << 20);
-  hipLaunchKernelGGL(crop_normalize_ragged_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, clips, crops, ncrops, np,
-                     (float4*)out_nhwc4, out_nchw, B, T, crop_h, crop_w);
+  hipLaunchKernelGGL(crop_normalize_ragged_kernel, dim3(bdv_ew_grid((int64_t)B * ncrops * crop_h * crop_w)), dim3(256), 0, (hipStream_t)stream,
+                     src, clips, crops, ncrops, clip_norm(mean, inv_std), (float4*)out_nhwc4, out_nchw, B, T, crop_h, crop_w);
   BDV_LAUNCH_CHECK("bdv_crop_normalize_ragged_u8");
   return BDV_OK;
 }

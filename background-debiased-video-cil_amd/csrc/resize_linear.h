@@ -1,5 +1,6 @@
-// OpenCV's INTER_LINEAR on 8-bit images, one output pixel at a time: shared by bdv_resize_linear_u8 (augment.hip) and the
-// ActorCutMix composite (actor_cut_mix.hip).  UPSTREAM mmaction2 Resize -> mmcv.imresize(interpolation='bilinear') ->
+// OpenCV's INTER_LINEAR on 8-bit images: the box setup, one output pixel, and the walk over and store of a thread's four pixels,
+// shared by bdv_resize_linear_u8 (augment.hip), bdv_resize_linear_ragged_u8 (ragged.hip) and the ActorCutMix composite
+// (actor_cut_mix.hip).  UPSTREAM mmaction2 Resize -> mmcv.imresize(interpolation='bilinear') ->
 // cv2.resize(..., INTER_LINEAR); the arithmetic restates OpenCV's published fixed-point algorithm (imgproc/resize.cpp) --
 // PARITY UNPINNED, see oracle/resize_oracle.py.  Every file that includes this header is built with -ffp-contract=off: the
 // float / double operations below must not be contracted.
@@ -93,6 +94,57 @@ __device__ __forceinline__ unsigned resize_pixel(const ResizeBox& b, int dx, int
     out |= (unsigned)(v & 255) << (8 * c);
   }
   return out;
+}
+
+// The path cv::resize takes for a bw x bh box (first pixel at base, rows `pitch` bytes apart) resized to Wd x Hd: a copy for the same
+// size, the 2x2 mean for an exact 2x shrink, else the fixed-point resample with cv::resize's scales 1 / (dsize / ssize) in double
+__device__ __forceinline__ ResizeBox resize_box(const uint8_t* base, size_t pitch, int bw, int bh, int Hd, int Wd) {
+  ResizeBox b;
+  b.base = base;
+  b.pitch = pitch;
+  b.bw = bw;
+  b.bh = bh;
+  b.mode = (bw == Wd && bh == Hd) ? 1 : (bw == 2 * Wd && bh == 2 * Hd) ? 2 : 0;
+  b.scale_x = 1.0 / ((double)Wd / bw);
+  b.scale_y = 1.0 / ((double)Hd / bh);
+  return b;
+}
+
+// A thread's group of four consecutive output pixels from pixel p0 of a frame of npix pixels, Wd wide: (dx, dy) of the current pixel
+// and cnt, the number of pixels that exist (the last group of a frame may be short).  One integer division per group, none per pixel.
+struct ResizeGroup {
+  int dx, dy, cnt;
+  __device__ __forceinline__ void next(int Wd) {
+    if (++dx == Wd) {
+      dx = 0;
+      ++dy;
+    }
+  }
+};
+
+__device__ __forceinline__ ResizeGroup resize_group(unsigned p0, unsigned npix, int Wd) {
+  ResizeGroup g;
+  g.dy = (int)(p0 / (unsigned)Wd);
+  g.dx = (int)(p0 - (unsigned)g.dy * (unsigned)Wd);
+  g.cnt = npix - p0 < 4u ? (int)(npix - p0) : 4;
+  return g;
+}
+
+// cnt packed pixels to out: three aligned dwords for a whole group when `dwords` (out is 4-byte aligned: the frame starts aligned and
+// is a whole number of dwords), else byte by byte
+__device__ __forceinline__ void resize_store4(uint8_t* out, const unsigned (&px)[4], int cnt, bool dwords) {
+  if (cnt == 4 && dwords) {
+    unsigned* o = reinterpret_cast<unsigned*>(out);
+    o[0] = px[0] | (px[1] << 24);
+    o[1] = (px[1] >> 8) | (px[2] << 16);
+    o[2] = (px[2] >> 16) | (px[3] << 8);
+  } else {
+    for (int k = 0; k < cnt; ++k) {
+      out[3 * k] = (uint8_t)px[k];
+      out[3 * k + 1] = (uint8_t)(px[k] >> 8);
+      out[3 * k + 2] = (uint8_t)(px[k] >> 16);
+    }
+  }
 }
 
 }  // namespace

@@ -276,12 +276,11 @@ extern "C" int bdv_resized_crop_f32(const uint8_t* frames, int F, int H, int W, 
   }
   CropGeom g{H, W, out_h, out_w};
   const long long total = (long long)F * out_h * out_w;
-  long long blocks = (total + 255) / 256;
-  if (blocks > (1 << 20)) blocks = 1 << 20;
+  const unsigned blocks = (unsigned)bdv_ew_grid(total);
   if (antialias)
-    hipLaunchKernelGGL(resized_crop_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, frames, boxes, out, g, total);
+    hipLaunchKernelGGL(resized_crop_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, frames, boxes, out, g, total);
   else
-    hipLaunchKernelGGL(resized_crop_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, frames, boxes, out, g, total);
+    hipLaunchKernelGGL(resized_crop_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, frames, boxes, out, g, total);
   BDV_LAUNCH_CHECK("bdv_resized_crop_f32");
   return BDV_OK;
 }
@@ -292,10 +291,7 @@ extern "C" int bdv_temporal_nanreduce_f32(const float* frames, int64_t total_fra
   BDV_REQUIRE(frames && first && counts && first_host && counts_host && out, "bdv_temporal_nanreduce_f32: null pointer");
   BDV_REQUIRE(V > 0 && V <= 65535 && P > 0 && P < (1ll << 31) - 1024, "bdv_temporal_nanreduce_f32: bad batch (V=%d, P=%lld)", V, (long long)P);
   BDV_REQUIRE(mode == 0 || mode == 1, "bdv_temporal_nanreduce_f32: mode %d (0 = median | 1 = mean)", mode);
-  for (int v = 0; v < V; ++v)
-    BDV_REQUIRE(counts_host[v] >= 1 && counts_host[v] <= 65535 && first_host[v] >= 0 && first_host[v] + counts_host[v] <= total_frames,
-                "bdv_temporal_nanreduce_f32: video %d: frames %lld..%lld of %lld (1..65535 frames per video)", v, (long long)first_host[v],
-                (long long)first_host[v] + counts_host[v] - 1, (long long)total_frames);
+  if (int rc = bdv_check_video_runs("bdv_temporal_nanreduce_f32", first_host, counts_host, V, total_frames)) return rc;
   dim3 grid((unsigned)((P + kRedThreads - 1) / kRedThreads), (unsigned)V);
   hipStream_t s = (hipStream_t)stream;
   if (mode == 0)

@@ -70,6 +70,16 @@ class BackgroundCropFrontEnd:
         B, Hs, Ws, _ = bg_u8.shape
         Hr, Wr = K.resized_size(Hs, Ws, self.resize)
         tops, lefts = self.draw(B, Hr, Wr) if offsets is None else offsets
+        tops, lefts = [int(v) for v in tops], [int(v) for v in lefts]
+        # the kernel reads the resized image at (top[b] + y, left[b] + x) unchecked: refuse a crop that leaves it before any upload
+        if len(tops) != B or len(lefts) != B:
+            raise ValueError(f'BackgroundCropFrontEnd: {len(tops)} tops and {len(lefts)} lefts for {B} images')
+        # (a crop larger than the image is refused by bg_resize_crop_u8, with torchvision's message)
+        max_top, max_left = Hr - self.crop[0], Wr - self.crop[1]
+        inside = all(0 <= t <= max_top for t in tops) and all(0 <= x <= max_left for x in lefts)
+        if max_top >= 0 and max_left >= 0 and not inside:
+            raise ValueError(f'BackgroundCropFrontEnd: offsets tops {tops} / lefts {lefts} for {B} images: every {self.crop[0]}x{self.crop[1]} '
+                             f'crop must lie inside the resized {Hr}x{Wr} image (0 <= top <= {max_top}, 0 <= left <= {max_left})')
         dev = bg_u8.device
         return K.bg_resize_crop_u8(bg_u8, self.resize, self.crop[0], self.crop[1],
                                    torch.tensor(list(tops), dtype=torch.int32).to(dev), torch.tensor(list(lefts), dtype=torch.int32).to(dev))

@@ -964,6 +964,32 @@ def avgpool_bwd(dout, in_shape, dtype=torch.float32):
     return dx
 
 
+def _f3(values):
+    return (ctypes.c_float * 3)(*[float(v) for v in values])
+
+
+def _mean_inv_std(mean, std):
+    """``(mean, 1 / std)`` as ``c_float * 3`` each; the reciprocal is taken in fp32, as the CPU restatement computes it."""
+    inv = 1.0 / torch.tensor(list(std), dtype=torch.float32)
+    return _f3(mean), _f3(inv.tolist())
+
+
+def _out_pair(B, F, h, w, want_nhwc4, want_nchw, device):
+    """The front-ends' outputs for B samples of F frames: ``(o4 (B*F, h, w, 4) | None, oc (B, F, 3, h, w) | None)`` fp32."""
+    o4 = torch.empty((B * F, h, w, 4), dtype=torch.float32, device=device) if want_nhwc4 else None
+    oc = torch.empty((B, F, 3, h, w), dtype=torch.float32, device=device) if want_nchw else None
+    return o4, oc
+
+
+def _video_runs(counts, device):
+    """Frames per video -> ``(first, counts)`` of the videos' runs in a tensor that holds them back to back, as
+    ``(first_h int64, counts_h int32, first_d, counts_d)``: on the host (the library validates them there) and on the device."""
+    counts_h = torch.tensor([int(c) for c in counts], dtype=torch.int32)
+    first_h = torch.zeros(counts_h.shape[0], dtype=torch.int64)
+    first_h[1:] = torch.cumsum(counts_h[:-1], 0)
+    return first_h, counts_h, first_h.to(device), counts_h.to(device)
+
+
 def bgmix_normalize_u8(frames, bg, mix, alpha, mean, std, want_nhwc4=True, want_nchw=False):
     """frames (B,T,H,W,3) u8, bg (B,H,W,3) u8 -- or fp32 pixel values in [0,255], the output of ``bg_resize_crop_u8`` -- | None,
     mix (B,) u8/bool | None."""
@@ -978,14 +1004,10 @@ def bgmix_normalize_u8(frames, bg, mix, alpha, mean, std, want_nhwc4=True, want_
         _chk(mix, (B,), dtype=torch.uint8, name='mix')
     else:
         mix = None
-    f3 = ctypes.c_float * 3
-    m = torch.tensor(list(mean), dtype=torch.float32)
-    s = torch.tensor(list(std), dtype=torch.float32)
-    inv = 1.0 / s      # fp32 reciprocal, as the CPU restatement computes it
-    o4 = torch.empty((B * T, H, W, 4), dtype=torch.float32, device=frames.device) if want_nhwc4 else None
-    oc = torch.empty((B, T, 3, H, W), dtype=torch.float32, device=frames.device) if want_nchw else None
-    check(lib().bdv_bgmix_normalize_u8(_p(frames), _p(bg), int(bg_f32), _p(mix), float(alpha), f3(*m.tolist()), f3(*s.tolist()),
-                                       f3(*inv.tolist()), _p(o4), _p(oc), B, T, H, W, _stream()), 'bdv_bgmix_normalize_u8')
+    m3, inv3 = _mean_inv_std(mean, std)
+    o4, oc = _out_pair(B, T, H, W, want_nhwc4, want_nchw, frames.device)
+    check(lib().bdv_bgmix_normalize_u8(_p(frames), _p(bg), int(bg_f32), _p(mix), float(alpha), m3, _f3(std), inv3, _p(o4), _p(oc), B, T, H, W,
+                                       _stream()), 'bdv_bgmix_normalize_u8')
     return o4, oc
 
 
@@ -1040,16 +1062,13 @@ def temporal_nanreduce_f32(frames, counts, mode: int = 0, zero_is_missing: bool 
     _chk(frames, dtype=torch.float32, name='frames')
     if frames.dim() < 2:
         raise ValueError(f'temporal_nanreduce_f32: expected (F, ...), got {tuple(frames.shape)}')
-    counts_h = torch.tensor([int(c) for c in counts], dtype=torch.int32)
+    dev = frames.device
+    first_h, counts_h, first_d, counts_d = _video_runs(counts, dev)
     V = int(counts_h.shape[0])
-    first_h = torch.zeros(V, dtype=torch.int64)
-    first_h[1:] = torch.cumsum(counts_h[:-1], 0)
     P = 1
     for d in frames.shape[1:]:
         P *= int(d)
-    dev = frames.device
     out = torch.empty((V,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=dev)
-    first_d, counts_d = first_h.to(dev), counts_h.to(dev)
     check(lib().bdv_temporal_nanreduce_f32(_p(frames), int(frames.shape[0]), _p(first_d), _p(counts_d), first_h.data_ptr(),
                                            counts_h.data_ptr(), V, P, int(mode), 1 if zero_is_missing else 0, _p(out), _stream()),
           'bdv_temporal_nanreduce_f32')
@@ -1065,18 +1084,16 @@ def temporal_masked_median_u8(frames, counts, box_first, boxes, min_visible: int
     _chk(frames, dtype=torch.uint8, name='frames')
     if frames.dim() != 4 or frames.shape[-1] != 3:
         raise ValueError(f'temporal_masked_median_u8: expected (F,H,W,3), got {tuple(frames.shape)}')
-    counts_h = torch.tensor([int(c) for c in counts], dtype=torch.int32)
+    dev = frames.device
+    first_h, counts_h, first_d, counts_d = _video_runs(counts, dev)
     V, H, W = int(counts_h.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-    first_h = torch.zeros(V, dtype=torch.int64)
-    first_h[1:] = torch.cumsum(counts_h[:-1], 0)
     bf_h = torch.as_tensor(box_first).to('cpu', torch.int32).reshape(-1).contiguous()
     bx_h = torch.as_tensor(boxes).to('cpu', torch.int32).reshape(-1, 4).contiguous()
     if bf_h.shape[0] != frames.shape[0] + 1:
         raise ValueError(f'temporal_masked_median_u8: box_first has {bf_h.shape[0]} entries for {frames.shape[0]} frames')
-    dev = frames.device
     out = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev)
     visible = torch.empty((V, H, W), dtype=torch.uint16, device=dev)
-    first_d, counts_d, bf_d, bx_d = first_h.to(dev), counts_h.to(dev), bf_h.to(dev), bx_h.to(dev)
+    bf_d, bx_d = bf_h.to(dev), bx_h.to(dev)
     nb = int(bx_h.shape[0])
     check(lib().bdv_temporal_masked_median_u8(_p(frames), int(frames.shape[0]), _p(first_d), _p(counts_d), first_h.data_ptr(),
                                               counts_h.data_ptr(), V, H, W, _p(bf_d), _p(bx_d) if nb else None, bf_h.data_ptr(),
@@ -1120,14 +1137,10 @@ def crop_normalize_u8(frames, crops, crop_h, crop_w, mean, std, want_nhwc4=True,
     B, T, H, W, _ = frames.shape
     n = len(crops)
     table = (ctypes.c_int32 * (3 * n))(*[int(v) for c in crops for v in c])
-    f3 = ctypes.c_float * 3
-    m = torch.tensor(list(mean), dtype=torch.float32)
-    inv = 1.0 / torch.tensor(list(std), dtype=torch.float32)      # fp32 reciprocal, as in bgmix_normalize_u8
-    o4 = torch.empty((B * n * T, crop_h, crop_w, 4), dtype=torch.float32, device=frames.device) if want_nhwc4 else None
-    oc = torch.empty((B, n * T, 3, crop_h, crop_w), dtype=torch.float32, device=frames.device) if want_nchw else None
-    check(lib().bdv_crop_normalize_u8(_p(frames), ctypes.cast(table, ctypes.c_void_p), n, int(crop_h), int(crop_w),
-                                      f3(*m.tolist()), f3(*inv.tolist()), _p(o4), _p(oc), B, T, H, W, _stream()),
-          'bdv_crop_normalize_u8')
+    m3, inv3 = _mean_inv_std(mean, std)
+    o4, oc = _out_pair(B, n * T, crop_h, crop_w, want_nhwc4, want_nchw, frames.device)
+    check(lib().bdv_crop_normalize_u8(_p(frames), ctypes.cast(table, ctypes.c_void_p), n, int(crop_h), int(crop_w), m3, inv3, _p(o4), _p(oc),
+                                      B, T, H, W, _stream()), 'bdv_crop_normalize_u8')
     return o4, oc
 
 
@@ -1163,15 +1176,11 @@ def crop_normalize_ragged_u8(src, clips, T: int, crops, crop_h, crop_w, mean, st
     if hk.dim() != 3 or hk.shape[0] != B or hk.shape[2] != 3:
         raise ValueError(f'crop_normalize_ragged_u8: crops must be ({B}, n, 3), got {tuple(hk.shape)}')
     n = int(hk.shape[1])
-    f3 = ctypes.c_float * 3
-    m = torch.tensor(list(mean), dtype=torch.float32)
-    inv = 1.0 / torch.tensor(list(std), dtype=torch.float32)      # fp32 reciprocal, as in crop_normalize_u8
-    o4 = torch.empty((B * n * T, crop_h, crop_w, 4), dtype=torch.float32, device=src.device) if want_nhwc4 else None
-    oc = torch.empty((B, n * T, 3, crop_h, crop_w), dtype=torch.float32, device=src.device) if want_nchw else None
+    m3, inv3 = _mean_inv_std(mean, std)
+    o4, oc = _out_pair(B, n * T, crop_h, crop_w, want_nhwc4, want_nchw, src.device)
     dc, dk = hc.to(src.device), hk.to(src.device)
     check(lib().bdv_crop_normalize_ragged_u8(_p(src), src.numel(), _p(dc), hc.data_ptr(), _p(dk), hk.data_ptr(), n, int(crop_h), int(crop_w),
-                                             f3(*m.tolist()), f3(*inv.tolist()), _p(o4), _p(oc), B, int(T), _stream()),
-          'bdv_crop_normalize_ragged_u8')
+                                             m3, inv3, _p(o4), _p(oc), B, int(T), _stream()), 'bdv_crop_normalize_ragged_u8')
     return o4, oc
 
 
@@ -1196,12 +1205,9 @@ def actor_cut_mix_u8(actor, scene, plan, nclips: int, out, mean, std):
     host = torch.as_tensor(plan, dtype=torch.int32).reshape(-1).contiguous()
     dev = host.to(actor.device, non_blocking=False)
     counts = torch.empty(int(nclips), dtype=torch.int32, device=actor.device)
-    f3 = ctypes.c_float * 3
-    m = torch.tensor(list(mean), dtype=torch.float32)
-    inv = 1.0 / torch.tensor(list(std), dtype=torch.float32)      # fp32 reciprocal, as in bgmix_normalize_u8
+    m3, inv3 = _mean_inv_std(mean, std)
     check(lib().bdv_actor_cut_mix_u8(_p(actor), n_actor, Ha, Wa, _p(scene), n_scene, Hs, Ws, _p(dev), host.data_ptr(), int(host.numel()),
-                                     int(nclips), T, Hd, Wd, f3(*m.tolist()), f3(*inv.tolist()), _p(out), B_out, _p(counts), _stream()),
-          'bdv_actor_cut_mix_u8')
+                                     int(nclips), T, Hd, Wd, m3, inv3, _p(out), B_out, _p(counts), _stream()), 'bdv_actor_cut_mix_u8')
     return counts
 
 
