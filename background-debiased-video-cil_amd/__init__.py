@@ -22,6 +22,8 @@ Import as ``bdvcil_amd`` (see ``bdvcil_amd.py`` at the repo root).  Layout:
 * ``task_loop``    the CIL task loop (CILTrainer + CILDataModule bookkeeping, same files on disk)
 * ``config_run``   a reference config file -> the clip loader that computes its pipelines (``tools/train_cil.py`` runs one)
 * ``gradcam``      Grad-CAM of a 2D recognizer: map, colormap overlay and the map's share inside person boxes (csrc/gradcam.hip)
+* ``kd_importance``  time-channel importance of the distilled features (TCD-style): gradient-based estimator and the map arithmetic
+                   (csrc/tc_kd.hip; config key ``kd_importance`` of the task loop)
 * ``bias``         background reliance of a trained model: actor attention and scene-only accuracy (``tools/bias_report.py``)
 """
 import os as _os
@@ -58,6 +60,7 @@ from .blending import CutmixBlending, ForegroundMergeBlending, MixupBlending, fo
 from .resnet3d import I3DHead, Recognizer3D, ResNet3d  # noqa: F401
 from .hooks import OutputHook, rgetattr  # noqa: F401
 from .functional import KDPodFlatFn, KDPodSpatialFn, kd_pod_flat, kd_pod_spatial  # noqa: F401
+from .functional import KDTimeChannelFn, kd_time_channel  # noqa: F401
 from .optim import (CILTSMOptimizerConstructor, CILTSMOptimizerConstructorImprovised, FusedSGD, build_lr_scheduler,  # noqa: F401
                     build_optimizer)
 from .frontend import BackgroundCropFrontEnd, BackgroundMixFrontEnd, CropFrontEnd, MultiScaleCropResize, TrainClipFrontEnd, crop_offsets  # noqa: F401
@@ -74,6 +77,7 @@ from .representation import Herding, ReprPredictor, class_means_from_repr, nme_c
 from .task_loop import AttrDict, CILTaskLoop, CILWorkDir, RawframeRecords, SyntheticClipLoader, TaskSplits  # noqa: F401
 from .config_run import build_clip_loader, clip_loader_spec, load_config  # noqa: F401
 from .gradcam import GradCAM  # noqa: F401
+from .kd_importance import KD_IMPORTANCE_TYPES, estimate_kd_importance, update_kd_importance  # noqa: F401
 from . import bias, gradcam  # noqa: F401,E402
 
 __version__ = '0.1.0'

@@ -164,6 +164,10 @@ SIGNATURES = {
     'bdv_pod_spatial_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, c_int, P]),
     'bdv_pod_spatial_bwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'bdv_pod_flat': (c_int, [P, P, P, P, c_int, c_int, P, c_size_t, c_int, P]),
+    'bdv_kd_tc_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'bdv_kd_tc_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, c_int, P]),
+    'bdv_kd_tc_bwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'bdv_tc_sqgrad_accum': (c_int, [P, P, c_float, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'bdv_multi_sqnorm':(c_int, [P, P, c_int, P, P, c_size_t, P]),
     'bdv_clip_coef': (c_int, [P, c_float, c_float, P, P]),
     'bdv_multi_sgd': (c_int, [P, P, P, P, P, P, c_int, c_float, c_float, P, P]),
@@ -187,7 +191,7 @@ class HipExtensionError(RuntimeError):
 
 
 HASHED_SOURCES = ('conv_mfma.hip', 'bn.hip', 'pool_frontend.hip', 'head_loss.hip', 'repr.hip', 'augment.hip', 'optim.hip', 'jpeg.hip',
-                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'ragged.hip', 'gradcam.hip', 'blend.hip', 'pod_kd.hip', 'fg_merge.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'loader_pieces.h', 'conv_row_run.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
+                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'ragged.hip', 'gradcam.hip', 'blend.hip', 'pod_kd.hip', 'fg_merge.hip', 'tc_kd.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'loader_pieces.h', 'conv_row_run.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
 
 
 def source_hash():

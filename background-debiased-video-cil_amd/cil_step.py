@@ -39,10 +39,13 @@ def check_kd_type(kd_type, num_modules: int, key: str = 'kd_type') -> List[str]:
     return kinds
 
 
-def _kd_term(kind: str, m_name: str, cur: torch.Tensor, prev: torch.Tensor):
+def _kd_term(kind: str, m_name: str, cur: torch.Tensor, prev: torch.Tensor, importance: Optional[torch.Tensor] = None):
     """One module's distillation loss.  'pod' is resolved on the hooked output: POD-spatial for a map (H*W > 1), POD-flat for
-    pooled (N, D, 1, 1) / (N, D) features."""
+    pooled (N, D, 1, 1) / (N, D) features.  ``importance`` (T, C): the module's time-channel map, which weights the 'mse' term
+    (``functional.kd_time_channel``); the POD losses take none."""
     if kind == 'mse':
+        if importance is not None:
+            return Fn.kd_time_channel(cur, prev, importance)
         return Fn.kd_mse(cur, prev)
     is_map = cur.dim() == 4 and cur.shape[2] * cur.shape[3] > 1
     if kind == 'pod':
@@ -62,14 +65,25 @@ def base_training_step(current_model: nn.Module, batch_data: Dict[str, torch.Ten
                        prev_hooks: Optional[OutputHook] = None, kd_modules_names: Sequence[str] = (),
                        kd_weight_by_module: Sequence[float] = (), adaptive_scale_factors: Sequence[float] = (),
                        kd_exemplar_only: bool = False, previous_task_num_classes: int = 0,
-                       kd_type='mse') -> Dict[str, torch.Tensor]:
+                       kd_type='mse', kd_importance: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
     """libs/cil/cil.py:512-556.  Returns the ``losses`` dict with an extra ``'loss'`` entry (the value the
     reference returns from ``training_step``).
 
     ``kd_type`` (one of ``KD_TYPES``, or one per entry of ``kd_modules_names``): the per-module distillation loss.  'mse' is the
     reference's ``nn.MSELoss``; 'pod_spatial' / 'pod_flat' are PODNet's pooled-output losses (UPSTREAM, unpinned; csrc/pod_kd.hip),
-    'pod' picks between the two by the hooked output's shape.  Weights, scale factors and ``kd_exemplar_only`` apply alike."""
+    'pod' picks between the two by the hooked output's shape.  Weights, scale factors and ``kd_exemplar_only`` apply alike.
+
+    ``kd_importance`` ``{module name: (T, C) fp32 tensor}``: time-channel importance maps (TCD; UPSTREAM, unpinned; csrc/tc_kd.hip).
+    An 'mse' module named in it distils with ``mean(A[n mod T, c] * (cur - prev)^2)``, rows n = b * T + t; all ones is the plain MSE.
+    Modules of another ``kd_type`` and modules not named keep their loss.  Not with ``kd_exemplar_only``: its row selection indexes
+    frames by sample position, after which ``n mod T`` has no meaning."""
     kd_kinds = check_kd_type(kd_type, len(kd_modules_names))
+    if kd_importance:
+        if kd_exemplar_only:
+            raise ValueError('kd_importance cannot be combined with kd_exemplar_only=True: the selected rows are no whole clips')
+        unknown = sorted(set(kd_importance) - set(kd_modules_names))
+        if unknown:
+            raise ValueError(f'kd_importance names {unknown}, which are not in kd_modules_names')
     imgs, labels = batch_data['imgs'], batch_data['label']
     losses = current_model(imgs, labels, batch_data=batch_data)
     use_kd = prev_model is not None and len(kd_modules_names) > 0
@@ -93,7 +107,7 @@ def base_training_step(current_model: nn.Module, batch_data: Dict[str, torch.Ten
                 else:
                     kd_loss = 0
             else:
-                kd_loss = _kd_term(kd_kind, m_name, cur, prev)
+                kd_loss = _kd_term(kd_kind, m_name, cur, prev, kd_importance.get(m_name) if kd_importance else None)
             losses[m_name] = kd_loss
             total_kd_loss = total_kd_loss + scale_factor * kd_weight * kd_loss
         losses['kd_loss'] = total_kd_loss

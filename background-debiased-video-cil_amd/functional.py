@@ -1037,3 +1037,23 @@ def kd_pod_spatial(cur: torch.Tensor, prev: torch.Tensor) -> torch.Tensor:
 
 def kd_pod_flat(cur: torch.Tensor, prev: torch.Tensor) -> torch.Tensor:
     return KDPodFlatFn.apply(cur, prev.detach())
+
+
+class KDTimeChannelFn(torch.autograd.Function):
+    """The MSE of libs/cil/cil.py:519-541 weighted by a time-channel importance map (T, C): mean of
+    ``importance[n mod T, c] * (cur - prev)^2`` over hooked outputs whose rows are frames n = b * T + t (csrc/tc_kd.hip).  Saves ``cur``,
+    ``prev`` and the map; ``prev`` and the map get no gradient."""
+
+    @staticmethod
+    def forward(ctx, cur, prev, importance):
+        ctx.save_for_backward(cur, prev, importance)
+        return K.kd_tc_fwd(cur, prev, importance)
+
+    @staticmethod
+    def backward(ctx, g):
+        cur, prev, importance = ctx.saved_tensors
+        return K.kd_tc_bwd(cur, prev, importance, g.reshape(1).to(torch.float32).contiguous()), None, None
+
+
+def kd_time_channel(cur: torch.Tensor, prev: torch.Tensor, importance: torch.Tensor) -> torch.Tensor:
+    return KDTimeChannelFn.apply(cur, prev.detach(), importance.detach())

@@ -71,19 +71,46 @@ def box_table(boxes, B: int, T: int):
 
 
 class _ReRoot:
-    """Forward hook of the target module: keeps its output, re-rooted as a leaf when it carries no graph (every parameter frozen)."""
+    """Forward hook of the target module: keeps its output, re-rooted as a leaf when it carries no graph (every parameter frozen).
+    ``dims``: the tensor ranks the module may return; ``who``: the caller, for the message."""
 
-    def __init__(self):
+    def __init__(self, dims=(4,), who='GradCAM: the target layer', expected='an (N, C, h, w) tensor'):
         self.output = None
+        self.dims, self.who, self.expected = tuple(dims), who, expected
 
     def __call__(self, module, inputs, output):
-        if not isinstance(output, torch.Tensor) or output.dim() != 4:
-            raise TypeError(f'GradCAM: the target layer must return an (N, C, h, w) tensor, got {type(output).__name__} '
+        if not isinstance(output, torch.Tensor) or output.dim() not in self.dims:
+            raise TypeError(f'{self.who} must return {self.expected}, got {type(output).__name__} '
                             f'{tuple(getattr(output, "shape", ()))}')
         if not output.requires_grad:
             output = output.detach().requires_grad_()
         self.output = output
         return output
+
+
+@contextlib.contextmanager
+def borrowed_frozen_eval(model):
+    """eval mode, ``average_clips='score'``, no trainable parameter -- and everything as it was afterwards, also when the body
+    raises.  Shared by ``GradCAM`` and ``kd_importance.estimate_kd_importance``."""
+    flags = [(m, m.training) for m in model.modules()]
+    grads = [(p, p.requires_grad) for p in model.parameters()]
+    had_cfg = hasattr(model, 'test_cfg')
+    cfg = model.test_cfg if had_cfg else None
+    try:
+        model.eval()
+        model.test_cfg = dict(cfg or {}, average_clips='score')
+        for p, _ in grads:
+            p.requires_grad_(False)
+        yield
+    finally:
+        for p, r in grads:
+            p.requires_grad_(r)
+        if had_cfg:
+            model.test_cfg = cfg
+        else:
+            del model.test_cfg
+        for m, t in flags:
+            m.training = t
 
 
 class GradCAM:
@@ -110,29 +137,9 @@ class GradCAM:
         self.mean, self.std = tuple(float(m) for m in mean), tuple(float(s) for s in std)
         self._lut_dev = None
 
-    @contextlib.contextmanager
     def _borrowed(self):
         """eval mode, ``average_clips='score'``, no trainable parameter -- and everything as it was afterwards."""
-        model = self.model
-        flags = [(m, m.training) for m in model.modules()]
-        grads = [(p, p.requires_grad) for p in model.parameters()]
-        had_cfg = hasattr(model, 'test_cfg')
-        cfg = model.test_cfg if had_cfg else None
-        try:
-            model.eval()
-            model.test_cfg = dict(cfg or {}, average_clips='score')
-            for p, _ in grads:
-                p.requires_grad_(False)
-            yield
-        finally:
-            for p, r in grads:
-                p.requires_grad_(r)
-            if had_cfg:
-                model.test_cfg = cfg
-            else:
-                del model.test_cfg
-            for m, t in flags:
-                m.training = t
+        return borrowed_frozen_eval(self.model)
 
     def _forward(self, imgs):
         return self.model(imgs, return_loss=False)

@@ -1616,6 +1616,79 @@ def pod_flat(cur, prev):
     return loss[0], d
 
 
+def _tc_nhwc(t: torch.Tensor, name: str, dtypes=(torch.float32, torch.bfloat16)) -> torch.Tensor:
+    """The (N, H, W, C) storage of a hooked KD module's output -- (N, C, H, W), (N, D, 1, 1) or (N, D): channels-last strides are
+    used in place, any other layout costs one copy."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f'{name}: expected a tensor, got {type(t)}')
+    if not t.is_cuda:
+        raise RuntimeError(f'{name}: the HIP path needs a GPU tensor (got device {t.device}); there is no CPU fallback')
+    if t.dtype not in dtypes:
+        raise TypeError(f'{name}: dtype {t.dtype}, expected one of {dtypes}')
+    if t.dim() == 2:
+        t = t[:, :, None, None]
+    if t.dim() != 4:
+        raise ValueError(f'{name}: expected (N, C, H, W), (N, D, 1, 1) or (N, D), got shape {tuple(t.shape)}')
+    p = t.permute(0, 2, 3, 1)
+    return p if p.is_contiguous() else p.contiguous()
+
+
+def _tc_map(table: torch.Tensor, N: int, C: int, name: str, what: str = 'importance') -> torch.Tensor:
+    """The fp32 (T, C) table of the time-channel kernels -- the importance map or the accumulator -- for N frames of C channels."""
+    _chk(table, name=f'{name}: {what}')
+    if table.dim() != 2 or table.shape[1] != C or table.shape[0] == 0 or N % table.shape[0] != 0:
+        raise ValueError(f'{name}: {what} of shape {tuple(table.shape)} for {N} frames of {C} channels; expected (T, C) with '
+                         f'T dividing the frame count')
+    return table
+
+
+def kd_tc_fwd(cur, prev, importance):
+    """Time-channel weighted distillation loss (csrc/tc_kd.hip): mean over all elements of ``importance[n mod T, c] * (cur - prev)^2``
+    for hooked outputs of shape (N, C, H, W), (N, D, 1, 1) or (N, D) and an fp32 (T, C) map."""
+    a, b = _tc_nhwc(cur, 'kd_tc: cur'), _tc_nhwc(prev, 'kd_tc: prev')
+    if cur.shape != prev.shape or cur.dtype != prev.dtype:
+        raise ValueError(f'kd_tc: cur {tuple(cur.shape)} {cur.dtype} and prev {tuple(prev.shape)} {prev.dtype} differ')
+    N, H, W, C = a.shape
+    A = _tc_map(importance, N, C, 'kd_tc')
+    T = A.shape[0]
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    ws = workspace(lib().bdv_kd_tc_workspace_bytes(N, T, C, H, W), a.device, 'tc')
+    check(lib().bdv_kd_tc_fwd(_p(a), _p(b), _p(A), _p(loss), N, T, C, H, W, _p(ws), ws.numel(), _act_code(a), _stream()), 'bdv_kd_tc_fwd')
+    return loss[0]
+
+
+def kd_tc_bwd(cur, prev, importance, gscale_dev):
+    """``dcur = gscale * 2 / numel * importance[n mod T, c] * (cur - prev)`` in ``cur``'s shape, strides and dtype."""
+    a, b = _tc_nhwc(cur, 'kd_tc_bwd: cur'), _tc_nhwc(prev, 'kd_tc_bwd: prev')
+    if cur.shape != prev.shape or cur.dtype != prev.dtype:
+        raise ValueError(f'kd_tc_bwd: cur {tuple(cur.shape)} {cur.dtype} and prev {tuple(prev.shape)} {prev.dtype} differ')
+    N, H, W, C = a.shape
+    A = _tc_map(importance, N, C, 'kd_tc_bwd')
+    _chk(gscale_dev.reshape(1), (1,), name='kd_tc_bwd: gscale')
+    out = torch.empty_like(cur)                      # cur's strides when cur is dense
+    o4 = out[:, :, None, None] if out.dim() == 2 else out
+    d = o4.permute(0, 2, 3, 1)
+    direct = out.stride() == cur.stride() and d.is_contiguous()
+    if not direct:
+        d = torch.empty_like(a)
+    check(lib().bdv_kd_tc_bwd(_p(a), _p(b), _p(A), _p(gscale_dev), _p(d), N, A.shape[0], C, H, W, _act_code(a), _stream()), 'bdv_kd_tc_bwd')
+    if not direct:
+        o4.copy_(d.permute(0, 3, 1, 2))
+    return out
+
+
+def tc_sqgrad_accum(S, grad, scale):
+    """``S[t, c] += scale^2 * sum_{b,h,w} grad[b*T+t, c, h, w]^2`` in place, for an fp32 gradient at a hooked module and the fp32
+    (T, C) accumulator ``S`` (csrc/tc_kd.hip): two stages in a fixed order, so ``S`` is bitwise reproducible."""
+    g = _tc_nhwc(grad, 'tc_sqgrad_accum: grad', dtypes=(torch.float32,))
+    N, H, W, C = g.shape
+    _tc_map(S, N, C, 'tc_sqgrad_accum', 'S')
+    T = S.shape[0]
+    ws = workspace(lib().bdv_kd_tc_workspace_bytes(N, T, C, H, W), g.device, 'tc')
+    check(lib().bdv_tc_sqgrad_accum(_p(g), _p(S), float(scale), N, T, C, H, W, _p(ws), ws.numel(), _stream()), 'bdv_tc_sqgrad_accum')
+    return S
+
+
 def _dense_storage(t: torch.Tensor) -> torch.Tensor:
     """Flat view over the storage of a dense (possibly permuted) tensor."""
     if not t.is_cuda or t.dtype not in (torch.float32, torch.bfloat16):

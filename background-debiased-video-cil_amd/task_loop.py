@@ -29,6 +29,7 @@ from . import kernels as K
 from .cil_step import check_kd_type, base_training_step, icarl_training_step, icarl_video_mix_training_step
 from .ddp import GradAllReducer, broadcast_parameters
 from .hooks import OutputHook
+from .kd_importance import KD_IMPORTANCE_TYPES, estimate_kd_importance, update_kd_importance
 from .optim import build_lr_scheduler, build_optimizer
 from .registry import build_model
 from .representation import Herding, ReprPredictor, class_means_from_repr, nme_classify
@@ -397,6 +398,49 @@ def check_loop_fg_merge(config):
     return out
 
 
+def check_loop_kd_importance(config):
+    """The ``kd_importance`` key of a loop config (absent or None = off), validated without touching the GPU:
+    ``dict(type='time_channel', batches=None, mix=0.0)`` with ``batches`` a positive int (estimation batches per rank; None = all) and
+    ``mix`` in [0, 1].  Returns the dict of the three values, or None.  The map weights the 'mse' distillation of ``methods='base'``
+    per (segment, channel), so the key is refused where it could not act or its estimator could not run."""
+    spec = config.get('kd_importance')
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError(f"kd_importance must be a dict(type='time_channel', batches=, mix=), got {spec!r}")
+    unknown = sorted(set(spec) - {'type', 'batches', 'mix'})
+    if unknown:
+        raise ValueError(f'kd_importance: unknown keys {unknown} (known: type, batches, mix)')
+    out = dict(type=spec.get('type', 'time_channel'), batches=spec.get('batches'), mix=spec.get('mix', 0.0))
+    if out['type'] not in KD_IMPORTANCE_TYPES:
+        raise ValueError(f"kd_importance: type={out['type']!r}, expected one of {KD_IMPORTANCE_TYPES}")
+    b = out['batches']
+    if b is not None and (isinstance(b, bool) or not isinstance(b, int) or b <= 0):
+        raise ValueError(f'kd_importance: batches must be a positive integer or None, got {b!r}')
+    m = out['mix']
+    if isinstance(m, bool) or not isinstance(m, (int, float)) or not 0 <= m <= 1:
+        raise ValueError(f'kd_importance: mix must be a number in [0, 1], got {m!r}')
+    method = config.get('methods', 'base')
+    if method != 'base':
+        raise ValueError(f"kd_importance has no effect with methods={method!r}: only methods='base' distils hooked features")
+    names = list(config.get('kd_modules_names') or ())
+    if not names:
+        raise ValueError('kd_importance has no effect without kd_modules_names')
+    if config.get('kd_exemplar_only', False):
+        raise ValueError('kd_importance cannot be combined with kd_exemplar_only=True: its row selection indexes frames by sample '
+                         'position, so a row no longer tells its segment')
+    kinds = check_kd_type(config.get('kd_type', 'mse'), len(names), key='kd_type')
+    if 'mse' not in kinds:
+        raise ValueError(f"kd_importance weights the 'mse' distillation only and kd_type={config.get('kd_type')!r} leaves no 'mse' module")
+    if config.get('conv_arith') == 'bf16':
+        raise ValueError("kd_importance cannot be combined with conv_arith='bf16': the estimator needs the backward through eval-mode "
+                         "BatchNorm, which is not implemented for bf16 activation storage; use conv_arith='bf16x1'")
+    model_type = str((config.get('model') or {}).get('type', ''))
+    if model_type.endswith('3D'):
+        raise ValueError(f'kd_importance needs a 2D recognizer (rows of the hooked outputs must be frames), got model type {model_type!r}')
+    return out
+
+
 def _in_arith(fn):
     """A public entry point of the loop runs under the loop's ``conv_arith`` (nothing to do without one); the process's own
     arithmetic is back when it returns or raises.  Entry points call each other: the blocks nest."""
@@ -436,6 +480,16 @@ class CILTaskLoop:
     list with one entry per ``kd_modules_names``.  Unknown values, a list of the wrong length, and a non-default value with another
     method raise ``ValueError`` here.
 
+    Config key ``kd_importance=dict(type='time_channel', batches=None, mix=0.0)`` (absent or None = off; beyond the reference, TCD-style):
+    at the end of every task but the last, on the weights that become the teacher, the loop estimates per 'mse' module how much each
+    (segment, channel) of its output matters to ``loss_cls`` (``kd_importance.estimate_kd_importance`` over the task's training records,
+    exemplars included, phase 'features_extraction', ``videos_per_gpu`` clips per batch, at most ``batches`` batches per rank), averages
+    the normalised map with the earlier tasks' and weights the next task's MSE with it, mixed toward uniform by ``mix``.  Rank 0
+    writes the unmixed maps to ``work_dir/kd_importance_task_{i}.pt``; a loop with ``starting_task > 0`` loads the file of the task
+    before and raises ``FileNotFoundError`` without it.  ``history`` gets a record per estimation.  Validated here by
+    ``check_loop_kd_importance``: ``methods='base'``, ``kd_modules_names`` with an 'mse' module, no ``kd_exemplar_only``, not
+    ``conv_arith='bf16'``, a 2D recognizer.
+
     Config key ``fg_merge=dict(beta, prob, bins)`` (absent = off): foreground merging (``blending.ForegroundMergeBlending``, beyond the
     reference) of ``batch_data['imgs']``, in place, at the top of every training step -- all three ``methods``, CBF fits included, so
     the KD teacher sees the merged clips too; never in validation, feature extraction or test.  Labels are untouched.  Validated here
@@ -447,6 +501,9 @@ class CILTaskLoop:
         self.config = config = config if isinstance(config, AttrDict) else AttrDict(config)
         self.conv_arith = check_loop_conv_arith(config)         # before any file or GPU work
         self.kd_type = check_loop_kd_type(config)
+        self.kd_importance_cfg = check_loop_kd_importance(config)
+        self.kd_importance: Optional[Dict[str, torch.Tensor]] = None       # {module: (T, C)} mixed maps on the device, from task 1 on
+        self._kd_importance_raw: Dict[str, torch.Tensor] = {}              # the unmixed maps A_k (fp32, CPU): what the file stores
         fg = check_loop_fg_merge(config)
         self.fg_merge = None
         if fg is not None:
@@ -636,6 +693,66 @@ class CILTaskLoop:
             for i in range(self._current_task):
                 self._all_bg_files.update(dict.fromkeys(self._train_records(self.files.task_splits_ann_files['train'][i]).bg_files))
         self.reload_train_dataset(use_internal_exemplar=True)
+        if self.kd_importance_cfg is not None:
+            path = self.kd_importance_file(self._current_task - 1)
+            self._barrier()
+            if not path.exists():
+                raise FileNotFoundError(f'{path}: kd_importance is set and starting_task={self.starting_task}, but the importance maps of '
+                                        f'task {self._current_task - 1} are missing; they cannot be rebuilt without the earlier tasks\' data')
+            maps = torch.load(path, map_location='cpu', weights_only=True)
+            self._set_kd_importance({n: m.to(torch.float32) for n, m in maps.items()})
+
+    # -- time-channel importance (config key kd_importance) --------------------------------------------------------------
+    def kd_importance_file(self, task_idx: int) -> pathlib.Path:
+        return self.files.work_dir / f'kd_importance_task_{task_idx}.pt'
+
+    def _kd_importance_names(self) -> List[str]:
+        names = list(self.config.kd_modules_names)
+        return [n for n, k in zip(names, check_kd_type(self.kd_type, len(names))) if k == 'mse']
+
+    def _set_kd_importance(self, raw: Dict[str, torch.Tensor]) -> None:
+        """Hold the unmixed maps and put their mixed form on the device for the step."""
+        mix = float(self.kd_importance_cfg['mix'])
+        self._kd_importance_raw = {n: m.detach().to('cpu', torch.float32) for n, m in raw.items()}
+        self.kd_importance = {n: ((1.0 - mix) * m.double() + mix).to(torch.float32).to(self.device).contiguous()
+                              for n, m in self._kd_importance_raw.items()}
+
+    @_in_arith
+    def estimate_kd_importance(self) -> Dict:
+        """Estimate the maps of the current task on ``current_model`` (the weights that become the teacher), merge them with the
+        earlier tasks', hold them for the next task's step, write the file and return the ``history`` record."""
+        cfg, spec, t = self.config, self.kd_importance_cfg, self._current_task
+        records = RawframeRecords(None, None, test_mode=True, phase='features_extraction')
+        records.video_infos = list(self.train_dataset.video_infos)
+        mine = epoch_batches(len(records), cfg.videos_per_gpu, False)[self.rank::self.world]
+        if spec['batches'] is not None:
+            mine = mine[:spec['batches']]
+        names = self._kd_importance_names()
+        T = self.current_model.cls_head.num_segments
+        try:
+            sums = estimate_kd_importance(self.current_model, self._load(records, mine), names, T)
+        except BaseException:
+            self.close()
+            raise
+        count = torch.tensor([float(next(iter(sums.values()))[1]) if sums else 0.0], dtype=torch.float64, device=self.device)
+        if self.world > 1:
+            dist.all_reduce(count)
+            for n in names:
+                dist.all_reduce(sums[n][0])
+        samples = int(count.item())
+        raw, entry = {}, {}
+        for n in names:
+            a_k, mixed, degenerate = update_kd_importance(sums[n][0], samples, self._kd_importance_raw.get(n), t, spec['mix'])
+            if degenerate:
+                self.log(f'Task {t} kd_importance: the gradient map of {n} is zero or not finite; its importance is uniform')
+            raw[n] = a_k
+            entry[n] = dict(min=float(mixed.min()), max=float(mixed.max()))
+        self._set_kd_importance(raw)
+        self._save_state(self._kd_importance_raw, self.kd_importance_file(t))
+        self._barrier()
+        record = dict(kd_importance=True, task=t, batches=len(mine), samples=samples, modules=entry)
+        self.log('Task {} kd_importance over {} samples ({} batches on this rank): {}'.format(t, samples, len(mine), entry))
+        return record
 
     def _freeze_prev(self):
         for p in self.prev_model.parameters():
@@ -666,7 +783,8 @@ class CILTaskLoop:
                                   adaptive_scale_factors=list(cfg.adaptive_scale_factors) if self.use_kd else (),
                                   kd_exemplar_only=cfg.get('kd_exemplar_only', False),
                                   previous_task_num_classes=self.num_classes(t - 1),
-                                  kd_type=self.kd_type if self.use_kd else 'mse')
+                                  kd_type=self.kd_type if self.use_kd else 'mse',
+                                  kd_importance=self.kd_importance if self.use_kd else None)
 
     @_in_arith
     def fit(self, records: RawframeRecords, max_epochs: int, validate: bool = False) -> List[float]:
@@ -924,6 +1042,12 @@ class CILTaskLoop:
             self.history.append(record)
             self._current_task += 1
             if self._current_task < self.num_tasks:
+                if self.kd_importance_cfg is not None:
+                    self._current_task = t                   # the estimate belongs to the task just learned
+                    try:
+                        self.history.append(self.estimate_kd_importance())
+                    finally:
+                        self._current_task = t + 1
                 self.prev_model.load_state_dict(self.current_model.state_dict())
                 self.prev_model.eval()
                 self.current_model.update_fc(self.num_classes(self._current_task))

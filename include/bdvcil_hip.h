@@ -509,6 +509,29 @@ int bdv_pod_spatial_bwd(const void* cur, const float* G, const float* gscale_dev
 int bdv_pod_flat(const void* cur, const void* prev, float* loss, float* dcur_unit, int N, int D, void* workspace,
                  size_t workspace_bytes, int act_dtype, void* stream);
 
+/* ---- time-channel importance distillation (csrc/tc_kd.hip) ------------------------------------
+ * UPSTREAM, unpinned: TCD (Park, Kang, Han, "Class-Incremental Learning for Action Recognition in Videos", ICCV 2021), the
+ * importance-weighted feature distillation and its gradient-based estimator as DESIGN 4.12 defines them; the reference has no
+ * such code.  Tensors are NHWC (N, H, W, C), N = B * T frames with row n = b * T + t; importance and S are (T, C) fp32.
+ * C % 4 == 0, N % T == 0, H * W * C / 4 <= 2^30, N / T * H * W <= 2^30. */
+/* libs/cil/cil.py:519-541 (site): bytes of workspace for bdv_kd_tc_fwd and bdv_tc_sqgrad_accum at these sizes (the larger of the
+ * forward's per-block partials and the accumulator's fp64 (T, C) slabs).  0 for a size either would refuse. */
+size_t bdv_kd_tc_workspace_bytes(int N, int T, int C, int H, int W);
+/* libs/cil/cil.py:519-541 (site), the nn.MSELoss weighted per (segment, channel):
+ * loss = 1 / (N C H W) * sum importance[n mod T, c] * (cur - prev)^2.  importance == 1 is bdv_kd_mse_fwd's value (another
+ * summation order).  act_dtype: element type of cur / prev. */
+int bdv_kd_tc_fwd(const void* cur, const void* prev, const float* importance, float* loss, int N, int T, int C, int H, int W,
+                  void* workspace, size_t workspace_bytes, int act_dtype, void* stream);
+/* libs/cil/cil.py:519-541 (site): dcur = gscale_dev[0] * 2 / (N C H W) * importance[n mod T, c] * (cur - prev), in the element
+ * type of cur; importance == 1 gives bdv_kd_mse_bwd's bits. */
+int bdv_kd_tc_bwd(const void* cur, const void* prev, const float* importance, const float* gscale_dev, void* dcur, int N, int T,
+                  int C, int H, int W, int act_dtype, void* stream);
+/* libs/cil/cil.py:519-541 (site), the estimator of the importance map: S[t, c] += scale^2 * sum_{b,h,w} grad[b*T+t, h, w, c]^2
+ * for an fp32 gradient at a hooked module; two stages, a fixed summation order, squares and sums in fp64 (S is rounded once
+ * per call).  Calling it again adds to S. */
+int bdv_tc_sqgrad_accum(const float* grad, float* S, float scale, int N, int T, int C, int H, int W, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ---- representation path: clip representations, NME classifier, class means, herding --------- */
 /* libs/cil/cil.py:501-506 (_extract_repr) + :564-571 (predict_step, extract_repr): feat = the hooked
  * cls_head.avg_pool output flattened to (B*crops*T, D); repr (B*crops, D) = F.normalize(mean over the T segments);

@@ -2,7 +2,7 @@
 
     VIDEO_CIL_ROOT=/data/ucf101 python tools/train_cil.py CONFIG [--test] [--test-nme] [--prefetch N] [--seed S] [--device D]
         [--conv-arith {bf16x3,f32mfma,bf16x2,f16x2,bf16x1,bf16}] [--kd-type {mse,pod,pod_spatial,pod_flat}]
-        [--fg-merge-prob P [--fg-merge-beta B]]
+        [--fg-merge-prob P [--fg-merge-beta B]] [--kd-importance [--kd-importance-mix X]]
 
 CONFIG is a config file of the reference (configs/ucf101/..., self-contained Python that reads VIDEO_CIL_ROOT).  The clip loader is
 built from the config's ``data.train`` and its four pipelines (``bdvcil_amd.clip_loader_spec``; a stage the loaders cannot honour is an
@@ -17,6 +17,9 @@ pooled-output losses ('pod' = POD-spatial on feature maps, POD-flat on pooled fe
 ``--fg-merge-prob P`` sets the config's ``fg_merge`` key: foreground merging of the training batches (a clip keeps its motion
 foreground and takes the rest from another clip of the batch, with probability P; labels untouched), ``--fg-merge-beta B`` the share
 of pixels kept as foreground (default 0.5); both win over the config file, whose other ``fg_merge`` entries stay.
+``--kd-importance`` sets the config's ``kd_importance`` key to ``dict(type='time_channel')``: after every task the loop estimates a
+time-channel importance map per 'mse' distillation module and weights the next task's MSE with it; ``--kd-importance-mix X`` (in
+[0, 1], default 0) mixes the map toward uniform.  Both win over the config file, whose other ``kd_importance`` entries stay.
 Several GPUs: start one process per GPU with torchrun; the process group is picked up from the environment."""
 import argparse
 import os
@@ -46,7 +49,25 @@ def build_parser():
                     help="foreground merging of the training batches with this probability per clip (the config's fg_merge key)")
     ap.add_argument('--fg-merge-beta', type=float, default=None,
                     help='share of the pixels kept as foreground (with --fg-merge-prob or an fg_merge key of the config; default 0.5)')
+    ap.add_argument('--kd-importance', action='store_true',
+                    help="time-channel importance weighting of the 'mse' distillation (the config's kd_importance key)")
+    ap.add_argument('--kd-importance-mix', type=float, default=None,
+                    help='mix the importance map toward uniform by this share (with --kd-importance or a kd_importance key of the config)')
     return ap
+
+
+def set_kd_importance(cfg, on=False, mix=None):
+    """--kd-importance / --kd-importance-mix -> the config's ``kd_importance`` key; entries of the config file that no flag names stay."""
+    if not on and mix is None:
+        return cfg
+    if not on and not cfg.get('kd_importance'):
+        raise SystemExit('--kd-importance-mix needs --kd-importance (the config has no kd_importance key)')
+    spec = dict(cfg.get('kd_importance') or {})
+    spec.setdefault('type', 'time_channel')
+    if mix is not None:
+        spec['mix'] = mix
+    cfg['kd_importance'] = spec
+    return cfg
 
 
 def set_fg_merge(cfg, prob=None, beta=None):
@@ -89,6 +110,8 @@ def main(argv=None):
         cfg['kd_type'] = args.kd_type
     set_fg_merge(cfg, args.fg_merge_prob, args.fg_merge_beta)
     bd.task_loop.check_loop_fg_merge(cfg)
+    set_kd_importance(cfg, args.kd_importance, args.kd_importance_mix)
+    bd.task_loop.check_loop_kd_importance(cfg)
     rank = dist.get_rank() if dist.is_initialized() else 0
     # each rank loads its own share of an epoch: its loader draws from its own stream
     loader = bd.build_clip_loader(cfg, device=device, seed=None if args.seed is None else args.seed + rank, threads=args.threads)
