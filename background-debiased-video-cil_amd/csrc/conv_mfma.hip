@@ -3160,7 +3160,7 @@ WgradPlan plan_wgrad(const bdv_conv_geom* g) {
   p.NTw = p.c4 ? (ktot + bn - 1) / bn : g->R * g->S * (g->Cin / bn);
   const int64_t M = (int64_t)g->N * g->Ho * g->Wo;
   const int nkt = (int)((M + BK - 1) / BK);
-  const int tiles = p.MTw * p.NTw;
+  const int tiles = p.MTw * p.NTw > 0 ? p.MTw * p.NTw : 1;   // (plan_conv refuses what has no tile; no division by zero here either way)
   // blocks = tiles * splits should fill whole rounds of co-resident blocks; slab bytes grow with splits
   int best_s = 1;
   double best_cost = 1e30;
@@ -3239,7 +3239,7 @@ WgradPlPlan plan_wgrad_pl(const bdv_conv_geom* g) {
   p.NTw = ((g->Rt > 1 ? g->Rt : 1) * g->R * g->S * g->Cin + p.BN - 1) / p.BN;
   const int64_t M = (int64_t)g->N * g->Ho * g->Wo;
   const int nkt = (int)((M + BK - 1) / BK);
-  const int tiles = p.MTw * p.NTw;
+  const int tiles = p.MTw * p.NTw > 0 ? p.MTw * p.NTw : 1;
   const int W = p.form == 0 ? 256 : 512;   // the 4-wave forms run two workgroups per CU
   // K-step of one workgroup, microseconds: MFMA-bound for the large tiles; the 64-channel layers are bound by streaming their
   // operands from HBM (a K-step reads 32 x (BM + BN) floats; 256 CUs share ~5 TB/s)
@@ -3351,8 +3351,12 @@ ConvPlan plan_conv(const bdv_conv_geom* g, int kind, int arith, bool pre) {
   PLAN_REQUIRE(kind >= kFprop && kind <= kWgrad && arith >= 0 && arith <= 3, "bdv_conv: kind %d (0 fprop, 1 dgrad, 2 wgrad), arith %d (0 fp32 MFMA, 1..3 bf16 pieces)", kind, arith);
   PLAN_REQUIRE(g->act_dtype == BDV_ACT_F32 || g->act_dtype == BDV_ACT_BF16, "bdv_conv: act_dtype %d (BDV_ACT_F32 = 0 | BDV_ACT_BF16 = 1)", g->act_dtype);
   const bool h16 = g->act_dtype == BDV_ACT_BF16;   // bf16 storage: the single-product plane kernels are the only ones that read / write it
+  // ... and their loaders move 16-byte units of EIGHT bf16 channels under one shift class (shift_class() once per thread and unit)
+  PLAN_REQUIRE(!h16 || g->fold % 8 == 0, "bdv_conv: bf16 activation storage needs fold %% 8 == 0 (fold=%d): a loader unit of 8 channels takes one shift class", g->fold);
   const bool c4 = g->Cin % BK != 0;
   if (kind == kWgrad) {
+    // every weight-gradient tile spans at least 64 input channels of one tap (the stem: 64 taps of 4)
+    PLAN_REQUIRE(g->Cin % 64 == 0 || g->Cin == 4, "bdv_conv_wgrad: Cin=%d must be a multiple of 64 (or exactly 4)", g->Cin);
     const int form = arith ? pl_wgrad_form(g) : -1;
     p.pre_ok = form >= 0 && !c4 && g->fold == 0 && !h16;
     PLAN_REQUIRE(!pre || p.pre_ok, "bdv_conv_wgrad: a producer BatchNorm in the loader needs the plane kernel, fp32 tensors, Cin %% 32 == 0 and no temporal shift");

@@ -37,7 +37,8 @@ extern "C" {
  * `precision=16` counterpart; bf16 instead of fp16: same MFMA rate on gfx950, fp32's exponent range, no loss scaler).  Values
  * widen exactly on load, arithmetic and accumulators stay fp32, stores round to nearest-even; BatchNorm statistics, weights,
  * weight gradients, ReLU masks and everything after the average pool stay fp32.  Convolutions then run the single-product bf16
- * MFMA kernels (pieces = 1) only. */
+ * MFMA kernels (pieces = 1) only, and a temporal shift needs fold % 8 == 0 there (fp32 tensors: fold % 4 == 0): the loaders move
+ * 16-byte units, eight bf16 channels, under one shift class; bdv_conv_plan_query refuses other folds. */
 #define BDV_ACT_F32 0
 #define BDV_ACT_BF16 1
 
@@ -52,7 +53,7 @@ typedef struct bdv_conv_geom {
   int32_t stride; /* 1 or 2 */
   int32_t pad;
   int32_t T;      /* num_segments (frames per clip); used only when fold > 0 */
-  int32_t fold;   /* temporal-shift fold = Cin / shift_div, multiple of 4; 0 = no shift */
+  int32_t fold;   /* temporal-shift fold = Cin / shift_div, multiple of 4 (of 8 under BDV_ACT_BF16); 0 = no shift */
   int32_t pad_w;  /* column padding when it differs from `pad` (then `pad` pads rows only); < 0: same as `pad`.
                    * A k x 1 x 1 temporal convolution of an I3D block (UPSTREAM mmaction ResNet3d Bottleneck3d.conv1,
                    * configs/_base_/models/i3d_r50.py:13) runs as a k x 1 conv on the [B][T][H*W][C] view of the same NHWC
