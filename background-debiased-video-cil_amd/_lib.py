@@ -191,7 +191,7 @@ class HipExtensionError(RuntimeError):
 
 
 HASHED_SOURCES = ('conv_mfma.hip', 'bn.hip', 'pool_frontend.hip', 'head_loss.hip', 'repr.hip', 'augment.hip', 'optim.hip', 'jpeg.hip',
-                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'ragged.hip', 'gradcam.hip', 'blend.hip', 'pod_kd.hip', 'fg_merge.hip', 'tc_kd.hip', 'api_common.cpp', 'common.h', 'resize_linear.h', 'loader_pieces.h', 'conv_row_run.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
+                  'background.hip', 'actor_cut_mix.hip', 'sim_cam.hip', 'ragged.hip', 'gradcam.hip', 'blend.hip', 'pod_kd.hip', 'fg_merge.hip', 'tc_kd.hip', 'api_common.cpp', 'common.h', 'reduce_pieces.h', 'resize_linear.h', 'loader_pieces.h', 'conv_row_run.h', 'Makefile', '../../include/bdvcil_hip.h')   # = HASHED in csrc/Makefile
 
 
 def source_hash():

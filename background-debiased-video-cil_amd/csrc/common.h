@@ -10,12 +10,20 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 void bdv_set_error(const char* fmt, ...);
 
-#define BDV_REQUIRE(cond, ...)        \
-  do {                                \
-    if (!(cond)) {                    \
-      bdv_set_error(__VA_ARGS__);     \
-      return BDV_EINVAL;              \
-    }                                 \
+// BDV_REQUIRE_CODE(cond, code, fmt, ...): unless cond holds, set the message and return code
+#define BDV_REQUIRE_CODE(cond, code, ...) \
+  do {                                    \
+    if (!(cond)) {                        \
+      bdv_set_error(__VA_ARGS__);         \
+      return code;                        \
+    }                                     \
+  } while (0)
+#define BDV_REQUIRE(cond, ...) BDV_REQUIRE_CODE(cond, BDV_EINVAL, __VA_ARGS__)
+// the "workspace too small" refusal of an entry point called `name` (a string literal): have / need in bytes, need evaluated once
+#define BDV_REQUIRE_WORKSPACE(name, have, need)                                                                                   \
+  do {                                                                                                                            \
+    const size_t need__ = (need);                                                                                                 \
+    BDV_REQUIRE_CODE((have) >= need__, BDV_EWORKSPACE, name ": workspace %zu < required %zu bytes", (size_t)(have), need__);      \
   } while (0)
 
 #define BDV_LAUNCH_CHECK(name)                                              \
@@ -54,22 +62,8 @@ static inline int bdv_check_video_runs(const char* who, const int64_t* first_hos
   return BDV_OK;
 }
 
-// wave-level and block-level sum (wave = 64 lanes)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+// wave_sum, wave_max, the block sums, the fp64 finalize, the softmax and arg-best pieces of the step tail
+#include "reduce_pieces.h"
 
 // ---- activation storage ------------------------------------------------------------------------------------------------
 // ES = bytes per activation element: 4 = fp32 (default everywhere), 2 = bf16 storage (BDV_ACT_BF16: BASELINE config 5, the

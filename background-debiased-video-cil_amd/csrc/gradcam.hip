@@ -133,15 +133,8 @@ struct RenderArgs {
   float alpha, mean[3], std[3];
 };
 
-// sum over the block in a fixed order: butterfly inside each wave, then the four wave sums left to right
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  __syncthreads();                      // sh may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
+// The block sums below: butterfly inside each wave, then the four wave sums left to right (SumOrder::Sequential); sh may still be
+// read from the previous call (REUSE).
 // one block per output row (b, t, y)
 __global__ __launch_bounds__(256) void gradcam_render_kernel(const RenderArgs a) {
   __shared__ double sh[4];
@@ -193,8 +186,8 @@ __global__ __launch_bounds__(256) void gradcam_render_kernel(const RenderArgs a)
     }
   }
   if (a.off) {
-    sv = block_sum_d(sv, sh);
-    si = block_sum_d(si, sh);
+    sv = block_sum<SumOrder::Sequential, true>(sv, sh);
+    si = block_sum<SumOrder::Sequential, true>(si, sh);
     if (threadIdx.x == 0) {
       a.partial[2 * row] = sv;
       a.partial[2 * row + 1] = si;
@@ -211,8 +204,8 @@ __global__ __launch_bounds__(256) void gradcam_sums_kernel(const double* __restr
     sv += p[2 * r];
     si += p[2 * r + 1];
   }
-  sv = block_sum_d(sv, sh);
-  si = block_sum_d(si, sh);
+  sv = block_sum<SumOrder::Sequential, true>(sv, sh);
+  si = block_sum<SumOrder::Sequential, true>(si, sh);
   if (threadIdx.x == 0) {
     sums[2 * blockIdx.x] = (float)sv;
     sums[2 * blockIdx.x + 1] = (float)si;

@@ -41,6 +41,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
       }
     else
       for (int d = tid; d < D; d += 256) xs[r * D + d] = 0.f;
+    // the block sum (SumOrder::Sequential) stays written out: through block_sum the linear head's instantiation, which drops the
+    // sums, came out at 2944 bytes for 6744 and ran 45.8 -> 48.1 us at (256, 2048) x 101 (profiles/tail_kernel_dedupe.txt)
     ss[r] = wave_sum(ss[r]);
     if (lane == 0) red[r][wave] = ss[r];
   }
@@ -91,15 +93,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
     __syncthreads();
     for (int q = tid; q < rows * K; q += 256) {
       const int r = q / K, k = q - r * K;
-      const float* c = cs + r * KP + k * P;
-      float mx = c[0];
-      for (int p = 1; p < P; ++p) mx = fmaxf(mx, c[p]);
-      float den = 0.f, num = 0.f;
-      for (int p = 0; p < P; ++p) {
-        const float e = expf(c[p] - mx);
-        den += e;
-        num += e * c[p];
-      }
+      float mx, den, num;
+      proxy_softmax(cs + r * KP + k * P, P, mx, den, num);
       out[(size_t)(n0 + r) * K + k] = num / den;
     }
   }
@@ -122,14 +117,8 @@ __global__ __launch_bounds__(256) void lsc_bwd_dx_kernel(const float* __restrict
   const float nx = xnorm[n];
   for (int k = tid; k < K; k += 256) {
     const float* c = cosbuf + (size_t)n * KP + k * P;
-    float mx = c[0];
-    for (int p = 1; p < P; ++p) mx = fmaxf(mx, c[p]);
-    float den = 0.f, num = 0.f;
-    for (int p = 0; p < P; ++p) {
-      const float e = expf(c[p] - mx);
-      den += e;
-      num += e * c[p];
-    }
+    float mx, den, num;
+    proxy_softmax(c, P, mx, den, num);
     const float sbar = num / den;
     const float g = dsim[(size_t)n * K + k];
     for (int p = 0; p < P; ++p) {
@@ -296,7 +285,7 @@ __global__ __launch_bounds__(256) void lsc_loss_kernel(const float* __restrict__
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float eta = eta_p[0];
   const float invB = 1.f / (float)B;
-  float loss_acc = 0.f, deta_acc = 0.f;
+  float acc[2] = {0.f, 0.f};  // loss, deta: lane 0 of each wave carries its rows
   for (int b = wave; b < B; b += 4) {
     const float* row = sim + (size_t)b * K;
     const int y = (int)targets[b];
@@ -306,12 +295,7 @@ __global__ __launch_bounds__(256) void lsc_loss_kernel(const float* __restrict__
       const float s = lsc_logit(eta, row[k], margin);
       if (s > mx) { mx = s; am = k; }
     }
-    // wave argmax with first-index tie break
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(mx, o, 64);
-      const int oa = __shfl_xor(am, o, 64);
-      if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
-    }
+    wave_argbest<ArgMax>(mx, am);
     float esum = 0.f;
     for (int k = lane; k < K; k += 64)
       if (k != y) esum += expf(lsc_logit(eta, row[k], margin) - mx);
@@ -321,7 +305,7 @@ __global__ __launch_bounds__(256) void lsc_loss_kernel(const float* __restrict__
     const float wgt = class_weights != nullptr ? class_weights[y] : 1.f;
     const float l = wgt * (logf(den) - num);
     const bool active = !hinge || l >= 0.f;
-    if (lane == 0) loss_acc += active ? l : 0.f;
+    if (lane == 0) acc[0] += active ? l : 0.f;
     float dpart = 0.f;
     for (int k = lane; k < K; k += 64) {
       float g = 0.f;  // dl/ds_k
@@ -334,16 +318,12 @@ __global__ __launch_bounds__(256) void lsc_loss_kernel(const float* __restrict__
       dpart += g * (row[k] - margin);
     }
     dpart = wave_sum(dpart);
-    if (lane == 0) deta_acc += dpart;
+    if (lane == 0) acc[1] += dpart;
   }
-  if (lane == 0) {
-    red[0][wave] = loss_acc;
-    red[1][wave] = deta_acc;
-  }
-  __syncthreads();
+  block_combine<SumOrder::Sequential>(acc, red);
   if (tid == 0) {
-    loss[0] = (red[0][0] + red[0][1] + red[0][2] + red[0][3]) * invB;
-    deta[0] = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) * invB;
+    loss[0] = acc[0] * invB;
+    deta[0] = acc[1] * invB;
   }
 }
 
@@ -358,10 +338,8 @@ __global__ __launch_bounds__(256) void softce_kernel(const float* __restrict__ s
   for (int b = wave; b < B; b += 4) {
     const float* row = score + (size_t)b * K;
     const int y = soft ? -1 : (int)labels[b];
-    float mx = -INFINITY;
-    for (int k = lane; k < K; k += 64) mx = fmaxf(mx, row[k]);
-    mx = wave_max(mx);
-    float es = 0.f, tsum = 0.f, ts = 0.f;
+    const float mx = wave_row_max(row, K, lane);
+    float es = 0.f, tsum = 0.f, ts = 0.f;  // one pass for all three: not wave_softmax_stats, which would read the row once more
     for (int k = lane; k < K; k += 64) {
       es += expf(row[k] - mx);
       const float t = soft ? soft[(size_t)b * K + k] : (k == y ? 1.f : 0.f);
@@ -378,9 +356,8 @@ __global__ __launch_bounds__(256) void softce_kernel(const float* __restrict__ s
       dscore[(size_t)b * K + k] = (expf(row[k] - lse) * tsum - t) * invB;
     }
   }
-  if (lane == 0) red[wave] = loss_acc;
-  __syncthreads();
-  if (tid == 0) loss[0] = (red[0] + red[1] + red[2] + red[3]) * invB;
+  loss_acc = block_combine<SumOrder::Sequential>(loss_acc, red);
+  if (tid == 0) loss[0] = loss_acc * invB;
 }
 
 // one wave per row: targets = onehot or softmax(prev logits) for old-class samples
@@ -393,12 +370,8 @@ __global__ __launch_bounds__(256) void icarl_targets_kernel(const int64_t* __res
   const int y = (int)labels[b];
   if (prev != nullptr && y < prevK) {
     const float* row = prev + (size_t)b * K;
-    float mx = -INFINITY;
-    for (int k = lane; k < K; k += 64) mx = fmaxf(mx, row[k]);
-    mx = wave_max(mx);
-    float es = 0.f;
-    for (int k = lane; k < K; k += 64) es += expf(row[k] - mx);
-    es = wave_sum(es);
+    float mx, es;
+    wave_softmax_stats(row, K, lane, mx, es);
     for (int k = lane; k < K; k += 64) tgt[(size_t)b * K + k] = expf(row[k] - mx) / es;
   } else {
     for (int k = lane; k < K; k += 64) tgt[(size_t)b * K + k] = base != nullptr ? base[(size_t)b * K + k] : ((k == y) ? 1.f : 0.f);
@@ -430,14 +403,7 @@ __global__ __launch_bounds__(256) void softmax_mean_kernel(const float* __restri
   for (int i = 0; i < n; ++i) {
     const float* row = s + ((size_t)b * n + i) * K;
     float mx = 0.f, es = 1.f;
-    if (apply_softmax) {
-      mx = -INFINITY;
-      for (int k = lane; k < K; k += 64) mx = fmaxf(mx, row[k]);
-      mx = wave_max(mx);
-      es = 0.f;
-      for (int k = lane; k < K; k += 64) es += expf(row[k] - mx);
-      es = wave_sum(es);
-    }
+    if (apply_softmax) wave_softmax_stats(row, K, lane, mx, es);
     for (int k = lane; k < K; k += 64) {
       const float v = apply_softmax ? expf(row[k] - mx) / es : row[k];
       out[(size_t)b * K + k] += v;
@@ -451,24 +417,20 @@ __global__ __launch_bounds__(256) void topk_acc_kernel(const float* __restrict__
                                                         float* __restrict__ acc, int B, int K) {
   __shared__ int red[2][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int h1 = 0, h5 = 0;
+  int hits[2] = {0, 0};  // top-1, top-5 of the wave's rows
   for (int b = wave; b < B; b += 4) {
     const float* row = score + (size_t)b * K;
     const float ys = row[(int)labels[b]];
     int greater = 0;
     for (int k = lane; k < K; k += 64) greater += row[k] > ys ? 1 : 0;
-    for (int o = 32; o > 0; o >>= 1) greater += __shfl_xor(greater, o, 64);
-    h1 += greater < 1;
-    h5 += greater < 5;
+    greater = wave_sum(greater);
+    hits[0] += greater < 1;
+    hits[1] += greater < 5;
   }
-  if (lane == 0) {
-    red[0][wave] = h1;
-    red[1][wave] = h5;
-  }
-  __syncthreads();
+  block_combine<SumOrder::Sequential>(hits, red);
   if (tid == 0) {
-    acc[0] = (float)(red[0][0] + red[0][1] + red[0][2] + red[0][3]) / (float)B;
-    acc[1] = (float)(red[1][0] + red[1][1] + red[1][2] + red[1][3]) / (float)B;
+    acc[0] = (float)hits[0] / (float)B;
+    acc[1] = (float)hits[1] / (float)B;
   }
 }
 
@@ -479,25 +441,15 @@ template <int ES = 4>
 __global__ __launch_bounds__(256) void sqdiff_partial_kernel(const void* __restrict__ a, const void* __restrict__ b,
                                                               float* __restrict__ partial, int64_t n4) {
   __shared__ float red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   float s = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n4; i += (int64_t)gridDim.x * 256) {
     const float4 x = act_ld4<ES>(a, i), y = act_ld4<ES>(b, i);
     const float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
     s += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
   }
-  s = wave_sum(s);
-  if (lane == 0) red[wave] = s;
-  __syncthreads();
-  if (tid == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void mse_finalize_kernel(const float* __restrict__ partial, int nb, double inv_numel, float* __restrict__ out) {
-  const int lane = threadIdx.x;  // one wave
-  double s = 0.0;
-  for (int i = lane; i < nb; i += 64) s += (double)partial[i];
-  s = wave_sum_d(s);
-  if (lane == 0) out[0] = (float)(s * inv_numel);
+  s = block_sum<SumOrder::Sequential>(s, red);
+  if (tid == 0) partial[blockIdx.x] = s;
 }
 
 template <int ES = 4>
@@ -652,17 +604,14 @@ extern "C" int bdv_kd_mse_fwd(const void* cur, const void* prev, float* mse, int
   BDV_REQUIRE_ACT(act_dtype, "bdv_kd_mse_fwd");
   BDV_REQUIRE(cur && prev && mse && workspace && numel > 0 && numel % 4 == 0, "bdv_kd_mse_fwd: bad argument");
   BDV_REQUIRE(bdv_aligned16(cur) && bdv_aligned16(prev), "bdv_kd_mse_fwd: alignment");
-  if (workspace_bytes < bdv_reduce_workspace_bytes()) {
-    bdv_set_error("bdv_kd_mse_fwd: workspace too small");
-    return BDV_EWORKSPACE;
-  }
+  BDV_REQUIRE_CODE(workspace_bytes >= bdv_reduce_workspace_bytes(), BDV_EWORKSPACE, "bdv_kd_mse_fwd: workspace too small");
   const int64_t n4 = numel / 4;
   int nb = (int)((n4 + 255) / 256);
   if (nb > RED_BLOCKS) nb = RED_BLOCKS;
   BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((sqdiff_partial_kernel<ES>), dim3(nb), dim3(256), 0, HL_STREAM, cur, prev,
                      (float*)workspace, n4));
   BDV_LAUNCH_CHECK("bdv_kd_mse_fwd(partial)");
-  hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(64), 0, HL_STREAM, (const float*)workspace, nb, 1.0 / (double)numel, mse);
+  hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(64), 0, HL_STREAM, (const float*)workspace, nb, 1.0 / (double)numel, mse);
   BDV_LAUNCH_CHECK("bdv_kd_mse_fwd(finalize)");
   return BDV_OK;
 }

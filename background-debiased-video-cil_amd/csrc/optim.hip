@@ -21,18 +21,8 @@ __global__ __launch_bounds__(256) void multi_sqnorm_partial_kernel(const float* 
     const float v = g[i];
     s += v * v;
   }
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) partial[(int64_t)t * CHUNKS + cy] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void sqnorm_finalize_kernel(const float* __restrict__ partial, int n, float* __restrict__ out) {
-  const int lane = threadIdx.x;  // one wave
-  double s = 0.0;
-  for (int i = lane; i < n; i += 64) s += (double)partial[i];
-  s = wave_sum_d(s);
-  if (lane == 0) out[0] = (float)s;
+  s = block_sum<SumOrder::Sequential>(s, red);
+  if (tid == 0) partial[(int64_t)t * CHUNKS + cy] = s;
 }
 
 __global__ void clip_coef_kernel(const float* __restrict__ sqnorm, float grad_scale, float max_norm, float* __restrict__ coef) {
@@ -70,14 +60,12 @@ __global__ __launch_bounds__(256) void multi_sgd_kernel(float* const* __restrict
 extern "C" int bdv_multi_sqnorm(const float* const* grads, const int64_t* numels, int ntensors, float* out_sqnorm, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   BDV_REQUIRE(grads && numels && out_sqnorm && workspace && ntensors > 0, "bdv_multi_sqnorm: bad argument");
-  if (workspace_bytes < (size_t)ntensors * CHUNKS * sizeof(float)) {
-    bdv_set_error("bdv_multi_sqnorm: workspace too small (need %zu bytes)", (size_t)ntensors * CHUNKS * sizeof(float));
-    return BDV_EWORKSPACE;
-  }
+  BDV_REQUIRE_CODE(workspace_bytes >= (size_t)ntensors * CHUNKS * sizeof(float), BDV_EWORKSPACE,
+                   "bdv_multi_sqnorm: workspace too small (need %zu bytes)", (size_t)ntensors * CHUNKS * sizeof(float));
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(multi_sqnorm_partial_kernel, dim3(ntensors, CHUNKS), dim3(256), 0, s, grads, numels, (float*)workspace);
   BDV_LAUNCH_CHECK("bdv_multi_sqnorm(partial)");
-  hipLaunchKernelGGL(sqnorm_finalize_kernel, dim3(1), dim3(64), 0, s, (const float*)workspace, ntensors * CHUNKS, out_sqnorm);
+  hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(64), 0, s, (const float*)workspace, ntensors * CHUNKS, 1.0, out_sqnorm);
   BDV_LAUNCH_CHECK("bdv_multi_sqnorm(finalize)");
   return BDV_OK;
 }

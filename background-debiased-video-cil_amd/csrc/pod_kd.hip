@@ -7,8 +7,8 @@
 //
 // Passes of pod_spatial.  Forward: pod_profile_kernel reads cur and prev once each (grid.z picks the tensor) and writes the two
 // profiles (N, H+W, C) fp32 plus one squared-norm partial per (frame, channel slab); pod_frame_kernel (one block per frame, reads
-// the profiles only) writes the frame's distance and the profile gradient G (N, H+W, C); pod_mean_kernel sums the N distances in
-// a fixed order.  Backward: pod_spatial_bwd_kernel reads cur and G and writes dcur = g * 2 * cur * (G[n,h,c] + G[n,H+w,c]).
+// the profiles only) writes the frame's distance and the profile gradient G (N, H+W, C); sum_finalize_kernel (reduce_pieces.h) sums the N
+// distances in a fixed order.  Backward: pod_spatial_bwd_kernel reads cur and G and writes dcur = g * 2 * cur * (G[n,h,c] + G[n,H+w,c]).
 // Every output location is written by exactly one thread and every sum has a fixed order: no atomics, run-to-run bitwise equal.
 //
 // Limits: C % 4 == 0 (16-byte lanes along C); H <= 64 and W <= 64 (POD_MAX_HW).  The column sums of a thread live in registers,
@@ -23,9 +23,6 @@ constexpr float POD_EPS = 1e-12f;   // F.normalize eps and cosine_embedding_loss
 constexpr int POD_MAX_HW = 64;
 constexpr int POD_CG = 16;          // channel groups (float4) per slab: 16 lanes x 16 B (fp32) along C
 constexpr int POD_WL = 4;           // column lanes per wave; the 4 waves of a block split the rows
-
-__device__ __forceinline__ float4 f4_add(const float4 a, const float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float f4_sq(const float4 a) { return (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w); }
 
 // grid (S, N, 2): block = frame n, channel slab s, tensor z (0 = cur, 1 = prev).  lane = (wl, cgl): cgl = channel group inside the
 // slab, wl = column lane; thread (wave, wl, cgl) reads the pixels (h, w) with h = wave (mod 4), w = wl (mod 4).
@@ -127,6 +124,8 @@ __global__ __launch_bounds__(256) void pod_profile_kernel(const void* __restrict
     }
     if (wv < 3) __syncthreads();
   }
+  // the block sum (SumOrder::Pairwise) stays written out here and in pod_frame_kernel: through block_sum the forward missed its
+  // timing on the layer-3 and layer-4 maps (profiles/tail_kernel_dedupe.txt)
   sq = wave_sum(sq);
   if (lane == 0) red[wave] = sq;
   __syncthreads();
@@ -180,15 +179,6 @@ __global__ __launch_bounds__(256) void pod_frame_kernel(const float4* __restrict
     g[i] = zero ? make_float4(0.f, 0.f, 0.f, 0.f)
                 : make_float4((d.x - ph.x * t) * k, (d.y - ph.y * t) * k, (d.z - ph.z * t) * k, (d.w - ph.w * t) * k);
   }
-}
-
-// out = sum(v[0..n)) * inv: one wave, fixed order
-__global__ void pod_mean_kernel(const float* __restrict__ v, int n, double inv, float* __restrict__ out) {
-  const int lane = threadIdx.x;
-  double s = 0.0;
-  for (int i = lane; i < n; i += 64) s += (double)v[i];
-  s = wave_sum_d(s);
-  if (lane == 0) out[0] = (float)(s * inv);
 }
 
 // grid N*H: block = one row (n, h) of W * C4 channel groups
@@ -251,25 +241,22 @@ extern "C" size_t bdv_pod_workspace_bytes(int N, int C, int H, int W) {
   return ((size_t)2 * N * (H + W) * C + (size_t)2 * N * pod_slabs(C) + (size_t)N) * sizeof(float);
 }
 
-#define POD_REQUIRE_WS(name, need)                                                              \
-  do {                                                                                          \
-    if (workspace_bytes < (need)) {                                                             \
-      bdv_set_error(name ": workspace %zu < required %zu bytes", workspace_bytes, (size_t)(need)); \
-      return BDV_EWORKSPACE;                                                                    \
-    }                                                                                           \
+// what bdv_pod_spatial_fwd and bdv_pod_spatial_bwd ask of N, C, H, W
+#define POD_REQUIRE_SHAPE(name)                                                                                              \
+  do {                                                                                                                       \
+    BDV_REQUIRE(C % 4 == 0, name ": C=%d is not a multiple of 4", C);                                                        \
+    BDV_REQUIRE(H <= POD_MAX_HW && W <= POD_MAX_HW, name ": H=%d W=%d exceeds the %d x %d limit", H, W, POD_MAX_HW, POD_MAX_HW); \
+    BDV_REQUIRE(N <= 65535, name ": N=%d exceeds 65535 frames", N);                                                          \
   } while (0)
 
 extern "C" int bdv_pod_spatial_fwd(const void* cur, const void* prev, float* loss, float* G, int N, int C, int H, int W,
                                    void* workspace, size_t workspace_bytes, int act_dtype, void* stream) {
   BDV_REQUIRE_ACT(act_dtype, "bdv_pod_spatial_fwd");
   BDV_REQUIRE(cur && prev && loss && G && workspace && N > 0 && C > 0 && H > 0 && W > 0, "bdv_pod_spatial_fwd: bad argument");
-  BDV_REQUIRE(C % 4 == 0, "bdv_pod_spatial_fwd: C=%d is not a multiple of 4", C);
-  BDV_REQUIRE(H <= POD_MAX_HW && W <= POD_MAX_HW, "bdv_pod_spatial_fwd: H=%d W=%d exceeds the %d x %d limit", H, W, POD_MAX_HW,
-              POD_MAX_HW);
-  BDV_REQUIRE(N <= 65535, "bdv_pod_spatial_fwd: N=%d exceeds 65535 frames", N);
+  POD_REQUIRE_SHAPE("bdv_pod_spatial_fwd");
   BDV_REQUIRE(bdv_aligned16(cur) && bdv_aligned16(prev) && bdv_aligned16(G) && bdv_aligned16(workspace),
               "bdv_pod_spatial_fwd: alignment");
-  POD_REQUIRE_WS("bdv_pod_spatial_fwd", bdv_pod_workspace_bytes(N, C, H, W));
+  BDV_REQUIRE_WORKSPACE("bdv_pod_spatial_fwd", workspace_bytes, bdv_pod_workspace_bytes(N, C, H, W));
   const int C4 = C / 4, S = pod_slabs(C), L4 = (H + W) * C4;
   float4* prof = (float4*)workspace;
   float* nrm = (float*)workspace + (size_t)2 * N * (H + W) * C;
@@ -287,7 +274,7 @@ extern "C" int bdv_pod_spatial_fwd(const void* cur, const void* prev, float* los
   hipLaunchKernelGGL(pod_frame_kernel, dim3(N), dim3(256), 0, PK_STREAM, (const float4*)prof, (const float*)nrm, (float4*)G, dist, N,
                      L4, S, 1.f / (float)N);
   BDV_LAUNCH_CHECK("bdv_pod_spatial_fwd(frame)");
-  hipLaunchKernelGGL(pod_mean_kernel, dim3(1), dim3(64), 0, PK_STREAM, (const float*)dist, N, 1.0 / (double)N, loss);
+  hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(64), 0, PK_STREAM, (const float*)dist, N, 1.0 / (double)N, loss);
   BDV_LAUNCH_CHECK("bdv_pod_spatial_fwd(mean)");
   return BDV_OK;
 }
@@ -296,10 +283,7 @@ extern "C" int bdv_pod_spatial_bwd(const void* cur, const float* G, const float*
                                    int act_dtype, void* stream) {
   BDV_REQUIRE_ACT(act_dtype, "bdv_pod_spatial_bwd");
   BDV_REQUIRE(cur && G && gscale_dev && dcur && N > 0 && C > 0 && H > 0 && W > 0, "bdv_pod_spatial_bwd: bad argument");
-  BDV_REQUIRE(C % 4 == 0, "bdv_pod_spatial_bwd: C=%d is not a multiple of 4", C);
-  BDV_REQUIRE(H <= POD_MAX_HW && W <= POD_MAX_HW, "bdv_pod_spatial_bwd: H=%d W=%d exceeds the %d x %d limit", H, W, POD_MAX_HW,
-              POD_MAX_HW);
-  BDV_REQUIRE(N <= 65535, "bdv_pod_spatial_bwd: N=%d exceeds 65535 frames", N);
+  POD_REQUIRE_SHAPE("bdv_pod_spatial_bwd");
   BDV_REQUIRE(bdv_aligned16(cur) && bdv_aligned16(G) && bdv_aligned16(dcur), "bdv_pod_spatial_bwd: alignment");
   BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((pod_spatial_bwd_kernel<ES>), dim3(N * H), dim3(256), 0, PK_STREAM, cur,
                                                    (const float4*)G, gscale_dev, dcur, H, W, C / 4));
@@ -313,12 +297,12 @@ extern "C" int bdv_pod_flat(const void* cur, const void* prev, float* loss, floa
   BDV_REQUIRE(cur && prev && loss && dcur_unit && workspace && N > 0 && D > 0, "bdv_pod_flat: bad argument");
   BDV_REQUIRE(D % 4 == 0, "bdv_pod_flat: D=%d is not a multiple of 4", D);
   BDV_REQUIRE(bdv_aligned16(cur) && bdv_aligned16(prev) && bdv_aligned16(dcur_unit), "bdv_pod_flat: alignment");
-  POD_REQUIRE_WS("bdv_pod_flat", bdv_pod_workspace_bytes(N, D, 1, 1));
+  BDV_REQUIRE_WORKSPACE("bdv_pod_flat", workspace_bytes, bdv_pod_workspace_bytes(N, D, 1, 1));
   float* rowloss = (float*)workspace;
   BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((pod_flat_kernel<ES>), dim3((N + 3) / 4), dim3(256), 0, PK_STREAM, cur, prev, rowloss,
                                                    (float4*)dcur_unit, N, D / 4, 1.f / (float)N));
   BDV_LAUNCH_CHECK("bdv_pod_flat(rows)");
-  hipLaunchKernelGGL(pod_mean_kernel, dim3(1), dim3(64), 0, PK_STREAM, (const float*)rowloss, N, 1.0 / (double)N, loss);
+  hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(64), 0, PK_STREAM, (const float*)rowloss, N, 1.0 / (double)N, loss);
   BDV_LAUNCH_CHECK("bdv_pod_flat(mean)");
   return BDV_OK;
 }

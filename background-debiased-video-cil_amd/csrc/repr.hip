@@ -15,14 +15,7 @@ constexpr float NORMALIZE_EPS = 1e-12f;  // F.normalize default eps
 constexpr float COS_EPS = 1e-8f;         // F.cosine_similarity default eps
 constexpr float PDIST_EPS = 1e-6f;       // torch.pairwise_distance default eps (added to the difference)
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  // 256 threads = 4 waves; every thread gets the total (fixed order)
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
+// Every block sum of this file is SumOrder::Pairwise, and its red may still be read from the call before (REUSE).
 
 // grid = B.  feat (B*crops*T, D) -> repr (B*crops, D) = normalize(mean_t feat), mean_crops (B, D) = mean_c repr
 __global__ __launch_bounds__(256) void repr_kernel(const float* __restrict__ feat, float* __restrict__ repr,
@@ -43,7 +36,7 @@ __global__ __launch_bounds__(256) void repr_kernel(const float* __restrict__ fea
       cur[d] = s;
       ss += s * s;
     }
-    const float nrm = fmaxf(sqrtf(block_sum(ss, red)), NORMALIZE_EPS);
+    const float nrm = fmaxf(sqrtf(block_sum<SumOrder::Pairwise, true>(ss, red)), NORMALIZE_EPS);
     for (int d = tid; d < D; d += 256) {
       const float v = cur[d] / nrm;
       repr[(size_t)(b * crops + c) * D + d] = v;
@@ -59,7 +52,7 @@ __global__ __launch_bounds__(256) void row_normalize_kernel(const float* __restr
   const float* r = x + (size_t)blockIdx.x * D;
   float ss = 0.f;
   for (int d = threadIdx.x; d < D; d += 256) ss += r[d] * r[d];
-  const float nrm = fmaxf(sqrtf(block_sum(ss, red)), eps);
+  const float nrm = fmaxf(sqrtf(block_sum<SumOrder::Pairwise, true>(ss, red)), eps);
   for (int d = threadIdx.x; d < D; d += 256) out[(size_t)blockIdx.x * D + d] = r[d] / nrm;
 }
 
@@ -78,7 +71,7 @@ __global__ __launch_bounds__(256) void nme_kernel(const float* __restrict__ repr
     const float* x = repr + (size_t)(s * crops + c) * D;
     float ss = 0.f;
     for (int d = tid; d < D; d += 256) ss += x[d] * x[d];
-    const float nx = fmaxf(sqrtf(block_sum(ss, red)), COS_EPS);
+    const float nx = fmaxf(sqrtf(block_sum<SumOrder::Pairwise, true>(ss, red)), COS_EPS);
     for (int d = tid; d < D; d += 256) xs[d] = x[d] / nx;
     __syncthreads();
     for (int k = wave; k < K; k += 4) {
@@ -100,26 +93,9 @@ __global__ __launch_bounds__(256) void nme_kernel(const float* __restrict__ repr
       bi = k;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) {
-      bv = ov;
-      bi = oi;
-    }
-  }
-  if (lane == 0) {
-    bestv[wave] = bv;
-    besti[wave] = bi;
-  }
-  __syncthreads();
+  wave_argbest<ArgMax>(bv, bi);
+  block_argbest<ArgMax>(bv, bi, bestv, besti);
   if (tid == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (bestv[w] > bv || (bestv[w] == bv && besti[w] < bi)) {
-        bv = bestv[w];
-        bi = besti[w];
-      }
     pred[s] = bi == 0x7fffffff ? 0 : bi;  // all-NaN row: torch.argmax returns the NaN position; 0 is the documented deviation
   }
 }
@@ -177,7 +153,7 @@ __global__ __launch_bounds__(256) void herding_kernel(const float* __restrict__ 
     mov[d] = 0.f;
     ss += s * s;
   }
-  const float tot = block_sum(ss, red);
+  const float tot = block_sum<SumOrder::Pairwise, true>(ss, red);
   if (cosine) {
     const float nrm = fmaxf(sqrtf(tot), NORMALIZE_EPS);
     float ss2 = 0.f;
@@ -186,7 +162,7 @@ __global__ __launch_bounds__(256) void herding_kernel(const float* __restrict__ 
       cm[d] = v;
       ss2 += v * v;
     }
-    const float n2 = fmaxf(sqrtf(block_sum(ss2, red)), COS_EPS);
+    const float n2 = fmaxf(sqrtf(block_sum<SumOrder::Pairwise, true>(ss2, red)), COS_EPS);
     for (int d = tid; d < D; d += 256) cmn[d] = cm[d] / n2;
   }
   for (int d = tid; d < D; d += 256) class_mean[d] = cm[d];
@@ -227,6 +203,7 @@ __global__ __launch_bounds__(256) void herding_kernel(const float* __restrict__ 
         bi = i;
       }
     }
+    // the cross-wave arg-min stays written out: through block_argbest<ArgMin> the loop missed its timing (profiles/tail_kernel_dedupe.txt)
     if (lane == 0) {
       bestv[wave] = bv;
       besti[wave] = bi;
@@ -280,10 +257,7 @@ extern "C" int bdv_nme_classify(const float* repr, const float* class_means, flo
   BDV_REQUIRE(repr && class_means && similarity && pred && workspace && S > 0 && crops > 0 && D > 0 && K > 0,
               "bdv_nme_classify: bad argument");
   BDV_REQUIRE((size_t)(D + K) * sizeof(float) <= 64 * 1024, "bdv_nme_classify: D + K = %d exceeds the 64 KB LDS budget", D + K);
-  if (workspace_bytes < bdv_nme_workspace_bytes(K, D)) {
-    bdv_set_error("bdv_nme_classify: workspace %zu < required %zu bytes", workspace_bytes, bdv_nme_workspace_bytes(K, D));
-    return BDV_EWORKSPACE;
-  }
+  BDV_REQUIRE_WORKSPACE("bdv_nme_classify", workspace_bytes, bdv_nme_workspace_bytes(K, D));
   float* wn = (float*)workspace;
   hipLaunchKernelGGL(row_normalize_kernel, dim3(K), dim3(256), 0, RP_STREAM, class_means, wn, D, COS_EPS);
   BDV_LAUNCH_CHECK("bdv_nme_classify(normalize)");
@@ -313,10 +287,7 @@ extern "C" int bdv_herding_select(const float* features, int n, int D, int num_e
               "bdv_herding_select: %d exemplars requested from %d samples (the reference's argmin fails on the empty remainder)",
               num_exemplars, n);
   BDV_REQUIRE((size_t)3 * D * sizeof(float) <= 96 * 1024, "bdv_herding_select: D=%d exceeds the LDS budget", D);
-  if (workspace_bytes < bdv_herding_workspace_bytes(n, D)) {
-    bdv_set_error("bdv_herding_select: workspace %zu < required %zu bytes", workspace_bytes, bdv_herding_workspace_bytes(n, D));
-    return BDV_EWORKSPACE;
-  }
+  BDV_REQUIRE_WORKSPACE("bdv_herding_select", workspace_bytes, bdv_herding_workspace_bytes(n, D));
   float* nf = (float*)workspace;
   int* alive = (int*)((char*)workspace + (size_t)n * D * sizeof(float));
   auto kern = herding_kernel;

@@ -6,7 +6,7 @@
 //   S[t, c] += scale^2 * sum_{b,h,w} grad[b * T + t, h, w, c]^2                     (the estimator's accumulator, grad fp32)
 //
 // Passes.  Forward: tc_sqdiff_partial_kernel reads cur and prev once each plus the cache-resident table and writes one partial per
-// block; tc_finalize_kernel sums them in fp64 in one wave.  Backward: tc_bwd_kernel, one streaming pass, the upstream scalar read
+// block; sum_finalize_kernel (reduce_pieces.h) sums them in fp64 in one wave.  Backward: tc_bwd_kernel, one streaming pass, the upstream scalar read
 // from device memory.  Accumulator: tc_sqgrad_partial_kernel reads grad once and writes one (T, C) slab per row partition;
 // tc_slab_sum_kernel adds the slabs in ascending order into S (squares and sums in fp64: S is rounded once).  A thread of the loss
 // kernels stays at one unit index inside the frame and one segment at a time, so its table entry is a register; a 16-byte unit never
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void tc_sqdiff_partial_kernel(const void* __re
                                                                  const float4* __restrict__ A, float* __restrict__ partial, int B, int T,
                                                                  int FU, int C4) {
   __shared__ float red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   float s = 0.f;
   for (int i = blockIdx.x * 256 + tid; i < FU; i += gridDim.x * 256) {
     const int c4 = i % C4;
@@ -61,19 +61,8 @@ __global__ __launch_bounds__(256) void tc_sqdiff_partial_kernel(const void* __re
       }
     }
   }
-  s = wave_sum(s);
-  if (lane == 0) red[wave] = s;
-  __syncthreads();
-  if (tid == 0) partial[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// out = sum(partial[0..nb)) * inv: one wave, fixed order, fp64
-__global__ void tc_finalize_kernel(const float* __restrict__ partial, int nb, double inv, float* __restrict__ out) {
-  const int lane = threadIdx.x;
-  double s = 0.0;
-  for (int i = lane; i < nb; i += 64) s += (double)partial[i];
-  s = wave_sum_d(s);
-  if (lane == 0) out[0] = (float)(s * inv);
+  s = block_sum<SumOrder::Pairwise>(s, red);
+  if (tid == 0) partial[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
 }
 
 template <int ES>
@@ -182,15 +171,6 @@ extern "C" size_t bdv_kd_tc_workspace_bytes(int N, int T, int C, int H, int W) {
                 name ": H=%d W=%d C=%d N=%d: a frame or a segment's rows exceed 2^30", H, W, C, N);                      \
   } while (0)
 
-#define TC_REQUIRE_WS(name)                                                                       \
-  do {                                                                                            \
-    const size_t need__ = bdv_kd_tc_workspace_bytes(N, T, C, H, W);                               \
-    if (workspace_bytes < need__) {                                                               \
-      bdv_set_error(name ": workspace %zu < required %zu bytes", workspace_bytes, need__);       \
-      return BDV_EWORKSPACE;                                                                      \
-    }                                                                                             \
-  } while (0)
-
 extern "C" int bdv_kd_tc_fwd(const void* cur, const void* prev, const float* importance, float* loss, int N, int T, int C, int H, int W,
                              void* workspace, size_t workspace_bytes, int act_dtype, void* stream) {
   BDV_REQUIRE_ACT(act_dtype, "bdv_kd_tc_fwd");
@@ -198,14 +178,14 @@ extern "C" int bdv_kd_tc_fwd(const void* cur, const void* prev, const float* imp
   TC_REQUIRE_SHAPE("bdv_kd_tc_fwd");
   BDV_REQUIRE(bdv_aligned16(cur) && bdv_aligned16(prev) && bdv_aligned16(importance) && bdv_aligned16(workspace),
               "bdv_kd_tc_fwd: alignment");
-  TC_REQUIRE_WS("bdv_kd_tc_fwd");
+  BDV_REQUIRE_WORKSPACE("bdv_kd_tc_fwd", workspace_bytes, bdv_kd_tc_workspace_bytes(N, T, C, H, W));
   const int C4 = C / 4, FU = H * W * C4;
   const dim3 grid = tc_grid(N / T, T, FU, TC_BLOCKS);
   const int nb = (int)(grid.x * grid.y * grid.z);
   BDV_ACT_SWITCH(act_dtype, ES, hipLaunchKernelGGL((tc_sqdiff_partial_kernel<ES>), grid, dim3(256), 0, TC_STREAM, cur, prev,
                                                    (const float4*)importance, (float*)workspace, N / T, T, FU, C4));
   BDV_LAUNCH_CHECK("bdv_kd_tc_fwd(partial)");
-  hipLaunchKernelGGL(tc_finalize_kernel, dim3(1), dim3(64), 0, TC_STREAM, (const float*)workspace, nb,
+  hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(64), 0, TC_STREAM, (const float*)workspace, nb,
                      1.0 / ((double)N * (double)FU * 4.0), loss);
   BDV_LAUNCH_CHECK("bdv_kd_tc_fwd(finalize)");
   return BDV_OK;
@@ -230,7 +210,7 @@ extern "C" int bdv_tc_sqgrad_accum(const float* grad, float* S, float scale, int
   BDV_REQUIRE(grad && S && workspace && tc_dims_ok(N, T, C, H, W), "bdv_tc_sqgrad_accum: bad argument");
   TC_REQUIRE_SHAPE("bdv_tc_sqgrad_accum");
   BDV_REQUIRE(bdv_aligned16(grad) && bdv_aligned16(S) && bdv_aligned16(workspace), "bdv_tc_sqgrad_accum: alignment");
-  TC_REQUIRE_WS("bdv_tc_sqgrad_accum");
+  BDV_REQUIRE_WORKSPACE("bdv_tc_sqgrad_accum", workspace_bytes, bdv_kd_tc_workspace_bytes(N, T, C, H, W));
   const int C4 = C / 4, HW = H * W, R = N / T * HW, cgw = tc_cgw(C4), P = tc_parts(N, T, C, HW);
   BDV_REQUIRE(T <= 65535, "bdv_tc_sqgrad_accum: T=%d exceeds 65535 segments", T);
   const dim3 grid((C4 + cgw - 1) / cgw, T, P);

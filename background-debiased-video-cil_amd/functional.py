@@ -1009,6 +1009,8 @@ class KDPodSpatialFn(torch.autograd.Function):
     def backward(ctx, g):
         cur, G = ctx.saved_tensors
         d = K.pod_spatial_bwd(cur, G, g.reshape(1).to(torch.float32).contiguous())
+        # pod_spatial_bwd answers in the strides of what it is given: the input itself when that was channels-last, otherwise the
+        # converted copy saved above -- and then the gradient still has to take the input's own strides
         if d.stride() != ctx.cur_strides:
             d = torch.empty_strided(d.shape, ctx.cur_strides, dtype=d.dtype, device=d.device).copy_(d)
         return d, None

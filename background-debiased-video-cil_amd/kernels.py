@@ -1542,34 +1542,57 @@ def kd_mse_bwd(cur, prev, gscale_dev, gscale_host=1.0):
     if d.stride() != cur.stride():
         raise ValueError('kd_mse_bwd: could not preserve strides')
     if gscale_dev is not None:
-        _chk(gscale_dev.reshape(1), (1,), name='gscale')
+        _gscale(gscale_dev, 'gscale')
     check(lib().bdv_kd_mse_bwd(_p(a), _p(b), _p(gscale_dev), float(gscale_host), _p(_dense_storage(d)), a.numel(), _act_code(a), _stream()),
           'bdv_kd_mse_bwd')
     return d
 
 
-def _pod_nhwc(t: torch.Tensor, name: str) -> torch.Tensor:
-    """The (N, H, W, C) storage of a logical (N, C, H, W) activation: the channels-last strides of the hooked stage outputs are
-    used in place, any other layout costs one copy."""
+def _kd_nhwc(t: torch.Tensor, name: str, dtypes=(torch.float32, torch.bfloat16), allow_2d: bool = False) -> torch.Tensor:
+    """The (N, H, W, C) storage of a hooked KD module's output, logically (N, C, H, W) -- with ``allow_2d`` also (N, D), taken as
+    (N, D, 1, 1): channels-last strides are used in place, any other layout costs one copy."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f'{name}: expected a tensor, got {type(t)}')
     if not t.is_cuda:
         raise RuntimeError(f'{name}: the HIP path needs a GPU tensor (got device {t.device}); there is no CPU fallback')
-    if t.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f'{name}: dtype {t.dtype}, expected torch.float32 or torch.bfloat16')
+    if t.dtype not in dtypes:
+        raise TypeError(f'{name}: dtype {t.dtype}, expected {" or ".join(map(str, dtypes))}')
+    if allow_2d and t.dim() == 2:
+        t = t[:, :, None, None]
     if t.dim() != 4:
-        raise ValueError(f'{name}: expected a 4-D (N, C, H, W) tensor, got shape {tuple(t.shape)}')
+        raise ValueError(f'{name}: expected ' + ('(N, C, H, W), (N, D, 1, 1) or (N, D)' if allow_2d else 'a 4-D (N, C, H, W) tensor')
+                         + f', got shape {tuple(t.shape)}')
     p = t.permute(0, 2, 3, 1)
     return p if p.is_contiguous() else p.contiguous()
+
+
+def _kd_pair(cur: torch.Tensor, prev: torch.Tensor, who: str):
+    if cur.shape != prev.shape or cur.dtype != prev.dtype:
+        raise ValueError(f'{who}: cur {tuple(cur.shape)} {cur.dtype} and prev {tuple(prev.shape)} {prev.dtype} differ')
+
+
+def _gscale(t: torch.Tensor, name: str) -> torch.Tensor:
+    """The upstream gradient of a distillation loss: one fp32 value in device memory."""
+    return _chk(t.reshape(1), (1,), name=name)
+
+
+def _with_strides_of(d_nhwc: torch.Tensor, cur: torch.Tensor) -> torch.Tensor:
+    """The (N, H, W, C) gradient storage ``d_nhwc`` as a tensor of ``cur``'s logical shape and strides: a view when ``cur`` holds its
+    elements in that order (channels-last maps, (N, D, 1, 1) and (N, D) features), one copy otherwise."""
+    d = d_nhwc.permute(0, 3, 1, 2).view(cur.shape)
+    if all(sd == sc for sd, sc, n in zip(d.stride(), cur.stride(), cur.shape) if n > 1):
+        return d.as_strided(cur.shape, cur.stride())     # only the strides of dimensions of length 1 can differ
+    out = torch.empty_like(cur)
+    out.copy_(d)
+    return out
 
 
 def pod_spatial_fwd(cur, prev):
     """POD-spatial distillation loss (csrc/pod_kd.hip) of logical (N, C, H, W) maps.  Returns ``(loss, G, cur_nhwc)``: the scalar,
     the profile gradient (N, H+W, C) fp32 and the (N, H, W, C) storage of ``cur`` that was read (``cur``'s own when it is
     channels-last), which together are what ``pod_spatial_bwd`` needs."""
-    a, b = _pod_nhwc(cur, 'pod_spatial: cur'), _pod_nhwc(prev, 'pod_spatial: prev')
-    if cur.shape != prev.shape or cur.dtype != prev.dtype:
-        raise ValueError(f'pod_spatial: cur {tuple(cur.shape)} {cur.dtype} and prev {tuple(prev.shape)} {prev.dtype} differ')
+    a, b = _kd_nhwc(cur, 'pod_spatial: cur'), _kd_nhwc(prev, 'pod_spatial: prev')
+    _kd_pair(cur, prev, 'pod_spatial')
     N, H, W, C = a.shape
     loss = torch.empty(1, dtype=torch.float32, device=a.device)
     G = torch.empty((N, H + W, C), dtype=torch.float32, device=a.device)
@@ -1581,56 +1604,28 @@ def pod_spatial_fwd(cur, prev):
 
 def pod_spatial_bwd(cur, G, gscale_dev):
     """``dcur = gscale * 2 * cur * (G[n,h,c] + G[n,H+w,c])`` for the logical (N, C, H, W) ``cur``, in ``cur``'s strides and dtype."""
-    a = _pod_nhwc(cur, 'pod_spatial_bwd: cur')
+    a = _kd_nhwc(cur, 'pod_spatial_bwd: cur')
     N, H, W, C = a.shape
     _chk(G, (N, H + W, C), name='pod_spatial_bwd: G')
-    _chk(gscale_dev.reshape(1), (1,), name='pod_spatial_bwd: gscale')
+    _gscale(gscale_dev, 'pod_spatial_bwd: gscale')
     d = torch.empty_like(a)
     check(lib().bdv_pod_spatial_bwd(_p(a), _p(G), _p(gscale_dev), _p(d), N, C, H, W, _act_code(a), _stream()), 'bdv_pod_spatial_bwd')
-    d = d.permute(0, 3, 1, 2)
-    if d.stride() == cur.stride():
-        return d
-    out = torch.empty_like(cur)
-    out.copy_(d)
-    return out
+    return _with_strides_of(d, cur)
 
 
 def pod_flat(cur, prev):
     """POD-flat (cosine embedding) distillation loss of (N, D) or (N, D, 1, 1) features.  Returns ``(loss, dcur_unit)`` with
     ``dcur_unit`` (N, D) fp32 the gradient for an upstream gradient of 1."""
-    for t, name in ((cur, 'cur'), (prev, 'prev')):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f'pod_flat: {name}: expected a tensor, got {type(t)}')
-        if not t.is_cuda:
-            raise RuntimeError(f'pod_flat: {name}: the HIP path needs a GPU tensor (got device {t.device}); there is no CPU fallback')
-    if cur.shape != prev.shape or cur.dtype != prev.dtype:
-        raise ValueError(f'pod_flat: cur {tuple(cur.shape)} {cur.dtype} and prev {tuple(prev.shape)} {prev.dtype} differ')
-    if cur.dim() not in (2, 4) or (cur.dim() == 4 and cur.shape[2] * cur.shape[3] != 1):
+    a, b = _kd_nhwc(cur, 'pod_flat: cur', allow_2d=True), _kd_nhwc(prev, 'pod_flat: prev', allow_2d=True)
+    _kd_pair(cur, prev, 'pod_flat')
+    N, H, W, D = a.shape
+    if H * W != 1:
         raise ValueError(f'pod_flat: expected (N, D) or (N, D, 1, 1) features, got shape {tuple(cur.shape)}')
-    N, D = cur.shape[0], cur.shape[1]
-    a, b = _chk_act(cur.reshape(N, D).contiguous(), name='pod_flat: cur'), _chk_act(prev.reshape(N, D).contiguous(), name='pod_flat: prev')
     loss = torch.empty(1, dtype=torch.float32, device=a.device)
     d = torch.empty((N, D), dtype=torch.float32, device=a.device)
     ws = workspace(lib().bdv_pod_workspace_bytes(N, D, 1, 1), a.device, 'pod')
     check(lib().bdv_pod_flat(_p(a), _p(b), _p(loss), _p(d), N, D, _p(ws), ws.numel(), _act_code(a), _stream()), 'bdv_pod_flat')
     return loss[0], d
-
-
-def _tc_nhwc(t: torch.Tensor, name: str, dtypes=(torch.float32, torch.bfloat16)) -> torch.Tensor:
-    """The (N, H, W, C) storage of a hooked KD module's output -- (N, C, H, W), (N, D, 1, 1) or (N, D): channels-last strides are
-    used in place, any other layout costs one copy."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f'{name}: expected a tensor, got {type(t)}')
-    if not t.is_cuda:
-        raise RuntimeError(f'{name}: the HIP path needs a GPU tensor (got device {t.device}); there is no CPU fallback')
-    if t.dtype not in dtypes:
-        raise TypeError(f'{name}: dtype {t.dtype}, expected one of {dtypes}')
-    if t.dim() == 2:
-        t = t[:, :, None, None]
-    if t.dim() != 4:
-        raise ValueError(f'{name}: expected (N, C, H, W), (N, D, 1, 1) or (N, D), got shape {tuple(t.shape)}')
-    p = t.permute(0, 2, 3, 1)
-    return p if p.is_contiguous() else p.contiguous()
 
 
 def _tc_map(table: torch.Tensor, N: int, C: int, name: str, what: str = 'importance') -> torch.Tensor:
@@ -1645,9 +1640,8 @@ def _tc_map(table: torch.Tensor, N: int, C: int, name: str, what: str = 'importa
 def kd_tc_fwd(cur, prev, importance):
     """Time-channel weighted distillation loss (csrc/tc_kd.hip): mean over all elements of ``importance[n mod T, c] * (cur - prev)^2``
     for hooked outputs of shape (N, C, H, W), (N, D, 1, 1) or (N, D) and an fp32 (T, C) map."""
-    a, b = _tc_nhwc(cur, 'kd_tc: cur'), _tc_nhwc(prev, 'kd_tc: prev')
-    if cur.shape != prev.shape or cur.dtype != prev.dtype:
-        raise ValueError(f'kd_tc: cur {tuple(cur.shape)} {cur.dtype} and prev {tuple(prev.shape)} {prev.dtype} differ')
+    a, b = _kd_nhwc(cur, 'kd_tc: cur', allow_2d=True), _kd_nhwc(prev, 'kd_tc: prev', allow_2d=True)
+    _kd_pair(cur, prev, 'kd_tc')
     N, H, W, C = a.shape
     A = _tc_map(importance, N, C, 'kd_tc')
     T = A.shape[0]
@@ -1659,28 +1653,21 @@ def kd_tc_fwd(cur, prev, importance):
 
 def kd_tc_bwd(cur, prev, importance, gscale_dev):
     """``dcur = gscale * 2 / numel * importance[n mod T, c] * (cur - prev)`` in ``cur``'s shape, strides and dtype."""
-    a, b = _tc_nhwc(cur, 'kd_tc_bwd: cur'), _tc_nhwc(prev, 'kd_tc_bwd: prev')
-    if cur.shape != prev.shape or cur.dtype != prev.dtype:
-        raise ValueError(f'kd_tc_bwd: cur {tuple(cur.shape)} {cur.dtype} and prev {tuple(prev.shape)} {prev.dtype} differ')
+    a, b = _kd_nhwc(cur, 'kd_tc_bwd: cur', allow_2d=True), _kd_nhwc(prev, 'kd_tc_bwd: prev', allow_2d=True)
+    _kd_pair(cur, prev, 'kd_tc_bwd')
     N, H, W, C = a.shape
     A = _tc_map(importance, N, C, 'kd_tc_bwd')
-    _chk(gscale_dev.reshape(1), (1,), name='kd_tc_bwd: gscale')
-    out = torch.empty_like(cur)                      # cur's strides when cur is dense
-    o4 = out[:, :, None, None] if out.dim() == 2 else out
-    d = o4.permute(0, 2, 3, 1)
-    direct = out.stride() == cur.stride() and d.is_contiguous()
-    if not direct:
-        d = torch.empty_like(a)
+    _gscale(gscale_dev, 'kd_tc_bwd: gscale')
+    # a is cur's own storage when cur is channels-last: a gradient allocated like it is then written in place, with no copy after
+    d = torch.empty_like(a)
     check(lib().bdv_kd_tc_bwd(_p(a), _p(b), _p(A), _p(gscale_dev), _p(d), N, A.shape[0], C, H, W, _act_code(a), _stream()), 'bdv_kd_tc_bwd')
-    if not direct:
-        o4.copy_(d.permute(0, 3, 1, 2))
-    return out
+    return _with_strides_of(d, cur)
 
 
 def tc_sqgrad_accum(S, grad, scale):
     """``S[t, c] += scale^2 * sum_{b,h,w} grad[b*T+t, c, h, w]^2`` in place, for an fp32 gradient at a hooked module and the fp32
     (T, C) accumulator ``S`` (csrc/tc_kd.hip): two stages in a fixed order, so ``S`` is bitwise reproducible."""
-    g = _tc_nhwc(grad, 'tc_sqgrad_accum: grad', dtypes=(torch.float32,))
+    g = _kd_nhwc(grad, 'tc_sqgrad_accum: grad', dtypes=(torch.float32,), allow_2d=True)
     N, H, W, C = g.shape
     _tc_map(S, N, C, 'tc_sqgrad_accum', 'S')
     T = S.shape[0]
